@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the wass_stereo dense-stereo hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--ndirs 5|8] [--config B|A|E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--ndirs 5|8] [--config B|A|E] [--full] [--dump-outputs DIR]
 
 One "step" = one synthetic rectified stereo pair pushed through the whole GPU hot path a1-a20 (SGBM, disparity
 clean-up, triangulation, outlier removal, RANSAC plane + refinement, mesh_cam.xyzC image in host memory).  The timed region
 cycles through up to 64 distinct frames per rank.  `value` is the rate of the pass that uploads both pictures of every frame
 from pinned host memory inside the step, one frame ahead ("H2D of 2 x 5 MB images + all kernels + D2H of the
-xyzC"; the boundary of the C++ driver hands over host buffers: decoded PNGs); the same steps with the inputs RESIDENT IN HBM
-when the clock starts are timed in the same run.  Both passes are always reported under the stable names `pcie_inclusive` and
+xyzC"; the boundary of the C++ driver hands over host buffers: decoded PNGs); with --full the same steps with the inputs RESIDENT
+IN HBM when the clock starts are timed in the same run.  The passes are reported under the stable names `pcie_inclusive` and
 `resident_inputs` (rounds 1-3 and 5: value = pcie_inclusive; round 4: value = resident_inputs; `value_is` says which).  With N > 1
 (one rank per GPU under torch.distributed.run; `--gpus N` without a launcher starts one) every rank processes its own
 frames -- stereo frames are independent, there is no data-path collective -- and the reported value is the whole-job
@@ -17,6 +17,9 @@ rate (weak scaling); the only exchange is the 40-byte plane all-reduce after the
 Prints ONE JSON line (rank 0) with BASELINE.json's metric plus
   roofline              -- path aggregation kernel family vs the 8 TB/s HBM roofline ((2R+4) B/cell)
   roofline_cost_volume  -- the cost-volume stage vs the packed-int16 VALU issue peak (it is not HBM-bound)
+A plain run stops there: set-up, warm-up, the timed steps and the line, with the figures that come out of the timed pass itself.
+--full adds everything that takes runs of its own: the second pass (the input mode that is not `value`), the roofline's
+`strict` probe and `kernel_ms`, and the sub-records below.
   cpu_baseline          -- the CPU oracle (5-path, whole path) timed on this box's host cores (rank 0, N = 1)
   cxx_driver            -- the shipped C++ sequence driver (wass_stereo_batch, one worker process per GPU) on a config-B sequence
                            of workdirs with every consumed output written: the product's own pairs/s, same run
@@ -28,6 +31,10 @@ Prints ONE JSON line (rank 0) with BASELINE.json's metric plus
                            JPEG-coded on the device
   mode_5path            -- config B in the mode the reference runs (MODE_SGBM, wass_stereo.cpp:775-777): pairs/s of the whole
                            chain, aggregation ms against its own (2*5+4) B/cell roofline
+
+--dump-outputs DIR writes what the timed pass computed in its last step as DIR/<name>.npy (float32 / float64): for the whole
+chain the frame's plane, point count and mesh_cam.xyzC (header and quantised points, a fixed seeded sample of rows when there are
+more than DUMP_MAX_POINTS), for --stage sgm the disparity map.  The inputs depend on the arguments only.
 """
 from __future__ import annotations
 
@@ -232,6 +239,36 @@ def repeat_check(planes, npts, warmup, nf):
         else:
             seen[k] = key
     return {"frames_revisited": revisits, "mismatches": int(bad)}
+
+
+DUMP_MAX_POINTS = 1_000_000        # rows of the xyzC point block written by --dump-outputs (12 + 8 bytes each)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def frame_output_arrays(o):
+    """The arrays a caller of the pipelined chain receives for one frame (wass_amd.batch.FrameOutput): the plane, the point count and
+    mesh_cam.xyzC split into its header (n, scale[3], min[3], Rinv[9], Tinv[3]; oracle/wass_oracle.c orc_encode_xyzc) and its
+    quantised points.  More than DUMP_MAX_POINTS points: a fixed, seeded sample of rows, their indices in `xyzc_point_rows`."""
+    blob = np.asarray(o.xyzc, dtype=np.uint8)
+    n = int(np.frombuffer(blob[:4].tobytes(), np.uint32)[0])
+    header = np.concatenate([[float(n)], np.frombuffer(blob[4:148].tobytes(), np.float64)])
+    pts = np.frombuffer(blob[148:148 + 6 * n].tobytes(), np.uint16).reshape(n, 3)
+    rows = np.arange(n, dtype=np.int64)
+    if n > DUMP_MAX_POINTS:
+        rows = np.sort(np.random.default_rng(20240607).choice(n, DUMP_MAX_POINTS, replace=False))
+    return {"plane": np.asarray(o.plane, np.float64), "n_points": np.array([o.n_points], np.float64), "xyzc_header": header,
+            "xyzc_points": pts[rows].astype(np.float32), "xyzc_point_rows": rows.astype(np.float64)}
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """DIR/<name>.npy for every array (float32 / float64 only, DUMP_MAX_BYTES in all)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def measured_traffic(config: str, ndirs: int):
@@ -585,6 +622,11 @@ def main():
     ap.add_argument("--allow-shared-gpu", action="store_true",
                     help="let several ranks share one GPU (rank r uses device r %% device_count): only for exercising the "
                          "multi-rank path on a single-GPU box; throughput numbers are then meaningless")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the second pass, the strict roofline probe, per-kernel times, the "
+                         "5-path, config E and SGM-stage-alone records, the C++ driver, wasscli_unchanged and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed pass computed in its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     # --gpus N without a launcher: become the launcher (one rank per GPU under torch.distributed.run, rendezvous on
@@ -685,10 +727,12 @@ def main():
         next frame's kernels."""
         planes, npts_hist, nbytes_hist, overflows = [], [], [], []
         kms = {}
+        last = [None]
 
         def keep(o):
             if o is not None:
                 planes.append(o.plane); npts_hist.append(o.n_points); nbytes_hist.append(len(o.xyzc)); overflows.append(o.cost_overflow)
+                last[0] = o
 
         def upload(i):
             dr, dl, dm = dring[i % NBUF]
@@ -752,17 +796,23 @@ def main():
         for k in range(max(steps - 2, 0), steps):
             take(ctx.sgm_call_timings(c0 + k + 1))
         return {"elapsed": time.perf_counter() - t0, "planes": planes, "npts": npts_hist, "nbytes": nbytes_hist, "overflows": overflows, "tm": tm,
-                "kernel_ms": {k: round(float(np.mean(v)), 3) for k, v in kms.items()}}
+                "kernel_ms": {k: round(float(np.mean(v)), 3) for k, v in kms.items()}, "last": last[0]}
 
     # the metric's pass includes the H2D of both pictures.  (Round 4 had the resident pass as `value`; the two
-    # differ by a fraction of a percent -- the 10 MB upload hides under the previous frame -- and both are always reported.)
+    # differ by a fraction of a percent -- the 10 MB upload hides under the previous frame -- and --full reports both.)
     resident_main = bool(args.resident_inputs)
     main_pass = run_pass(resident_main, args.steps, args.warmup)
     elapsed = main_pass["elapsed"]
     planes, npts_hist, nbytes_hist, overflows = main_pass["planes"], main_pass["npts"], main_pass["nbytes"], main_pass["overflows"]
     agg_ms, cost_ms, sel_ms, sgm_ms, vsum_ms = (main_pass["tm"][k] for k in ("agg", "cost", "sel", "sgm", "vsum"))
+    # the last timed step's outputs, before anything else runs on the context (the xyzC bytes live in the pipeline's pinned buffers)
+    if args.dump_outputs and rank == 0:
+        if args.stage == "sgm":
+            dump_outputs(args.dump_outputs, {"disparity16": sgm_out.cpu().numpy().astype(np.float32)})
+        else:
+            dump_outputs(args.dump_outputs, frame_output_arrays(main_pass["last"]))
     other_pass = None
-    if world == 1 and not args.no_pcie_pass:
+    if args.full and world == 1 and not args.no_pcie_pass:
         other_pass = run_pass(not resident_main, args.steps, min(args.warmup, 5))
     # The mode the reference actually runs: StereoSGBM::create leaves MODE_SGBM, five paths (wass_stereo.cpp:775-777).  Same
     # frames, same chain, same brackets, inputs uploaded inside the step like the headline pass.
@@ -770,14 +820,14 @@ def main():
     # the production kernel, best of three each, outside the timed region).  The probe re-launches the LAST call's form of the kernel,
     # so it comes right behind the pass it belongs to (round 5 probed after the 5-path pass and charged the 8-path record with the
     # 5-path kernel).
-    vsum_probe = ctx.sgm_probe_vsum()
+    vsum_probe = ctx.sgm_probe_vsum() if args.full else None
     # per-kernel times of the family (hipEvents around every launch, a few pipelined frames outside the timed passes): the record
     # can be re-derived from the line alone
     kernel_ms = None
-    if world == 1 and args.stage == "full":
+    if args.full and world == 1 and args.stage == "full":
         kernel_ms = run_pass(resident_main, 6, 2, kernel_events=True)["kernel_ms"]
     pass5 = vsum_probe5 = kernel_ms5 = None
-    if world == 1 and args.config == "B" and args.stage == "full" and args.ndirs == 8 and not args.no_5path:
+    if args.full and world == 1 and args.config == "B" and args.stage == "full" and args.ndirs == 8 and not args.no_5path:
         params5 = wass_amd.default_sgm_params(D, ndirs=5)
         pipe5 = FramePipeline(ctx, w, h, params5, geom, tail_overlap=tail_overlap)
         pass5 = run_pass(False, min(args.steps, 64), min(args.warmup, 5), pipe=pipe5, params=params5)
@@ -856,8 +906,6 @@ def main():
         #          in this run as the difference to the plain vertical sum on the same horizontal sums (wass_sgm_probe_vsum);
         #  with_fused_vertical_sum: that whole kernel charged to the family, its own algorithmic bytes included.
         t_vs = float(np.mean(vsum_ms)) * 1e-3
-        path2_marginal = max(0.0, vsum_probe[1] - vsum_probe[0]) * 1e-3
-        achieved_strict = alg_bytes / (t_agg + path2_marginal) / 1e9
         alg_fused = alg_bytes + cells * (4 + (2 if args.ndirs == 5 else 0))
         achieved_fused = alg_fused / (t_agg + t_vs) / 1e9
         t_cost = float(np.mean(cost_ms)) * 1e-3
@@ -894,11 +942,6 @@ def main():
                          # measured bytes over the measured time: how hard the memory system is driven (the guide's achievable
                          # HBM rate is ~6.3 TB/s); the gap between this and `achieved` is traffic beyond the algorithmic bytes
                          "effective_tbps": round(traffic[0] / t_agg / 1e12, 3) if traffic else None,
-                         "strict": {"achieved": round(achieved_strict, 1), "frac": round(achieved_strict / HBM_PEAK_GBS, 4),
-                                    "ms": round((t_agg + path2_marginal) * 1e3, 3),
-                                    "vertical_sum_ms": {"plain": round(vsum_probe[0], 3), "with_column_paths": round(vsum_probe[1], 3)},
-                                    "note": "same bytes; time = aggregation launches + what the column paths add to the cost stage's vertical "
-                                            "sum (measured in this run: production kernel minus plain sum on the same data)"},
                          "with_fused_vertical_sum": {"achieved": round(achieved_fused, 1), "frac": round(achieved_fused / HBM_PEAK_GBS, 4),
                                                      "algorithmic_bytes": alg_fused, "ms": round((t_agg + t_vs) * 1e3, 3)}},
             "roofline_cost_volume": {"bound": "valu", "kernel": "k_prefilter + k_hsum_q + k_vsum_col", "achieved": round(cost_tops, 2),
@@ -919,6 +962,14 @@ def main():
             "cost_overflow": int(overflow),
             "repeat_check": repeat_check(planes, npts_hist, args.warmup, nf),
         }
+        if vsum_probe is not None:
+            path2_marginal = max(0.0, vsum_probe[1] - vsum_probe[0]) * 1e-3
+            achieved_strict = alg_bytes / (t_agg + path2_marginal) / 1e9
+            line["roofline"]["strict"] = {"achieved": round(achieved_strict, 1), "frac": round(achieved_strict / HBM_PEAK_GBS, 4),
+                                          "ms": round((t_agg + path2_marginal) * 1e3, 3),
+                                          "vertical_sum_ms": {"plain": round(vsum_probe[0], 3), "with_column_paths": round(vsum_probe[1], 3)},
+                                          "note": "same bytes; time = aggregation launches + what the column paths add to the cost stage's vertical "
+                                                  "sum (measured in this run: production kernel minus plain sum on the same data)"}
         def pass_record(ps, steps, resident):
             return {"pairs_per_sec": round(world * steps / ps["elapsed"], 4), "ms_per_step": round(ps["elapsed"] / steps * 1e3, 3), "steps": steps,
                     "inputs": ("resident in HBM when the clock starts" if resident else
@@ -955,7 +1006,7 @@ def main():
                                                 "sum (production kernel minus plain sum on the same data, probed right behind this pass)"}},
                 "repeat_check": repeat_check(pass5["planes"], pass5["npts"], min(args.warmup, 5), nf),
                 "cost_overflow": int(max(pass5["overflows"])) if pass5["overflows"] else 0}
-        if world == 1 and args.config == "B" and args.stage == "full" and not args.no_config_e:
+        if args.full and world == 1 and args.config == "B" and args.stage == "full" and not args.no_config_e:
             ctx.close()
             ctx = None
             line["config_E"] = config_e_record(dev_index, args.ndirs)
@@ -964,7 +1015,7 @@ def main():
             # them 0.1-0.3 ms; this is the kernel family on its own, same brackets
             line["roofline"]["sgm_stage_alone"] = {k: v for k, v in config_e_record(dev_index, args.ndirs, steps=8, config="B").items()
                                                    if k in ("workload", "aggregate_ms", "cost_volume_ms", "sgm_total_ms", "roofline")}
-        if world == 1 and args.config == "B" and args.stage == "full" and not args.no_cxx_driver:
+        if args.full and world == 1 and args.config == "B" and args.stage == "full" and not args.no_cxx_driver:
             if ctx is not None:
                 ctx.close()
                 ctx = None
@@ -983,11 +1034,11 @@ def main():
                 line["wasscli_unchanged"] = wasscli_unchanged_record(args.ndirs)
             except Exception as e:
                 line["wasscli_unchanged"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.config)
     # N > 1: the PRODUCT's scaling point beside the harness's -- the shipped sequence driver with one worker per GPU, run by rank 0
     # once every rank has let go of its GPU (contexts closed, caches emptied; the ranks wait at the barrier below meanwhile)
-    multi_cxx = world > 1 and args.config == "B" and args.stage == "full" and not args.no_cxx_driver
+    multi_cxx = args.full and world > 1 and args.config == "B" and args.stage == "full" and not args.no_cxx_driver
     if multi_cxx:
         ctx.close()
         ctx = None

@@ -1,5 +1,8 @@
 import os
+import pathlib
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -32,3 +35,22 @@ def gpu_ctx():
     ctx = wass_amd.Context(0)
     yield ctx
     ctx.close()
+
+
+@pytest.fixture
+def sockroot(tmp_path):
+    """Where the tests make their socket directories.  A Unix socket's path holds at most 107 bytes (sun_path) and the server binds
+    <dir>/wass_stereo_<uid>_gpu<g>.sock -- a longer one makes every caller compute in-process -- so where pytest's tmp_path is too
+    deep for <tmp_path>/sockN/<name>, a short directory of the temporary area is used instead and removed afterwards."""
+    budget = 107 - len("/sock99/wass_stereo_4294967295_gpu99.sock")
+    if len(str(tmp_path)) <= budget:
+        yield tmp_path
+        return
+    for base in (tempfile.gettempdir(), "/tmp"):
+        if len(base) + len("/wss_XXXXXXXX") <= budget and os.access(base, os.W_OK):
+            d = tempfile.mkdtemp(prefix="wss_", dir=base)
+            break
+    else:
+        pytest.fail(f"no writable temporary directory short enough for a Unix socket path (tmp_path: {tmp_path})")
+    yield pathlib.Path(d)
+    shutil.rmtree(d, ignore_errors=True)

@@ -330,7 +330,7 @@ def test_raw_sequence_equals_prepare_then_stereo(prepare, tmp_path, save_undisto
 
 
 @pytest.mark.gpu
-def test_the_call_sequence_of_wasscli_prepare_and_stereo(prepare, tmp_path):
+def test_the_call_sequence_of_wasscli_prepare_and_stereo(prepare, tmp_path, sockroot):
     """What cli/wasscli/wasscli.py does, call for call, from its working directory with RELATIVE paths: find_wass_pipeline (:54-76: every
     program run without arguments must exit 0), do_prepare (:224-234: one wass_prepare per frame with an EMPTY argument where --demosaic
     would be, the output decoded as ASCII), do_stereo (:326-346: `wass_stereo config/stereo_config.txt output/%06d_wd`, four at a time,
@@ -344,7 +344,7 @@ def test_the_call_sequence_of_wasscli_prepare_and_stereo(prepare, tmp_path):
     root = tmp_path / "work"
     for d in ("config", "input/cam0", "input/cam1", "output"):
         (root / d).mkdir(parents=True)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     env = dict(os.environ, WASS_SERVER_DIR=str(sock), WASS_SERVER_IDLE="3", PATH=os.path.dirname(build.CLI) + os.pathsep + os.environ.get("PATH", ""))
     env.pop("WASS_NO_SERVER", None)

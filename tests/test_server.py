@@ -42,12 +42,12 @@ def _wait_gone(sockdir, seconds=15):
     return not _servers(sockdir)
 
 
-def test_server_is_started_on_demand_relays_log_and_exit_code_and_goes_away(cli, tmp_path):
+def test_server_is_started_on_demand_relays_log_and_exit_code_and_goes_away(cli, tmp_path, sockroot):
     import torch
     if torch.cuda.is_available():
         pytest.skip("the no-GPU behaviour is tested on the build container")
     wd, cfg, *_ = make_workdir(str(tmp_path), 160, 120, 32)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     a = subprocess.run([cli, cfg, wd], capture_output=True, text=True, env=_env(sock, WASS_DEBUG_IMAGES="0"))
     assert len(_servers(sock)) == 1                                   # started by the first caller, still there
@@ -62,7 +62,7 @@ def test_server_is_started_on_demand_relays_log_and_exit_code_and_goes_away(cli,
     assert not [f for f in os.listdir(sock) if f.endswith(".sock")]   # and took its socket with it
 
 
-def test_concurrent_callers_share_one_server(cli, tmp_path):
+def test_concurrent_callers_share_one_server(cli, tmp_path, sockroot):
     import torch
     if torch.cuda.is_available():
         pytest.skip("the no-GPU behaviour is tested on the build container")
@@ -72,7 +72,7 @@ def test_concurrent_callers_share_one_server(cli, tmp_path):
         t.mkdir()
         wd, cfg, *_ = make_workdir(str(t), 160, 120, 32, frame=i)
         wds.append((wd, cfg))
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     with ThreadPoolExecutor(4) as ex:
         res = list(ex.map(lambda wc: subprocess.run([cli, wc[1], wc[0]], capture_output=True, text=True, env=_env(sock, WASS_DEBUG_IMAGES="0")), wds))
@@ -83,7 +83,7 @@ def test_concurrent_callers_share_one_server(cli, tmp_path):
     _wait_gone(sock)
 
 
-def test_a_killed_server_costs_time_never_a_frame(cli, tmp_path):
+def test_a_killed_server_costs_time_never_a_frame(cli, tmp_path, sockroot):
     """The server is killed while idle (its socket file stays behind, nobody listens): the next caller finds the stale socket,
     takes the lock, starts a fresh server and gets its answer; a caller that cannot start one computes the frame itself."""
     import signal
@@ -91,7 +91,7 @@ def test_a_killed_server_costs_time_never_a_frame(cli, tmp_path):
     if torch.cuda.is_available():
         pytest.skip("the no-GPU behaviour is tested on the build container")
     wd, cfg, *_ = make_workdir(str(tmp_path), 160, 120, 32)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     a = subprocess.run([cli, cfg, wd], capture_output=True, text=True, env=_env(sock, WASS_DEBUG_IMAGES="0"))
     srv = _servers(sock)
@@ -111,9 +111,9 @@ def test_a_killed_server_costs_time_never_a_frame(cli, tmp_path):
     assert not _servers(notdir)
 
 
-def test_no_server_switch_and_ineligible_configurations_stay_in_process(cli, tmp_path):
+def test_no_server_switch_and_ineligible_configurations_stay_in_process(cli, tmp_path, sockroot):
     wd, cfg, *_ = make_workdir(str(tmp_path), 160, 120, 32)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     subprocess.run([cli, cfg, wd], capture_output=True, text=True, env=dict(_env(sock), WASS_NO_SERVER="1"))
     assert not os.listdir(sock)
@@ -125,7 +125,7 @@ def test_no_server_switch_and_ineligible_configurations_stay_in_process(cli, tmp
 
 
 @pytest.mark.gpu
-def test_four_concurrent_callers_over_32_workdirs_write_the_files_of_in_process_runs(cli, tmp_path):
+def test_four_concurrent_callers_over_32_workdirs_write_the_files_of_in_process_runs(cli, tmp_path, sockroot):
     w, h, D = 320, 240, 64
     nd, nrep = 8, 4
     seq_a, seq_b = tmp_path / "a", tmp_path / "b"
@@ -138,7 +138,7 @@ def test_four_concurrent_callers_over_32_workdirs_write_the_files_of_in_process_
             for seq in (seq_a, seq_b):
                 shutil.copytree(wd, seq / ("%06d_wd" % (rep * nd + i)))
     n = nd * nrep
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     for i in range(nd):                                                  # the reference's way, in-process: one per distinct frame is enough
         r = subprocess.run([cli, cfg, str(seq_a / ("%06d_wd" % i))], capture_output=True, text=True, env=dict(os.environ, WASS_NO_SERVER="1", WASS_DEBUG_IMAGES="0"))
@@ -162,11 +162,11 @@ def test_four_concurrent_callers_over_32_workdirs_write_the_files_of_in_process_
 
 
 @pytest.mark.gpu
-def test_server_draws_the_debug_pictures_too(cli, tmp_path):
+def test_server_draws_the_debug_pictures_too(cli, tmp_path, sockroot):
     wd, cfg, *_ = make_workdir(str(tmp_path), 320, 240, 64)
     wd2 = str(tmp_path / "b_wd")
     shutil.copytree(wd, wd2)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     a = subprocess.run([cli, cfg, wd], capture_output=True, text=True, env=dict(os.environ, WASS_NO_SERVER="1", WASS_DEBUG_FORMAT="png"))
     b = subprocess.run([cli, cfg, wd2], capture_output=True, text=True, env=_env(sock, WASS_DEBUG_FORMAT="png"))
@@ -209,7 +209,7 @@ def test_the_per_frame_client_carries_no_gpu_runtime_and_no_computation(cli, tmp
     assert not os.path.exists(os.path.join(wd, "mesh_cam.xyzC"))
 
 
-def test_read_ahead_decodes_the_next_workdirs_and_never_serves_a_changed_file(cli, tmp_path):
+def test_read_ahead_decodes_the_next_workdirs_and_never_serves_a_changed_file(cli, tmp_path, sockroot):
     """wasscli walks 000000_wd, 000001_wd, ... in order; after two requests from one sequence directory the server inflates the PNGs of
     the next workdirs before their callers exist (ReadAhead, stereo_server.hpp).  A pair decoded early is used only while both files
     are still the ones that were read: a picture replaced in between is decoded again."""
@@ -225,7 +225,7 @@ def test_read_ahead_decodes_the_next_workdirs_and_never_serves_a_changed_file(cl
     seq.mkdir()
     for i in range(6):
         shutil.copytree(wd, seq / ("%06d_wd" % i))
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     tlog = tmp_path / "timing.log"
     env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_SERVER_TIMING=str(tlog), WASS_SERVER_SPECULATE="0")     # (decode only; speculation has its own test)
@@ -254,7 +254,7 @@ def test_read_ahead_decodes_the_next_workdirs_and_never_serves_a_changed_file(cl
     assert " ahead " not in tlog.read_text()
 
 
-def test_on_a_multi_gpu_node_frame_i_goes_to_gpu_i_mod_g_and_each_server_reads_its_own_stride_ahead(cli, tmp_path):
+def test_on_a_multi_gpu_node_frame_i_goes_to_gpu_i_mod_g_and_each_server_reads_its_own_stride_ahead(cli, tmp_path, sockroot):
     """Callers pick the GPU by the number in the workdir's name (the sequence driver's rule, frame i -> GPU i mod G): wasscli's
     consecutive frames land on different GPUs, and the server of GPU g sees g, g+G, g+2G, ... -- which is what it reads ahead."""
     import torch
@@ -267,7 +267,7 @@ def test_on_a_multi_gpu_node_frame_i_goes_to_gpu_i_mod_g_and_each_server_reads_i
     seq.mkdir()
     for i in range(8):
         shutil.copytree(wd, seq / ("%06d_wd" % i))
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     tlog = tmp_path / "timing.log"
     env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_SERVER_TIMING=str(tlog), WASS_NUM_GPUS="2", WASS_SERVER_SPECULATE="0")
@@ -294,7 +294,7 @@ def test_on_a_multi_gpu_node_frame_i_goes_to_gpu_i_mod_g_and_each_server_reads_i
     _wait_gone(sock)
 
 
-def test_visibility_variables_and_foreign_parts_limit_the_gpus_a_caller_counts(cli, tmp_path):
+def test_visibility_variables_and_foreign_parts_limit_the_gpus_a_caller_counts(cli, tmp_path, sockroot):
     """Round-5 advisor: the GPU count came from the KFD topology alone -- on an 8-GPU node restricted to one device seven of eight callers
     asked for a GPU their server could not open.  The count is now what a server process of THIS environment could use: gfx950 nodes only
     (no APU / iGPU / CPU nodes), at most as many as HIP_VISIBLE_DEVICES & co. list."""
@@ -314,7 +314,7 @@ def test_visibility_variables_and_foreign_parts_limit_the_gpus_a_caller_counts(c
         shutil.copytree(wd, seq / ("%06d_wd" % i))
 
     def sockets(extra):
-        sock = tmp_path / ("sock%d" % len(os.listdir(tmp_path)))
+        sock = sockroot / ("sock%d" % len(os.listdir(sockroot)))
         sock.mkdir()
         env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_KFD_NODES=str(topo), WASS_SERVER_SPECULATE="0", WASS_SERVER_READAHEAD="0", **extra)
         for v in ("WASS_GPU_DEVICE", "WASS_NUM_GPUS", "HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "GPU_DEVICE_ORDINAL"):
@@ -332,7 +332,7 @@ def test_visibility_variables_and_foreign_parts_limit_the_gpus_a_caller_counts(c
     assert sockets({"WASS_NUM_GPUS": "3", "HIP_VISIBLE_DEVICES": "0"}) == ["0", "1", "2"]      # the override is an override
 
 
-def test_a_configuration_beyond_the_servers_limit_is_computed_by_its_caller(cli, tmp_path):
+def test_a_configuration_beyond_the_servers_limit_is_computed_by_its_caller(cli, tmp_path, sockroot):
     """Every distinct configuration text is a pipeline with a context and gigabytes of scratch of its own; the server holds at most
     WASS_SERVER_MAX_CONFIGS (4) of them and REFUSES a further one -- that caller computes its frame in-process -- instead of running
     the GPU out of memory for everybody (round-5 advisor)."""
@@ -342,7 +342,7 @@ def test_a_configuration_beyond_the_servers_limit_is_computed_by_its_caller(cli,
     wd, cfg, *_ = make_workdir(str(tmp_path), 160, 120, 32)
     cfg2 = str(tmp_path / "cfg2.txt")
     open(cfg2, "w").write(open(cfg).read() + "DENSE_UNIQUENESS_RATIO=5\n")
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     tlog = tmp_path / "timing.log"
     env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_SERVER_MAX_CONFIGS="1", WASS_SERVER_TIMING=str(tlog))
@@ -356,7 +356,7 @@ def test_a_configuration_beyond_the_servers_limit_is_computed_by_its_caller(cli,
 
 
 @pytest.mark.gpu
-def test_two_sequences_of_different_picture_size_share_one_server(cli, tmp_path):
+def test_two_sequences_of_different_picture_size_share_one_server(cli, tmp_path, sockroot):
     """Round-5 advisor (high): the server keeps up to three frames STAGED in front of the GPU; a frame of another picture size used to
     re-allocate the input buffers underneath them (same configuration text = same pipeline).  Two sequences of different cameras, four
     callers, interleaved: every file equals the in-process run's."""
@@ -381,7 +381,7 @@ def test_two_sequences_of_different_picture_size_share_one_server(cli, tmp_path)
         for i in range(nd):
             r = subprocess.run([cli, cfg, str(a / ("%06d_wd" % i))], capture_output=True, text=True, env=dict(os.environ, WASS_NO_SERVER="1", WASS_DEBUG_IMAGES="0"))
             assert r.returncode == 0, r.stdout[-1500:]
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     jobs = [str(seqs[i % 2][1] / ("%06d_wd" % (i // 2))) for i in range(2 * nd)]           # sizes alternate
     for rnd in range(2):                                                                   # (second round: speculated frames of both sizes in the cache)
@@ -397,7 +397,7 @@ def test_two_sequences_of_different_picture_size_share_one_server(cli, tmp_path)
 
 
 @pytest.mark.gpu
-def test_a_frame_sent_to_a_gpu_that_is_not_there_is_computed_by_its_caller(cli, tmp_path):
+def test_a_frame_sent_to_a_gpu_that_is_not_there_is_computed_by_its_caller(cli, tmp_path, sockroot):
     """Round-5 advisor: a caller picks GPU = frame number mod (GPUs it counts); where the count is too high (WASS_NUM_GPUS, or a topology that
     shows more than the runtime gives this process) the server of the missing device used to ANSWER "no usable GPU" and the frame was lost.
     It now refuses, and the caller computes the frame itself: on this one-GPU box with WASS_NUM_GPUS=2 every second frame takes that route."""
@@ -408,7 +408,7 @@ def test_a_frame_sent_to_a_gpu_that_is_not_there_is_computed_by_its_caller(cli, 
         shutil.copytree(wd, seq / ("%06d_wd" % i))
     ref = subprocess.run([cli, cfg, wd], capture_output=True, text=True, env=dict(os.environ, WASS_NO_SERVER="1", WASS_DEBUG_IMAGES="0"))
     assert ref.returncode == 0
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_NUM_GPUS="2")
     env.pop("WASS_GPU_DEVICE", None)
@@ -422,14 +422,14 @@ def test_a_frame_sent_to_a_gpu_that_is_not_there_is_computed_by_its_caller(cli, 
 
 
 @pytest.mark.gpu
-def test_the_server_applies_each_callers_options_not_its_own_environment(cli, tmp_path):
+def test_the_server_applies_each_callers_options_not_its_own_environment(cli, tmp_path, sockroot):
     """Round-5 advisor: WASS_DEBUG_FORMAT / WASS_HOST_INLIER_TEXT were forwarded and keyed but read from the SERVER's environment, i.e.
     from whichever caller had started it.  A server started without them serves a caller that sets them, and the other way round."""
     wd, cfg, *_ = make_workdir(str(tmp_path), 320, 240, 64)
     wds = [str(tmp_path / ("w%d_wd" % k)) for k in range(3)]
     for d in wds:
         shutil.copytree(wd, d)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     plain, png = _env(sock), _env(sock, WASS_DEBUG_FORMAT="png", WASS_HOST_INLIER_TEXT="1")
     for e in (plain, png):
@@ -449,7 +449,7 @@ def test_the_server_applies_each_callers_options_not_its_own_environment(cli, tm
     _wait_gone(sock)
 
 
-def test_the_server_survives_garbage_on_its_socket(cli, tmp_path):
+def test_the_server_survives_garbage_on_its_socket(cli, tmp_path, sockroot):
     """Anything may connect to a unix socket in /tmp: a wrong magic, a truncated request, an oversized length or a caller that hangs
     up early costs that connection only -- the next real caller is served by the same server."""
     import socket
@@ -458,7 +458,7 @@ def test_the_server_survives_garbage_on_its_socket(cli, tmp_path):
     if torch.cuda.is_available():
         pytest.skip("the no-GPU behaviour is tested on the build container")
     wd, cfg, *_ = make_workdir(str(tmp_path), 160, 120, 32)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     env = dict(_env(sock, WASS_DEBUG_IMAGES="0"), WASS_SERVER_IDLE="4")
     a = subprocess.run([cli, cfg, wd], capture_output=True, text=True, env=env)
@@ -506,7 +506,7 @@ def _seq(tmp_path, n, w=160, h=120, D=32):
     return seq, cfg
 
 
-def test_speculation_prepares_ahead_without_touching_the_workdir(cli, tmp_path):
+def test_speculation_prepares_ahead_without_touching_the_workdir(cli, tmp_path, sockroot):
     """After two requests from a sequence the worker builds (and, with a GPU, computes) the next workdirs' frames before anybody asks:
     until the caller comes NOTHING is written into such a workdir; then it holds what an ordinary call leaves.  A frame whose input
     changed in between is recomputed, one whose caller never comes is dropped."""
@@ -516,7 +516,7 @@ def test_speculation_prepares_ahead_without_touching_the_workdir(cli, tmp_path):
     if torch.cuda.is_available():
         pytest.skip("the no-GPU behaviour is tested on the build container")
     seq, cfg = _seq(tmp_path, 7)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     tlog = tmp_path / "timing.log"
     env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_SERVER_TIMING=str(tlog))
@@ -548,7 +548,7 @@ def test_speculation_prepares_ahead_without_touching_the_workdir(cli, tmp_path):
 
 
 @pytest.mark.gpu
-def test_frames_computed_ahead_of_their_callers_are_the_frames_of_in_process_runs(cli, tmp_path):
+def test_frames_computed_ahead_of_their_callers_are_the_frames_of_in_process_runs(cli, tmp_path, sockroot):
     """Speculation with a GPU: a slow caller finds most of its frames computed before it asks; what it gets is byte for byte what a process
     of its own writes -- also for a workdir whose pictures were replaced after the worker had computed the old ones."""
     import numpy as np
@@ -568,7 +568,7 @@ def test_frames_computed_ahead_of_their_callers_are_the_frames_of_in_process_run
     for i in range(nd):
         r = subprocess.run([cli, cfg, str(seq_a / ("%06d_wd" % i))], capture_output=True, text=True, env=dict(os.environ, WASS_NO_SERVER="1", WASS_DEBUG_IMAGES="0"))
         assert r.returncode == 0, r.stdout[-1500:]
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     tlog = tmp_path / "timing.log"
     env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_SERVER_TIMING=str(tlog))
@@ -590,14 +590,14 @@ def test_frames_computed_ahead_of_their_callers_are_the_frames_of_in_process_run
     assert sum(1 for v in rows.values() if v == "computed") >= n // 2, rows
 
 
-def test_speculation_on_a_multi_gpu_node_follows_each_servers_stride(cli, tmp_path):
+def test_speculation_on_a_multi_gpu_node_follows_each_servers_stride(cli, tmp_path, sockroot):
     """Two pretended GPUs, speculation on: the server of GPU g prepares g + 2, g + 4, ... ahead (never its neighbour's frames), hands
     them to their callers and leaves the workdirs nobody asked for untouched."""
     import torch
     if torch.cuda.is_available():
         pytest.skip("the no-GPU behaviour is tested on the build container")
     seq, cfg = _seq(tmp_path, 12)
-    sock = tmp_path / "sock"
+    sock = sockroot / "sock"
     sock.mkdir()
     tlog = tmp_path / "timing.log"
     env = _env(sock, WASS_DEBUG_IMAGES="0", WASS_SERVER_TIMING=str(tlog), WASS_NUM_GPUS="2")
