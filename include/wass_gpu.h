@@ -491,6 +491,51 @@ enum { WASS_GRID_CELL_MEAN = 0, WASS_GRID_CELL_MEDIAN = 1 };
 int wass_mesh_grid_idw_ex(wass_ctx* ctx, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, float* grid_out,
                           uint8_t* mask_out);
 
+/* ---- row f3, the reference's default interpolator: DCT surface interpolation -----------------------------------------
+ * gridding/wassgridsurface/DCTInterpolator.py (wassgridsurface --ia DCT, the default: wassgridsurface.py:639): the cell map I
+ * (NaN = no data) is fitted by the first nfreqs x nfreqs coefficients x of an orthonormal DCT-III basis, Irec = A_y^T x A_x,
+ * minimising sum M (Irec - I)^2 / sum M + regularizer_alpha |x|_1 with torch.optim.Rprop (etas 0.5 / 1.2, step sizes
+ * 1e-6 / 50) for max_iters + 1 steps; every 50th step stops when max |x_i - x_(i-1)| < tolerance_change.  grid_out
+ * (height x width float32) is Irec of the final x, NaN where user_mask (height x width bytes, may be NULL) is 0
+ * (wassgridsurface.py:355-357).  Extension: a rectangular grid uses a basis of size height for the rows and one of size
+ * width for the columns (the reference raises a shape error unless width == height, where both agree).
+ * x0 (nfreqs x nfreqs, may be NULL): the start value, e.g. the coeffs_out of the previous frame; NULL draws a deterministic
+ * uniform [0, 1) one from opts->seed (the reference's torch.rand stream is not reproduced).  coeffs_out (nfreqs^2, may be
+ * NULL): the final x.  Returns WASS_ERR_INVALID_ARG for nfreqs outside [1, min(width, height)] and WASS_ERR_TOO_FEW_POINTS
+ * (grid_out all NaN) for a map without data.  The same inputs give the same bits on every run.  The solve runs on the
+ * context's stream and the call returns when it has finished (the host checks the tolerance once per 50 steps). */
+typedef struct {
+    int    nfreqs;                  /* Nfreqs             (150)   */
+    int    max_iters;               /* MAX_ITERS          (500)   */
+    double tolerance_change;        /* TOLERANCE_CHANGE   (1e-4)  */
+    double regularizer_alpha;       /* REGULARIZER_ALPHA  (8e-7)  */
+    double learning_rate;           /* LEARNING_RATE      (5.0)   */
+    uint64_t seed;                  /* start value when x0 is NULL (0) */
+} wass_dct_opts;
+typedef struct {
+    int    steps;                   /* Rprop steps run                                   */
+    int    converged;               /* 1: stopped by tolerance_change                    */
+    double data_loss;               /* sum M (Irec - I)^2 / sum M of the final x         */
+    double reg_loss;                /* |x|_1 of the final x                              */
+    double fdelta;                  /* max |x_i - x_(i-1)| at the last check             */
+} wass_dct_info;
+void wass_dct_opts_default(wass_dct_opts* opts);
+int wass_grid_dct(wass_ctx* ctx, const float* zz, int width, int height, const wass_dct_opts* opts, const float* x0,
+                  const uint8_t* user_mask, float* grid_out, float* coeffs_out, wass_dct_info* info);
+/* the same on device pointers (zz, x0, user_mask, grid_out, coeffs_out) */
+int wass_grid_dct_dev(wass_ctx* ctx, const float* zz, int width, int height, const wass_dct_opts* opts, const float* x0,
+                      const uint8_t* user_mask, float* grid_out, float* coeffs_out, wass_dct_info* info);
+/* From the resident mesh: the alignment and binning of wass_mesh_grid_idw_ex (cell_statistic), then the solve above, with no
+ * trip through the host.  cells_out (height x width float32, may be NULL): the binned cell map it solved on, NaN = empty
+ * cell (the reference's ZZ). */
+int wass_mesh_grid_dct(wass_ctx* ctx, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, const wass_dct_opts* opts,
+                       const float* x0, const uint8_t* user_mask, float* grid_out, float* cells_out, float* coeffs_out,
+                       wass_dct_info* info);
+/* One evaluation at x (nfreqs^2, host pointers): grad_out = the gradient of the loss above (alpha sign(x) included,
+ * sign(0) = 0), data_loss and reg_loss = |x|_1 (either may be NULL).  For tests and for callers with their own optimiser. */
+int wass_grid_dct_eval(wass_ctx* ctx, const float* zz, int width, int height, int nfreqs, double alpha, const float* x,
+                       float* grad_out, double* data_loss, double* reg_loss);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

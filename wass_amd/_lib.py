@@ -60,6 +60,18 @@ class GridSetup(C.Structure):
                 ("ymin", C.c_double), ("ymax", C.c_double), ("width", C.c_int), ("height", C.c_int)]
 
 
+class DctOpts(C.Structure):
+    """wass_dct_opts"""
+    _fields_ = [("nfreqs", C.c_int), ("max_iters", C.c_int), ("tolerance_change", C.c_double), ("regularizer_alpha", C.c_double),
+                ("learning_rate", C.c_double), ("seed", C.c_uint64)]
+
+
+class DctInfo(C.Structure):
+    """wass_dct_info"""
+    _fields_ = [("steps", C.c_int), ("converged", C.c_int), ("data_loss", C.c_double), ("reg_loss", C.c_double),
+                ("fdelta", C.c_double)]
+
+
 class Geom(C.Structure):
     """wass_geom"""
     _fields_ = [("K_left", C.c_double * 9), ("K_right", C.c_double * 9), ("R", C.c_double * 9), ("T", C.c_double * 3),
@@ -167,6 +179,11 @@ SYMBOLS = {
     "wass_free": (None, [_vp]),
     "wass_mesh_grid_idw": (_i, [_vp, _vp, C.POINTER(GridSetup), _vp, _vp]),
     "wass_mesh_grid_idw_ex": (_i, [_vp, _vp, C.POINTER(GridSetup), _i, _vp, _vp]),
+    "wass_dct_opts_default": (None, [C.POINTER(DctOpts)]),
+    "wass_grid_dct": (_i, [_vp, _vp, _i, _i, C.POINTER(DctOpts), _vp, _vp, _vp, _vp, C.POINTER(DctInfo)]),
+    "wass_grid_dct_dev": (_i, [_vp, _vp, _i, _i, C.POINTER(DctOpts), _vp, _vp, _vp, _vp, C.POINTER(DctInfo)]),
+    "wass_mesh_grid_dct": (_i, [_vp, _vp, C.POINTER(GridSetup), _i, C.POINTER(DctOpts), _vp, _vp, _vp, _vp, _vp, C.POINTER(DctInfo)]),
+    "wass_grid_dct_eval": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

@@ -124,6 +124,7 @@ struct wass_ctx {
     wass::Buf rs_r, rs_l;          // DENSE_SCALE != 1: resized SGBM inputs
     wass::Buf raw2;                // speckle filter: median-filtered padded disparity
     wass::Buf grid;                // wass_mesh_grid_idw: accumulators and maps of the surface grid (grid.hip)
+    wass::Buf dct, dct_io;         // wass_grid_dct*: bases, state and partial slabs of the solve / host-pointer staging (grid_dct.hip)
     wass::Buf counters;            // striped atomics of the mesh stages
     wass::Buf tri_cnt;             // striped count of the points the last triangulation produced (read by the frame tail)
     wass::Buf inl;                 // every n-th refinement inlier of the frame tail (plane_refinement_inliers.xyz)

@@ -167,10 +167,23 @@ __global__ void __launch_bounds__(256) k_grid_close(const double* __restrict__ z
 
 using namespace wass;
 
-extern "C" int wass_mesh_grid_idw_ex(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, float* grid_out,
-                                     uint8_t* mask_out)
+namespace wass {
+
+// the binned cell map as float32, NaN where no point fell (the ZZ the reference hands to its interpolator, :345)
+__global__ void __launch_bounds__(256) k_grid_cells_f32(const double* __restrict__ cellval, const unsigned int* __restrict__ cnt, size_t ng,
+                                                        float* __restrict__ cells)
 {
-    if (!c || !m || !gs || !grid_out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ng) return;
+    cells[c] = cnt[c] ? (float)cellval[c] : __builtin_nanf("");
+}
+
+// Alignment and binning shared by the interpolators: fills c->grid and returns the per-cell values (fp64) and counts.
+// With d_cells != NULL also writes the height x width float32 cell map there (NaN = empty cell).  Enqueued on c->ts().
+static int grid_bin(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, GridDev& g, double** cellval_out,
+                    unsigned int** cnt_out, float** out_p, uint8_t** dil_p, uint8_t** mask_p, double** zi_p, float* d_cells)
+{
+    if (!c || !m || !gs) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     if (gs->width < 2 || gs->height < 2 || !(gs->xmax > gs->xmin) || !(gs->ymax > gs->ymin)) return set_err(c, WASS_ERR_INVALID_ARG, "bad grid");
     if (cell_statistic != WASS_GRID_CELL_MEAN && cell_statistic != WASS_GRID_CELL_MEDIAN) return set_err(c, WASS_ERR_INVALID_ARG, "unknown cell statistic");
     WASS_HIP(c, hipSetDevice(c->device));
@@ -193,13 +206,12 @@ extern "C" int wass_mesh_grid_idw_ex(wass_ctx* c, const wass_mesh* m, const wass
     unsigned int* pcell = fill + ng;                         // median mode only
     uint8_t* dil = (uint8_t*)(pcell + (median ? n : 0));
     uint8_t* mask = dil + ng;
-    GridDev g;
     memcpy(g.R, gs->R, sizeof g.R); memcpy(g.T, gs->T, sizeof g.T);
     g.baseline = gs->baseline; g.xmin = gs->xmin; g.ymin = gs->ymin;
     g.sx = (gs->width - 1) / (gs->xmax - gs->xmin); g.sy = (gs->height - 1) / (gs->ymax - gs->ymin);
     g.gw = gs->width; g.gh = gs->height;
     hipStream_t s = c->ts();
-    const dim3 gg((gs->width + 255) / 256, gs->height), blk(256), gp((unsigned)((n + 255) / 256)), gc((unsigned)((ng + 255) / 256));
+    const dim3 blk(256), gp((unsigned)((n + 255) / 256)), gc((unsigned)((ng + 255) / 256));
     WASS_HIP(c, hipMemsetAsync(cnt, 0, ng * 4, s));
     if (median) {
         WASS_HIP(c, hipMemsetAsync(fill, 0, ng * 4, s));
@@ -212,6 +224,39 @@ extern "C" int wass_mesh_grid_idw_ex(wass_ctx* c, const wass_mesh* m, const wass
         hipLaunchKernelGGL(k_grid_scatter, gp, blk, 0, s, m->valid, m->x, m->y, m->z, n, g, sum, cnt);
         hipLaunchKernelGGL(k_grid_cell_mean, gc, blk, 0, s, (const long long*)sum, (const unsigned int*)cnt, ng, cellval);
     }
+    if (d_cells) hipLaunchKernelGGL(k_grid_cells_f32, gc, blk, 0, s, (const double*)cellval, (const unsigned int*)cnt, ng, d_cells);
+    WASS_HIP(c, hipGetLastError());
+    if (cellval_out) *cellval_out = cellval;
+    if (cnt_out) *cnt_out = cnt;
+    if (out_p) *out_p = out;
+    if (dil_p) *dil_p = dil;
+    if (mask_p) *mask_p = mask;
+    if (zi_p) *zi_p = zi;
+    return WASS_OK;
+}
+
+int grid_cells_dev(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, float* d_cells)
+{
+    GridDev g;
+    return grid_bin(c, m, gs, cell_statistic, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_cells);
+}
+
+}  // namespace wass
+
+extern "C" int wass_mesh_grid_idw_ex(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, float* grid_out,
+                                     uint8_t* mask_out)
+{
+    if (!c || !m || !gs || !grid_out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    GridDev g;
+    double *cellval, *zi;
+    unsigned int* cnt;
+    float* out;
+    uint8_t *dil, *mask;
+    int rc;
+    if ((rc = grid_bin(c, m, gs, cell_statistic, g, &cellval, &cnt, &out, &dil, &mask, &zi, nullptr))) return rc;
+    const size_t ng = (size_t)gs->width * gs->height;
+    hipStream_t s = c->ts();
+    const dim3 gg((gs->width + 255) / 256, gs->height), blk(256);
     hipLaunchKernelGGL(k_grid_idw, gg, blk, 0, s, (const double*)cellval, (const unsigned int*)cnt, g.gw, g.gh, zi, dil);
     hipLaunchKernelGGL(k_grid_close, gg, blk, 0, s, (const double*)zi, (const uint8_t*)dil, g.gw, g.gh, out, mask);
     WASS_HIP(c, hipGetLastError());

@@ -347,6 +347,44 @@ class Context:
             C.byref(n) if count else None))
         return Mesh(self, h), (int(n.value) if count else None)
 
+    def grid_dct(self, zz: np.ndarray, dct_options=None, x0=None, user_mask=None, seed: int = 0):
+        """DCT surface interpolation of the cell map zz (height x width, NaN = no data; DCTInterpolator.py): (float32 grid, float32
+        coefficients nfreqs x nfreqs, info dict).  dct_options: the reference's names (Nfreqs, MAX_ITERS, TOLERANCE_CHANGE,
+        REGULARIZER_ALPHA, LEARNING_RATE); x0: start value (default: uniform [0, 1) drawn from seed); user_mask: NaN where 0."""
+        zz = np.ascontiguousarray(zz, np.float32)
+        h, w = zz.shape
+        o = dct_opts(dct_options, seed)
+        x0c = None if x0 is None else np.ascontiguousarray(x0, np.float32).reshape(o.nfreqs, o.nfreqs)
+        um = None if user_mask is None else np.ascontiguousarray(user_mask, np.uint8).reshape(h, w)
+        grid = np.empty((h, w), np.float32)
+        coeffs = np.empty((max(o.nfreqs, 1), max(o.nfreqs, 1)), np.float32)      # invalid nfreqs: the library reports it
+        info = _lib.DctInfo()
+        self._check(self._lib.wass_grid_dct(self._h, zz.ctypes.data, w, h, C.byref(o), None if x0c is None else x0c.ctypes.data,
+                                            None if um is None else um.ctypes.data, grid.ctypes.data, coeffs.ctypes.data, C.byref(info)))
+        return grid, coeffs, dct_info(info)
+
+    def grid_dct_dev(self, d_zz, d_out, dct_options=None, d_x0=None, d_user_mask=None, d_coeffs=None, seed: int = 0):
+        """grid_dct on device tensors (float32 zz and out, height x width contiguous); returns the info dict."""
+        h, w = d_zz.shape
+        o = dct_opts(dct_options, seed)
+        info = _lib.DctInfo()
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        self._check(self._lib.wass_grid_dct_dev(self._h, d_zz.data_ptr(), w, h, C.byref(o), ptr(d_x0), ptr(d_user_mask), d_out.data_ptr(),
+                                                ptr(d_coeffs), C.byref(info)))
+        return dct_info(info)
+
+    def grid_dct_eval(self, zz: np.ndarray, x: np.ndarray, alpha: float = 8e-7):
+        """One evaluation of the DCT interpolator's loss at x (nfreqs x nfreqs): (float32 gradient, data loss, |x|_1)."""
+        zz = np.ascontiguousarray(zz, np.float32)
+        x = np.ascontiguousarray(x, np.float32)
+        h, w = zz.shape
+        nf = x.shape[0]
+        g = np.empty((nf, nf), np.float32)
+        dl, rl = C.c_double(), C.c_double()
+        self._check(self._lib.wass_grid_dct_eval(self._h, zz.ctypes.data, w, h, nf, float(alpha), x.ctypes.data, g.ctypes.data,
+                                                 C.byref(dl), C.byref(rl)))
+        return g, dl.value, rl.value
+
     def mesh_upload(self, valid, p3d, gray=None):
         valid = np.ascontiguousarray(valid, np.uint8)
         p3d = np.ascontiguousarray(p3d, np.float64)
@@ -426,6 +464,28 @@ def init_rectify_map(K, R, P, width: int, height: int):
     return mx, my
 
 
+_DCT_NAMES = {"Nfreqs": "nfreqs", "MAX_ITERS": "max_iters", "TOLERANCE_CHANGE": "tolerance_change",
+              "REGULARIZER_ALPHA": "regularizer_alpha", "LEARNING_RATE": "learning_rate"}
+
+
+def dct_opts(dct_options=None, seed: int = 0) -> _lib.DctOpts:
+    """wass_dct_opts from a dict with the reference's option names (DCTInterpolator._get_setting_helper); None = default."""
+    o = _lib.DctOpts()
+    _lib.load().wass_dct_opts_default(C.byref(o))
+    for k, v in (dct_options or {}).items():
+        if k not in _DCT_NAMES:
+            raise KeyError(f"unknown DCT option {k!r}")
+        if v is not None:
+            setattr(o, _DCT_NAMES[k], v)
+    o.seed = int(seed)
+    return o
+
+
+def dct_info(info: _lib.DctInfo) -> dict:
+    return {"steps": info.steps, "converged": bool(info.converged), "data_loss": info.data_loss, "reg_loss": info.reg_loss,
+            "fdelta": info.fdelta}
+
+
 class Mesh:
     """Device-resident organised point cloud (wass_mesh) -- the PovMesh of the reference."""
 
@@ -466,6 +526,25 @@ class Mesh:
         self.ctx._check(self.ctx._lib.wass_mesh_grid_idw_ex(self.ctx._h, self._h, C.byref(gs), {"mean": 0, "median": 1}[cell], grid.ctypes.data,
                                                             mask.ctypes.data))
         return grid, mask
+
+    def grid_dct(self, plane, baseline: float, xmin: float, xmax: float, ymin: float, ymax: float, width: int, height: int,
+                 cell: str = "mean", dct_options=None, x0=None, user_mask=None, seed: int = 0):
+        """Surface grid of this cloud aligned on `plane` with the DCT interpolator (wassgridsurface.py:316-365, the default --ia DCT):
+        (float32 grid, float32 cell map it solved on (NaN = empty), float32 coefficients, info dict)."""
+        gs = _lib.GridSetup()
+        R, T, _, _ = RT_from_plane(plane)
+        gs.R[:] = np.asarray(R, float).ravel().tolist(); gs.T[:] = np.asarray(T, float).ravel().tolist()
+        gs.baseline, gs.xmin, gs.xmax, gs.ymin, gs.ymax, gs.width, gs.height = baseline, xmin, xmax, ymin, ymax, width, height
+        o = dct_opts(dct_options, seed)
+        x0c = None if x0 is None else np.ascontiguousarray(x0, np.float32).reshape(o.nfreqs, o.nfreqs)
+        um = None if user_mask is None else np.ascontiguousarray(user_mask, np.uint8).reshape(height, width)
+        grid = np.empty((height, width), np.float32); cells = np.empty((height, width), np.float32)
+        coeffs = np.empty((max(o.nfreqs, 1), max(o.nfreqs, 1)), np.float32)
+        info = _lib.DctInfo()
+        self.ctx._check(self.ctx._lib.wass_mesh_grid_dct(self.ctx._h, self._h, C.byref(gs), {"mean": 0, "median": 1}[cell], C.byref(o),
+                                                         None if x0c is None else x0c.ctypes.data, None if um is None else um.ctypes.data,
+                                                         grid.ctypes.data, cells.ctypes.data, coeffs.ctypes.data, C.byref(info)))
+        return grid, cells, coeffs, dct_info(info)
 
     def zgap_percentile(self, pct: float):
         out = C.c_double(); n = C.c_uint64()
