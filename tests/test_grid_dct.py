@@ -65,3 +65,74 @@ def test_grid_dct_isa_has_no_wide_buffer_store_with_sgpr_offset(tmp_path):
     assert "v_mfma_f32_16x16x4_f32" in asm or "v_mfma_f32_16x16x4f32" in asm
     bad = re.findall(r"buffer_store_dwordx[34]\s+[^\n]*\],\s*s\d+[^\n]*", asm)
     assert not bad, f"{len(bad)} wide buffer stores with an SGPR offset, e.g. {bad[0].strip()}"
+
+
+# ---- the helpers of the shape sweep (tests/test_grid_dct_shapes_gpu.py): the probe's closed form and what the case table reaches
+# Bound: the closed form and evaluate() use the same f32 bases; the closed form rounds four f32 products and one difference
+# (|ir| < |z|, so the difference amplifies nothing), fp64 rounds none of them to f32: <= 4 * 2^-23 relative.
+@pytest.mark.parametrize("shape,cell,coef", [
+    ((50, 37, 33), (49, 36), (5, 32)), ((50, 37, 33), (0, 0), None), ((17, 33, 17), (16, 32), (16, 16)),
+    ((176, 176, 176), (15, 16), (160, 159)), ((330, 322, 321), (329, 321), (320, 320)), ((24, 2300, 20), (16, 2299), (0, 0)),
+    ((1, 40, 1), (0, 39), (0, 0)), ((40, 1, 1), (39, 0), None)])
+def test_probe_closed_form_matches_fp64(shape, cell, coef):
+    H, W, nf = shape
+    zz = np.full((H, W), np.nan, np.float32)
+    zz[cell] = 0.37
+    x = np.zeros((nf, nf), np.float32)
+    if coef is not None:
+        x[coef] = 0.5
+    gr, dlr, _ = D.evaluate(zz, x, 0.0, np.float64)
+    g, dl = D.probe_expected(H, W, nf, cell, 0.37, coef)
+    assert g.shape == (nf, nf) and g.dtype == np.float32
+    assert (np.abs(g - gr) <= 4 * 2.0 ** -23 * np.abs(gr) + 1e-37).all()
+    assert abs(dl - dlr) <= 4 * 2.0 ** -23 * dlr
+
+
+def test_probe_two_cells_add():
+    """count = 2 halves cs and the loss: the sum of the two closed forms is the fp64 gradient of the two-cell grid."""
+    H, W, nf = 50, 37, 33
+    zz = np.full((H, W), np.nan, np.float32)
+    zz[0, 0] = zz[H - 1, W - 1] = 0.37
+    gr, dlr, _ = D.evaluate(zz, np.zeros((nf, nf), np.float32), 0.0, np.float64)
+    a, la = D.probe_expected(H, W, nf, (0, 0), 0.37, count=2)
+    b, lb = D.probe_expected(H, W, nf, (H - 1, W - 1), 0.37, count=2)
+    assert (np.abs(a + b - gr) <= 8 * 2.0 ** -23 * np.maximum(np.abs(a), np.abs(b)) + 1e-37).all()
+    assert abs(la + lb - dlr) <= 1e-6 * dlr
+
+
+def test_shape_cases_reach_every_launch_plan():
+    """The case table covers what it claims: every k_dct_resid<NFT>, two and three passes, nchunk 1 and 8, a shorter last chunk,
+    a tpc above 4 that the four waves do not split evenly, waves without a tile, and small, odd and aligned sizes on both axes."""
+    plans = {c: D.plan(*c) for c in D.SHAPE_CASES}
+    assert len(set(D.SHAPE_CASES)) == len(D.SHAPE_CASES)
+    for (H, W, nf), p in plans.items():
+        assert 1 <= nf <= min(H, W)
+        assert (p["nchunk"] - 1) * p["tpc"] + p["last"] == p["Wp"] // 16 and 1 <= p["last"] <= p["tpc"] and 1 <= p["nchunk"] <= 8
+        assert sum(p["nft"]) == p["nfp"] // 16 and all(n == 10 for n in p["nft"][:-1])
+    assert {n for p in plans.values() for n in p["nft"]} == set(range(1, 11))
+    assert {len(p["nft"]) for p in plans.values()} >= {1, 2, 3}
+    assert {p["nchunk"] for p in plans.values()} >= {1, 8}
+    assert any(p["tpc"] >= 2 and p["last"] < p["tpc"] for p in plans.values())
+    assert any(p["tpc"] > 4 and p["tpc"] % 4 for p in plans.values())
+    assert any(p["tpc"] < 4 for p in plans.values())                  # t_end < RESID_WAVES: waves that hold only zeros
+    for axis in (0, 1):
+        sizes = {c[axis] for c in D.SHAPE_CASES}
+        assert any(s < 16 for s in sizes) and 1 in sizes
+        assert any(s % 2 and s > 16 for s in sizes)
+        assert any(s % 16 == 0 for s in sizes)
+
+
+def test_plan_matches_the_source():
+    """plan() restates constants of grid_dct.hip: fail when they move."""
+    src = open(os.path.join(ROOT, "wass_amd", "csrc", "grid_dct.hip")).read()
+    for line in ("constexpr int RESID_WAVES = 4;", "constexpr int FT_GROUP = 10;", "int nchunk = (512 + nrb - 1) / nrb;",
+                 "if (nchunk > 8) nchunk = 8;", "p.tpc = (nct + nchunk - 1) / nchunk;", "p.nchunk = (nct + p.tpc - 1) / p.tpc;"):
+        assert line in src, line
+
+
+def test_seeded_start_restatement():
+    x = D.splitmix_x0(0, 4)
+    assert x.dtype == np.float32 and ((x >= 0) & (x < 1)).all() and len(np.unique(x)) == 16
+    # splitmix64's first output for state 0 is 0xE220A8397B1DCDAF (the published test vector): its top 24 bits
+    assert x[0, 0] == np.float32(0xE220A8 / 16777216.0)
+    assert not np.array_equal(D.splitmix_x0(1, 4), x)
