@@ -536,6 +536,60 @@ int wass_mesh_grid_dct(wass_ctx* ctx, const wass_mesh* m, const wass_grid_setup*
 int wass_grid_dct_eval(wass_ctx* ctx, const float* zz, int width, int height, int nfreqs, double alpha, const float* x,
                        float* grad_out, double* data_loss, double* reg_loss);
 
+/* ---- row f3, the sequence layer: what wassgridsurface --action grid does with the frames of a sequence -----------------
+ * gridding/wassgridsurface/wassgridsurface.py:235-591 (grid): every frame binned, interpolated, masked, optionally median
+ * filtered (--mf), pushed as millimetres into a count x Y x X cube, with the sequence's zmin / zmax / zmean, the per-point
+ * average elevation and, with -z / --force-zero-mean, that average subtracted from every surface. */
+/* Several cell maps of one shape in one DCT solve.  zz, grid_out: n_frames x height x width float32, contiguous; x0,
+ * coeffs_out: n_frames x nfreqs x nfreqs or NULL (NULL x0: every frame starts from the seeded draw of opts->seed, as
+ * wass_grid_dct does for each of them); user_mask: ONE height x width byte map for all frames, or NULL; info (may be NULL) and
+ * status: n_frames entries.  Frame i is bit for bit what wass_grid_dct returns for zz[i], x0[i] and the same options: grid,
+ * coefficients, steps, converged, data_loss, reg_loss, fdelta (the frames share launches, never a sum).  The stopping rule is
+ * per frame: a frame below tolerance_change at a check step is finished and is not stepped again while the others go on.  A
+ * frame without data gets an all-NaN grid, status[i] = WASS_ERR_TOO_FEW_POINTS and a zeroed info[i] (its coeffs_out are not
+ * written) and does not disturb the others; status[i] = WASS_OK otherwise, and the call returns WASS_OK when the batch ran.
+ * n_frames < 1 and the argument errors of wass_grid_dct return WASS_ERR_INVALID_ARG.  A large n_frames is walked in sub-batches
+ * (scratch below 1 GiB); results do not depend on that. */
+int wass_grid_dct_batch(wass_ctx* ctx, const float* zz, int n_frames, int width, int height, const wass_dct_opts* opts,
+                        const float* x0, const uint8_t* user_mask, float* grid_out, float* coeffs_out, wass_dct_info* info,
+                        int* status);
+/* the same on device pointers (zz, x0, user_mask, grid_out, coeffs_out); info and status are host memory */
+int wass_grid_dct_batch_dev(wass_ctx* ctx, const float* zz, int n_frames, int width, int height, const wass_dct_opts* opts,
+                            const float* x0, const uint8_t* user_mask, float* grid_out, float* coeffs_out, wass_dct_info* info,
+                            int* status);
+/* The alignment and binning of wass_mesh_grid_idw_ex / wass_mesh_grid_dct alone (:316-346): the height x width float32 cell map
+ * (NaN = empty cell, the reference's ZZ) into device memory, e.g. one slice of a batch buffer.  Enqueued on the context's
+ * stream; the mesh must stay alive until that work has run (any synchronising call, such as the solve, will do). */
+int wass_mesh_grid_cells_dev(wass_ctx* ctx, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, float* d_cells);
+/* --mf (:359-363): Zi[mask == 0] = 0; cv.medianBlur(Zi, ksize); Zi[mask == 0] = NaN on float32, n_frames maps at once, d_mask
+ * (height x width bytes, shared, may be NULL) the final mask.  The border is replicated as cv::medianBlur does.  ksize 3 or 5
+ * (cv::medianBlur takes no other size for 32-bit float, so the reference cannot either: WASS_ERR_INVALID_ARG); 0 only applies
+ * the mask.  The median of an odd window is one of its elements: the result equals numpy's median over the edge-padded windows
+ * bit for bit (a window that holds a NaN gives NaN).  d_in == d_out is refused.  Asynchronous on the context's stream. */
+int wass_grid_median_dev(wass_ctx* ctx, const float* d_in, float* d_out, int n_frames, int width, int height, int ksize,
+                         const uint8_t* d_mask);
+/* What grid() keeps across the frames (:298-302, 490-494, 528-551, 554-576).
+ * push (frames in sequence order, d_zi: n_frames x height x width metres on the device): per frame nanmean / nanmin / nanmax;
+ * the per-point sum acc += (double)Zi in push order (NaN propagates, as Zmean_grids + Zi does); d_z_mm_out (may be NULL) =
+ * Zi * 1000.0f, the float32 millimetres push_Z stores.  No floating-point atomics and a summation order that depends on the
+ * grid size only: any split of the frames over the calls gives the same bits.
+ * finish: zmin / zmax / zmean = np.amin / np.amax / np.mean of the per-frame values (one all-NaN frame makes them NaN);
+ * mean_perpoint_mm (host, height x width, may be NULL) = acc / n_frames * 1000; with force_zero_mean zmean = 0 and
+ * zmax = -zmin (:543-546).  frame_mean / frame_min / frame_max (host, one per pushed frame, may be NULL).
+ * zero_mean (after finish): z = (float)((double)z - mean_perpoint_mm) on n_frames device maps of millimetres, the arithmetic of
+ * the reference's chunked pass over the cube. */
+typedef struct wass_grid_seq wass_grid_seq;
+typedef struct {
+    double zmin, zmax, zmean;       /* metres, like the reference's attributes          */
+    int    n_frames;                /* frames pushed                                    */
+} wass_grid_seq_stats;
+int wass_grid_seq_create(wass_ctx* ctx, int width, int height, wass_grid_seq** out);
+int wass_grid_seq_push_dev(wass_grid_seq* seq, const float* d_zi, int n_frames, float* d_z_mm_out);
+int wass_grid_seq_finish(wass_grid_seq* seq, int force_zero_mean, wass_grid_seq_stats* stats, double* mean_perpoint_mm,
+                         double* frame_mean, double* frame_min, double* frame_max);
+int wass_grid_seq_zero_mean_dev(wass_grid_seq* seq, float* d_z_mm, int n_frames);
+void wass_grid_seq_destroy(wass_grid_seq* seq);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

@@ -2,9 +2,12 @@
 """Time the DCT surface interpolator: wass_grid_dct_dev at 1024 x 1024, Nf 150, all 501 Rprop steps (TOLERANCE_CHANGE 0), after
 warm-up, against a torch restatement of the reference loop (autograd + torch.optim.Rprop, DCTInterpolator.py) on the same GPU.
 
-    python scripts/time_grid_dct.py [--n 1024] [--nf 150] [--reps 5]
+    python scripts/time_grid_dct.py [--n 1024] [--nf 150] [--reps 5] [--batch 1,2,4,8,16]
 
 Prints one JSON line: ms per solve, effective TFLOP/s (2 (2 H W Nf + Nf^2 (H + W)) FLOP per step) and the torch loop's ms.
+With --batch also wass_grid_dct_batch_dev on that many distinct maps per call, for every size of the list: "batch" maps the
+size to the median ms per call, ms per frame and all repeats.  WASS_GPU_LIB=<another build> times that build's single solve
+with the same script (an older build has no batch entry: leave --batch out).
 """
 import argparse
 import json
@@ -55,6 +58,7 @@ def main():
     ap.add_argument("--nf", type=int, default=150)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--batch", default="", help="comma-separated batch sizes for wass_grid_dct_batch_dev (default: none)")
     a = ap.parse_args()
     n, nf, iters = a.n, a.nf, 500
     zz = surface(n)
@@ -71,6 +75,22 @@ def main():
             t0 = time.perf_counter()
             ctx.grid_dct_dev(d_zz, d_out, opts)                        # returns when the solve has finished
             times.append((time.perf_counter() - t0) * 1e3)
+        batches = [int(b) for b in a.batch.split(",") if b]
+        if batches:
+            d_all = torch.tensor(np.stack([surface(n, seed=i) for i in range(max(batches))]), device="cuda")
+            d_all_out = torch.empty_like(d_all)
+            torch.cuda.synchronize()
+            res["batch"] = {}
+            for nb in batches:
+                infos, status = ctx.grid_dct_batch_dev(d_all[:nb], d_all_out[:nb], opts)          # warm-up: the scratch grows
+                assert all(i["steps"] == iters + 1 for i in infos) and (status == 0).all()
+                tb = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    ctx.grid_dct_batch_dev(d_all[:nb], d_all_out[:nb], opts)
+                    tb.append((time.perf_counter() - t0) * 1e3)
+                res["batch"][str(nb)] = {"ms_per_call": round(float(np.median(tb)), 3), "ms_per_frame": round(float(np.median(tb)) / nb, 3),
+                                         "ms_all": [round(t, 3) for t in tb]}
     flop = 2.0 * (2.0 * n * n * nf + nf * nf * (n + n)) * (iters + 1)
     res["ms_per_solve"] = round(float(np.median(times)), 3)
     res["ms_all"] = [round(t, 3) for t in times]

@@ -72,6 +72,11 @@ class DctInfo(C.Structure):
                 ("fdelta", C.c_double)]
 
 
+class GridSeqStats(C.Structure):
+    """wass_grid_seq_stats"""
+    _fields_ = [("zmin", C.c_double), ("zmax", C.c_double), ("zmean", C.c_double), ("n_frames", C.c_int)]
+
+
 class Geom(C.Structure):
     """wass_geom"""
     _fields_ = [("K_left", C.c_double * 9), ("K_right", C.c_double * 9), ("R", C.c_double * 9), ("T", C.c_double * 3),
@@ -184,6 +189,15 @@ SYMBOLS = {
     "wass_grid_dct_dev": (_i, [_vp, _vp, _i, _i, C.POINTER(DctOpts), _vp, _vp, _vp, _vp, C.POINTER(DctInfo)]),
     "wass_mesh_grid_dct": (_i, [_vp, _vp, C.POINTER(GridSetup), _i, C.POINTER(DctOpts), _vp, _vp, _vp, _vp, _vp, C.POINTER(DctInfo)]),
     "wass_grid_dct_eval": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "wass_grid_dct_batch": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(DctOpts), _vp, _vp, _vp, _vp, C.POINTER(DctInfo), C.POINTER(_i)]),
+    "wass_grid_dct_batch_dev": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(DctOpts), _vp, _vp, _vp, _vp, C.POINTER(DctInfo), C.POINTER(_i)]),
+    "wass_mesh_grid_cells_dev": (_i, [_vp, _vp, C.POINTER(GridSetup), _i, _vp]),
+    "wass_grid_median_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "wass_grid_seq_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "wass_grid_seq_push_dev": (_i, [_vp, _vp, _i, _vp]),
+    "wass_grid_seq_finish": (_i, [_vp, _i, C.POINTER(GridSeqStats), _vp, _vp, _vp, _vp]),
+    "wass_grid_seq_zero_mean_dev": (_i, [_vp, _vp, _i]),
+    "wass_grid_seq_destroy": (None, [_vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

@@ -243,6 +243,12 @@ int grid_cells_dev(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, i
 
 }  // namespace wass
 
+extern "C" int wass_mesh_grid_cells_dev(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, float* d_cells)
+{
+    if (!d_cells) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    return grid_cells_dev(c, m, gs, cell_statistic, d_cells);
+}
+
 extern "C" int wass_mesh_grid_idw_ex(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, int cell_statistic, float* grid_out,
                                      uint8_t* mask_out)
 {

@@ -373,6 +373,64 @@ class Context:
                                                 ptr(d_coeffs), C.byref(info)))
         return dct_info(info)
 
+    def grid_dct_batch(self, zz: np.ndarray, dct_options=None, x0=None, user_mask=None, seed: int = 0):
+        """grid_dct on n cell maps of one shape in one set of launches (wass_grid_dct_batch): zz n x height x width, x0 None or
+        n x nfreqs x nfreqs, user_mask one height x width map for all frames.  Returns (grids n x height x width, coefficients
+        n x nfreqs x nfreqs, list of info dicts, status int32[n]); frame i equals grid_dct(zz[i], ..., x0[i]) bit for bit.  A frame
+        without data has status -6 (WASS_ERR_TOO_FEW_POINTS), an all-NaN grid, NaN coefficients and zeroed info."""
+        zz = np.ascontiguousarray(zz, np.float32)
+        if zz.ndim != 3:
+            raise ValueError("zz: n x height x width expected")
+        n, h, w = zz.shape
+        o = dct_opts(dct_options, seed)
+        nf = max(o.nfreqs, 1)
+        x0c = None if x0 is None else np.ascontiguousarray(x0, np.float32).reshape(n, o.nfreqs, o.nfreqs)
+        um = None if user_mask is None else np.ascontiguousarray(user_mask, np.uint8).reshape(h, w)
+        grid = np.empty((n, h, w), np.float32)
+        coeffs = np.full((n, nf, nf), np.nan, np.float32)
+        info = (_lib.DctInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), np.int32)
+        self._check(self._lib.wass_grid_dct_batch(self._h, zz.ctypes.data, n, w, h, C.byref(o), None if x0c is None else x0c.ctypes.data,
+                                                  None if um is None else um.ctypes.data, grid.ctypes.data, coeffs.ctypes.data, info,
+                                                  status.ctypes.data_as(C.POINTER(C.c_int))))
+        return grid, coeffs, [dct_info(i) for i in info[:n]], status[:n]
+
+    def grid_dct_batch_dev(self, d_zz, d_out, dct_options=None, d_x0=None, d_user_mask=None, d_coeffs=None, seed: int = 0):
+        """grid_dct_batch on device tensors (float32 zz and out, n x height x width contiguous); returns (info dicts, status)."""
+        n, h, w = d_zz.shape
+        o = dct_opts(dct_options, seed)
+        info = (_lib.DctInfo * max(n, 1))()
+        status = np.zeros(max(n, 1), np.int32)
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        self._check(self._lib.wass_grid_dct_batch_dev(self._h, d_zz.data_ptr(), n, w, h, C.byref(o), ptr(d_x0), ptr(d_user_mask),
+                                                      d_out.data_ptr(), ptr(d_coeffs), info, status.ctypes.data_as(C.POINTER(C.c_int))))
+        return [dct_info(i) for i in info[:n]], status[:n]
+
+    def grid_median_dev(self, d_in, d_out, ksize: int, d_mask=None):
+        """The --mf median filter on device tensors (wass_grid_median_dev): float32 n x height x width (or height x width) in and
+        out, uint8 height x width mask or None.  Asynchronous on self.stream."""
+        n = 1 if d_in.dim() == 2 else d_in.shape[0]
+        h, w = d_in.shape[-2:]
+        self._check(self._lib.wass_grid_median_dev(self._h, d_in.data_ptr(), d_out.data_ptr(), n, w, h, int(ksize),
+                                                   None if d_mask is None else d_mask.data_ptr()))
+        return d_out
+
+    def grid_median(self, z: np.ndarray, ksize: int, mask=None) -> np.ndarray:
+        """wassgridsurface --mf on host arrays: Zi[mask == 0] = 0, cv.medianBlur(Zi, ksize) (3 or 5; 0: mask only),
+        Zi[mask == 0] = NaN; z float32 height x width or n x height x width, mask one height x width map or None."""
+        import torch
+        z = np.ascontiguousarray(z, np.float32)
+        if z.ndim not in (2, 3):
+            raise ValueError("z: height x width or n x height x width expected")
+        dev = torch.device("cuda", self.device_id)
+        d_in = torch.from_numpy(z).to(dev)
+        d_mask = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask, np.uint8).reshape(z.shape[-2:])).to(dev)
+        d_out = torch.empty_like(d_in)
+        torch.cuda.synchronize(dev)
+        self.grid_median_dev(d_in, d_out, ksize, d_mask)
+        self.synchronize()
+        return d_out.cpu().numpy()
+
     def grid_dct_eval(self, zz: np.ndarray, x: np.ndarray, alpha: float = 8e-7):
         """One evaluation of the DCT interpolator's loss at x (nfreqs x nfreqs): (float32 gradient, data loss, |x|_1)."""
         zz = np.ascontiguousarray(zz, np.float32)
@@ -486,6 +544,61 @@ def dct_info(info: _lib.DctInfo) -> dict:
             "fdelta": info.fdelta}
 
 
+def grid_setup(R, T, baseline: float, xmin: float, xmax: float, ymin: float, ymax: float, width: int, height: int) -> _lib.GridSetup:
+    """wass_grid_setup from the reference's gridsetup values (Rpl, Tpl, CAM_BASELINE, the extent and the grid size)."""
+    gs = _lib.GridSetup()
+    gs.R[:] = np.asarray(R, float).ravel().tolist(); gs.T[:] = np.asarray(T, float).ravel().tolist()
+    gs.baseline, gs.xmin, gs.xmax, gs.ymin, gs.ymax, gs.width, gs.height = (float(baseline), float(xmin), float(xmax), float(ymin),
+                                                                           float(ymax), int(width), int(height))
+    return gs
+
+
+class GridSequence:
+    """What the reference's grid() keeps across the frames of a sequence (wass_grid_seq): per-frame nanmean / nanmin / nanmax, the
+    per-point fp64 sum, the millimetre slices, and at the end zmin / zmax / zmean, the per-point mean and the zero-mean pass."""
+
+    def __init__(self, ctx: Context, width: int, height: int):
+        self.ctx, self.width, self.height = ctx, int(width), int(height)
+        h = C.c_void_p()
+        ctx._check(ctx._lib.wass_grid_seq_create(ctx._h, self.width, self.height, C.byref(h)))
+        self._h = h
+        self.n_frames = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.wass_grid_seq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push_dev(self, d_zi, d_z_mm=None):
+        """d_zi: float32 device tensor n x height x width (metres), frames in sequence order; d_z_mm (same shape, optional)
+        receives Zi * 1000 as float32.  Returns when the frames' statistics have been read."""
+        n = 1 if d_zi.dim() == 2 else d_zi.shape[0]
+        self.ctx._check(self.ctx._lib.wass_grid_seq_push_dev(self._h, d_zi.data_ptr(), n, None if d_z_mm is None else d_z_mm.data_ptr()))
+        self.n_frames += n
+
+    def finish(self, force_zero_mean: bool = False) -> dict:
+        """zmin, zmax, zmean (metres), mean_perpoint_mm (float64 height x width) and the per-frame means / minima / maxima."""
+        st = _lib.GridSeqStats()
+        mean = np.empty((self.height, self.width), np.float64)
+        fm, fmin, fmax = (np.empty(max(self.n_frames, 1), np.float64) for _ in range(3))
+        self.ctx._check(self.ctx._lib.wass_grid_seq_finish(self._h, int(bool(force_zero_mean)), C.byref(st), mean.ctypes.data, fm.ctypes.data,
+                                                           fmin.ctypes.data, fmax.ctypes.data))
+        n = self.n_frames
+        return {"zmin": st.zmin, "zmax": st.zmax, "zmean": st.zmean, "n_frames": st.n_frames, "mean_perpoint_mm": mean,
+                "frame_mean": fm[:n], "frame_min": fmin[:n], "frame_max": fmax[:n]}
+
+    def zero_mean_dev(self, d_z_mm):
+        """z = float32(float64(z) - mean_perpoint_mm) in place on n x height x width millimetre maps (after finish)."""
+        n = 1 if d_z_mm.dim() == 2 else d_z_mm.shape[0]
+        self.ctx._check(self.ctx._lib.wass_grid_seq_zero_mean_dev(self._h, d_z_mm.data_ptr(), n))
+
+
 class Mesh:
     """Device-resident organised point cloud (wass_mesh) -- the PovMesh of the reference."""
 
@@ -545,6 +658,14 @@ class Mesh:
                                                          None if x0c is None else x0c.ctypes.data, None if um is None else um.ctypes.data,
                                                          grid.ctypes.data, cells.ctypes.data, coeffs.ctypes.data, C.byref(info)))
         return grid, cells, coeffs, dct_info(info)
+
+    def grid_cells_dev(self, gs: "_lib.GridSetup", d_cells, cell: str = "median"):
+        """The alignment and binning alone (wass_mesh_grid_cells_dev): the float32 height x width cell map (NaN = empty) into the
+        device tensor d_cells, e.g. one slice of a batch buffer.  Asynchronous: keep this mesh alive until the stream has run."""
+        if tuple(d_cells.shape) != (gs.height, gs.width) or not d_cells.is_contiguous():
+            raise ValueError("d_cells: a contiguous float32 height x width tensor expected")
+        self.ctx._check(self.ctx._lib.wass_mesh_grid_cells_dev(self.ctx._h, self._h, C.byref(gs), {"mean": 0, "median": 1}[cell],
+                                                               d_cells.data_ptr()))
 
     def zgap_percentile(self, pct: float):
         out = C.c_double(); n = C.c_uint64()
