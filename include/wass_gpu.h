@@ -476,7 +476,10 @@ void wass_free(void* p);
  * points on the width x height grid over [xmin,xmax] x [ymin,ymax] (:322-326) and fill the gaps with
  * IDWInterpolator(KSIZE=5, exp=2.4, reps=1) (IDWInterpolator.py:23-58).  grid_out: height x width float32, NaN outside
  * the closed point mask; mask_out (may be NULL) that mask.  A cell takes the mean of its points (deterministic) where the
- * reference takes the median of ten random sub-samples (randomised): see grid.hip. */
+ * reference takes the median of ten random sub-samples (randomised): see grid.hip.
+ * A point's column is floor((x - xmin) / (xmax - xmin) * (width - 1) + 0.5) in fp64, with the reference's order of roundings
+ * (no precomputed scale), its row likewise; a point whose column or row falls outside the grid, or whose aligned x or y is
+ * NaN or infinite, is dropped. */
 typedef struct {
     double R[9], T[3];              /* gridsetup["Rpl"], ["Tpl"]                        */
     double baseline;                /* gridsetup["CAM_BASELINE"] (metres)               */

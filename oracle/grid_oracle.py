@@ -77,7 +77,14 @@ def grid_idw(points, plane, baseline, xmin, xmax, ymin, ymax, width, height, cel
     good = (px >= 0) & (px < width) & (py >= 0) & (py < height)
     px, py, pz = px[good].astype(np.int64), py[good].astype(np.int64), m[2, good]
     ZZ = cell_values(px, py, pz, width, height, cell, seed, subsample_percent)
-    # IDWInterpolator(KSIZE=5, exp=2.4, reps=1)
+    return idw_from_cells(ZZ)
+
+
+def idw_from_cells(ZZ):
+    """IDWInterpolator(KSIZE=5, exp=2.4, reps=1) on a (height, width) cell map, NaN = empty cell.  Returns (Zi float64 with NaN
+    outside the mask, mask uint8)."""
+    ZZ = np.asarray(ZZ, np.float64)
+    height, width = ZZ.shape
     KS = 5
     Kd = np.array([(k - KS // 2) for k in range(KS)], dtype=np.float64)
     Kx = np.tile(Kd, (KS, 1)); Ky = Kx.T

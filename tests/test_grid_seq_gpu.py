@@ -228,6 +228,24 @@ def test_accumulator_equals_oracle_and_does_not_depend_on_the_split(gpu_ctx, for
     _check_against_oracle(*a, frames, force_zero_mean)
 
 
+@pytest.mark.parametrize("w,h", [(257, 300), (1024, 1024)])
+def test_accumulator_equals_oracle_above_65536_cells(gpu_ctx, w, h):
+    """k_seq_stats runs at most 256 workgroups of 256 threads: only a map of more than 65 536 cells sends its grid-stride loop
+    round a second time (77 100 cells: a second turn for some threads only; 1024 x 1024: sixteen turns for all)."""
+    rng = np.random.default_rng(w)
+    frames = np.stack([0.3 * band_limited(h, w, seed=600 + i, keep=1.0) + np.float32(rng.normal(0, 0.02)) for i in range(3)])
+    mask = np.ones((h, w), bool); mask[:, 17] = False; mask[h - 3] = False
+    frames[:, ~mask] = np.nan
+    frames[:, mask] = np.nan_to_num(frames[:, mask], nan=0.125)
+    for fzm in (False, True):
+        a = _push_all(gpu_ctx, frames, (2, 1), fzm)
+        b = _push_all(gpu_ctx, frames, (1, 1, 1), fzm)
+        for k in ("zmin", "zmax", "zmean", "mean_perpoint_mm", "frame_mean", "frame_min", "frame_max"):
+            assert np.array_equal(np.asarray(a[0][k]), np.asarray(b[0][k]), equal_nan=True), k
+        assert np.array_equal(a[1], b[1], equal_nan=True) and np.array_equal(a[2], b[2], equal_nan=True)
+        _check_against_oracle(*a, frames, fzm)
+
+
 def test_accumulator_nan_cases(gpu_ctx):
     a = np.array([[1.0, 2.0, np.nan], [3.0, -4.0, np.nan]], np.float32)
     b = np.array([[0.5, 0.5, np.nan], [0.5, 0.5, np.nan]], np.float32)

@@ -20,9 +20,26 @@
 namespace wass {
 
 struct GridDev {
-    double R[9], T[3], baseline, xmin, ymin, sx, sy;      // sx = (W - 1) / (xmax - xmin)
+    double R[9], T[3], baseline, xmin, ymin, xext, yext, wm1, hm1;      // xext = xmax - xmin, wm1 = W - 1
     int gw, gh;
 };
+
+constexpr unsigned int GRID_OUTSIDE = 0xFFFFFFFFu;
+
+// Alignment and binning of one point, the one place where both cell statistics get their cell from: returns the cell
+// (GRID_OUTSIDE: not in the grid, which a NaN or infinite coordinate is too) and the aligned height in az.  The bin follows the
+// reference's sequence of roundings (:324-325): subtract, divide by the extent, multiply by W - 1, add 0.5, floor.  A
+// precomputed scale (W - 1) / (xmax - xmin) rounds differently and moves a point within an ulp or two of a cell boundary into
+// the neighbouring cell (tests/test_grid_bin.py counts them).
+__device__ __forceinline__ unsigned int grid_align_bin(const GridDev& g, double x, double y, double z, double& az)
+{
+    const double ax = (g.R[0] * x + g.R[1] * y + g.R[2] * z + g.T[0]) * g.baseline;
+    const double ay = (g.R[3] * x + g.R[4] * y + g.R[5] * z + g.T[1]) * g.baseline;
+    az = -(g.R[6] * x + g.R[7] * y + g.R[8] * z + g.T[2]) * g.baseline;
+    const double fx = floor((ax - g.xmin) / g.xext * g.wm1 + 0.5), fy = floor((ay - g.ymin) / g.yext * g.hm1 + 0.5);
+    if (!(fx >= 0 && fx < g.gw && fy >= 0 && fy < g.gh)) return GRID_OUTSIDE;
+    return (unsigned int)((size_t)fy * g.gw + (size_t)fx);
+}
 
 __global__ void __launch_bounds__(256) k_grid_scatter(const uint8_t* __restrict__ valid, const double* __restrict__ X,
                                                       const double* __restrict__ Y, const double* __restrict__ Z, size_t n, GridDev g,
@@ -30,37 +47,26 @@ __global__ void __launch_bounds__(256) k_grid_scatter(const uint8_t* __restrict_
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || !valid[i]) return;
-    const double x = X[i], y = Y[i], z = Z[i];
-    const double ax = (g.R[0] * x + g.R[1] * y + g.R[2] * z + g.T[0]) * g.baseline;
-    const double ay = (g.R[3] * x + g.R[4] * y + g.R[5] * z + g.T[1]) * g.baseline;
-    const double az = -(g.R[6] * x + g.R[7] * y + g.R[8] * z + g.T[2]) * g.baseline;
-    const double fx = floor((ax - g.xmin) * g.sx + 0.5), fy = floor((ay - g.ymin) * g.sy + 0.5);
-    if (!(fx >= 0 && fx < g.gw && fy >= 0 && fy < g.gh)) return;
-    const size_t cidx = (size_t)fy * g.gw + (size_t)fx;
-    atomicAdd((unsigned long long*)&sum[cidx], (unsigned long long)(long long)llrint(az * 16777216.0));
-    atomicAdd(&cnt[cidx], 1u);
+    double az;
+    const unsigned int cell = grid_align_bin(g, X[i], Y[i], Z[i], az);
+    if (cell == GRID_OUTSIDE) return;
+    atomicAdd((unsigned long long*)&sum[cell], (unsigned long long)(long long)llrint(az * 16777216.0));
+    atomicAdd(&cnt[cell], 1u);
 }
 
 // ---- median mode: points bucketed by cell
-// pass 1: the cell of every point (0xFFFFFFFF: not in the grid) and its height, counts per cell
+// pass 1: the cell of every point (GRID_OUTSIDE: not in the grid) and its height, counts per cell
 __global__ void __launch_bounds__(256) k_grid_bucket_count(const uint8_t* __restrict__ valid, const double* __restrict__ X,
                                                            const double* __restrict__ Y, const double* __restrict__ Z, size_t n, GridDev g,
                                                            unsigned int* __restrict__ pcell, double* __restrict__ pz, unsigned int* __restrict__ cnt)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    unsigned int cell = 0xFFFFFFFFu;
+    unsigned int cell = GRID_OUTSIDE;
     double az = 0.0;
     if (valid[i]) {
-        const double x = X[i], y = Y[i], z = Z[i];
-        const double ax = (g.R[0] * x + g.R[1] * y + g.R[2] * z + g.T[0]) * g.baseline;
-        const double ay = (g.R[3] * x + g.R[4] * y + g.R[5] * z + g.T[1]) * g.baseline;
-        az = -(g.R[6] * x + g.R[7] * y + g.R[8] * z + g.T[2]) * g.baseline;
-        const double fx = floor((ax - g.xmin) * g.sx + 0.5), fy = floor((ay - g.ymin) * g.sy + 0.5);
-        if (fx >= 0 && fx < g.gw && fy >= 0 && fy < g.gh) {
-            cell = (unsigned int)((size_t)fy * g.gw + (size_t)fx);
-            atomicAdd(&cnt[cell], 1u);
-        }
+        cell = grid_align_bin(g, X[i], Y[i], Z[i], az);
+        if (cell != GRID_OUTSIDE) atomicAdd(&cnt[cell], 1u);
     }
     pcell[i] = cell;
     pz[i] = az;
@@ -91,7 +97,7 @@ __global__ void __launch_bounds__(256) k_grid_bucket_fill(const unsigned int* __
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const unsigned int c = pcell[i];
-    if (c == 0xFFFFFFFFu) return;
+    if (c == GRID_OUTSIDE) return;
     vals[off[c] + atomicAdd(&fill[c], 1u)] = pz[i];
 }
 // every cell sorts its own segment in place (shell sort: cells hold a handful of points, a few hundred next to the cameras)
@@ -208,7 +214,7 @@ static int grid_bin(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, 
     uint8_t* mask = dil + ng;
     memcpy(g.R, gs->R, sizeof g.R); memcpy(g.T, gs->T, sizeof g.T);
     g.baseline = gs->baseline; g.xmin = gs->xmin; g.ymin = gs->ymin;
-    g.sx = (gs->width - 1) / (gs->xmax - gs->xmin); g.sy = (gs->height - 1) / (gs->ymax - gs->ymin);
+    g.xext = gs->xmax - gs->xmin; g.yext = gs->ymax - gs->ymin; g.wm1 = gs->width - 1; g.hm1 = gs->height - 1;
     g.gw = gs->width; g.gh = gs->height;
     hipStream_t s = c->ts();
     const dim3 blk(256), gp((unsigned)((n + 255) / 256)), gc((unsigned)((ng + 255) / 256));
