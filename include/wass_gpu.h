@@ -593,6 +593,41 @@ int wass_grid_seq_finish(wass_grid_seq* seq, int force_zero_mean, wass_grid_seq_
 int wass_grid_seq_zero_mean_dev(wass_grid_seq* seq, float* d_z_mm, int n_frames);
 void wass_grid_seq_destroy(wass_grid_seq* seq);
 
+/* ---- wave spectra of the gridded cube: postproc/wasspost/spectra.py as array functions ----------
+ * compute_3D_spectrum (:53-171): Welch's method over 3-D segments of nt x ny x nx cells.  The host computes axes, windows
+ * and the scale (wass_amd/postproc.py); one segment per push:
+ *   fill     a NaN becomes its cell's mean over the segment's frames that are not NaN (np.nanmean(axis=0) of the float32
+ *            segment times datascale); a cell that is NaN throughout is recorded in a device flag and enters as 0
+ *   centre   minus the mean of the filled segment; times win_y[y] * win_x[x] * win_t[t] (fp64, then f32)
+ *   DFT      along x (real to complex, kx = 0 .. nx / 2), y and t as products with f32 twiddle matrices on the f32 MFMA, every
+ *            sum in a fixed order: the same segment gives the same bits on every run
+ *   power    S[fftshift on the three axes] += |X|^2 in fp64, in push order; the half not computed is read at the mirrored
+ *            (-f, -ky, -kx)
+ * create: win_* are nt / ny / nx doubles (NULL: the symmetric Hann window of scipy.signal.windows.hann).  The handle owns
+ * about six f32 copies of the window in device memory (wass_spec3d_scratch_bytes says how much: 1.1 GB at 100 x 684 x 684);
+ * WASS_ERR_NO_MEMORY when that is more than 16 GiB or the allocation fails, WASS_ERR_INVALID_ARG for an axis outside
+ * 1 .. 8192.
+ * push: seg points at the segment's first cell, cell (t, y, x) at seg[t * stride_t + y * stride_y + x] (strides in
+ * elements); host memory for wass_spec3d_push, device memory for wass_spec3d_push_dev (read in place).  Enqueued on the
+ * context's stream; the host form returns when the segment has been handed to the runtime.
+ * finish: S (host, nt x ny x nx doubles) = scale * the sum; *n_segments = segments pushed; *had_all_nan_cell = 1 if a cell
+ * of some segment was NaN throughout (the reference's result is NaN everywhere then).  The handle starts over. */
+typedef struct wass_spec3d wass_spec3d;
+int wass_spec3d_scratch_bytes(int nt, int ny, int nx, size_t* bytes);
+int wass_spec3d_create(wass_ctx* ctx, int nt, int ny, int nx, const double* win_t, const double* win_y, const double* win_x,
+                       wass_spec3d** out);
+int wass_spec3d_push(wass_spec3d* h, const float* seg, size_t stride_t, size_t stride_y, double datascale);
+int wass_spec3d_push_dev(wass_spec3d* h, const float* d_seg, size_t stride_t, size_t stride_y, double datascale);
+int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* n_segments, int* had_all_nan_cell);
+void wass_spec3d_destroy(wass_spec3d* h);
+/* compute_spectrum (:9-49): S[nperseg / 2 + 1] (host) = the sum over n_series series (host, n_series x n_samples float32) of
+ * scipy.signal.csd(x, x, fs, nperseg=nperseg) with x = (float32)(series * scale) minus its mean: segments of nperseg with
+ * overlap nperseg / 2, each minus its own mean, periodic Hann window, one-sided density scaling, mean over the segments.
+ * nperseg > n_samples shrinks to n_samples (and the overlap with it), as csd does.  The DFT is the product of the 3-D
+ * spectrum's x stage; sums in fp64 and in a fixed order. */
+int wass_spec1d_welch(wass_ctx* ctx, const float* series, int n_series, int n_samples, int nperseg, double fs, double scale,
+                      double* S);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

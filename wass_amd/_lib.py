@@ -198,6 +198,13 @@ SYMBOLS = {
     "wass_grid_seq_finish": (_i, [_vp, _i, C.POINTER(GridSeqStats), _vp, _vp, _vp, _vp]),
     "wass_grid_seq_zero_mean_dev": (_i, [_vp, _vp, _i]),
     "wass_grid_seq_destroy": (None, [_vp]),
+    "wass_spec3d_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "wass_spec3d_create": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "wass_spec3d_push": (_i, [_vp, _vp, _sz, _sz, C.c_double]),
+    "wass_spec3d_push_dev": (_i, [_vp, _vp, _sz, _sz, C.c_double]),
+    "wass_spec3d_finish": (_i, [_vp, C.c_double, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "wass_spec3d_destroy": (None, [_vp]),
+    "wass_spec1d_welch": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, _vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

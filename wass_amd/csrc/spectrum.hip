@@ -1,0 +1,603 @@
+// spectrum.hip -- wave spectra of the gridded cube: the two array functions of postproc/wasspost/spectra.py,
+// compute_3D_spectrum (:53-171, Welch's method over 3-D segments) and compute_spectrum (:9-49, scipy.signal.csd of the centre
+// series and its neighbours).  The host side (wass_amd/postproc.py) computes axes, windows and the scale in fp64; segments come
+// here.
+//
+// The window lengths are whatever two thirds of the grid gives (683 is prime, 684 is not, Nt is any even number), so the DFT is
+// a product with a twiddle matrix on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fma chain), the idiom of grid_dct.hip, for
+// every length alike:
+//   k_seg_cell / k_seg_mean / k_seg_window   NaN fill by the cell's mean over the segment, global mean, separable Hann window
+//   k_dft_stage  x:  real [t][y][x]      -> complex [t][y][kx],  kx = 0 .. nx/2 only (the input is real)
+//   k_dft_stage  y:  complex [t][y][kx]  -> complex [t][ky][kx]  (one product per t)
+//   k_dft_stage  t:  complex [t][ky][kx] -> complex [f][ky][kx]
+//   k_spec_power     S[fftshift] += |X|^2 in fp64, the other half of kx read at the mirrored (-f, -ky, -kx)
+// Every stage is  Out[m][n] = sum_k (cos - i sin)(2 pi m k / len) In[k][n]  with the twiddle as the A operand: only the strides of
+// In and Out differ.  A workgroup of four waves makes a 64 x 64 tile of Out: the twiddle and input tiles of 16 k go through LDS
+// (the next pair is in flight from global memory while the current one is multiplied), every wave keeps a 32 x 32 patch, i.e.
+// eight 16 x 16 accumulators (real and imaginary).  No reduction uses an atomic: the same input gives the same bits.
+//
+// Scratch of one handle, in units of one real f32 copy of the window (nt * ny * nx * 4 bytes): 1 for the prepared segment, 1 for
+// the host-pointer staging, about 2 for the two complex half-spectra the stages alternate between, 2 for the fp64 Welch sum:
+// about 6, i.e. 1.1 GB at 100 x 684 x 684 and 3.4 GB at 300 x 684 x 684.  SPEC_SCRATCH_CAP bounds it.
+#include "common.h"
+
+#include <math.h>
+#include <new>
+#include <vector>
+
+namespace wass {
+
+typedef float sp_f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr size_t SPEC_SCRATCH_CAP = (size_t)16 << 30;   // bytes one handle / one wass_spec1d_welch call may allocate
+constexpr int SPEC_MAX_AXIS = 8192;                     // longest transform
+constexpr int SP_TM = 64, SP_TN = 64, SP_TK = 16;       // tile of k_dft_stage
+constexpr int SP_LD = 80;                               // LDS row pitch: the four k rows of one MFMA operand fall on banks 0 / 16 / 32 / 48
+
+static inline int sp_round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// C[k][m] = cos(2 pi k m / n), S[k][m] = sin(2 pi k m / n) for k < n, m < nm; 0 in the padding (Kp rows of Mp).  fp64 with the angle
+// reduced exactly, (k m) mod n in integers, then cast to f32.
+__global__ void __launch_bounds__(256) k_dft_twiddle(float* __restrict__ Cm, float* __restrict__ Sm, int n, int nm, int Mp)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (m >= Mp) return;
+    double c = 0.0, s = 0.0;
+    if (k < n && m < nm) {
+        const long long r = ((long long)k * m) % n;
+        const double a = 6.283185307179586476925286766559 * (double)r / (double)n;
+        c = cos(a);
+        s = sin(a);
+    }
+    Cm[(size_t)k * Mp + m] = (float)c;
+    Sm[(size_t)k * Mp + m] = (float)s;
+}
+
+struct DftArgs {
+    const float* Tc; const float* Ts; int Mp;       // twiddle pair, [Kp][Mp]
+    const float* Bre; const float* Bim;             // input planes (Bim unused for a real input)
+    float* Ore; float* Oim;                         // output planes
+    int M, N, K;                                    // output rows, columns, contraction length (unpadded)
+    long long b_sk, b_sn, b_sb;                     // element strides of the input: k, n, batch (blockIdx.z)
+    long long o_sm, o_sn, o_sb;                     // ... of the output
+};
+
+// KCONTIG: the input's k is its contiguous axis (the x stage), else n is.  Loads outside K x N read as 0, stores outside M x N are
+// dropped; the twiddle's padding is 0, so nothing outside the problem reaches an accumulator.
+template <bool CPLX, bool KCONTIG>
+__global__ void __launch_bounds__(256) k_dft_stage(const DftArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float As_c[SP_TK][SP_LD];
+    __shared__ __attribute__((aligned(16))) float As_s[SP_TK][SP_LD];
+    __shared__ float Bs_r[SP_TK][SP_LD];
+    __shared__ float Bs_i[CPLX ? SP_TK : 1][SP_LD];
+
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, lo = l & 15, hi = l >> 4;
+    const int m0 = blockIdx.y * SP_TM, n0 = blockIdx.x * SP_TN;
+    const float* __restrict__ Bre = a.Bre + (long long)blockIdx.z * a.b_sb;
+    const float* __restrict__ Bim = CPLX ? a.Bim + (long long)blockIdx.z * a.b_sb : nullptr;
+
+    // this thread's part of a tile pair: one float4 of each twiddle, four scalars of each input plane
+    const int ak = tid >> 4, am = (tid & 15) * 4;
+    const int bk = KCONTIG ? (tid & 15) : (tid >> 6), bn = KCONTIG ? (tid >> 4) : (tid & 63);
+    constexpr int BK_STEP = KCONTIG ? 0 : 4, BN_STEP = KCONTIG ? 16 : 0;
+    sp_f32x4 pc, ps;
+    float pr[4], pi[4];
+    auto fetch = [&](int k0) {
+        pc = *(const sp_f32x4*)&a.Tc[(size_t)(k0 + ak) * a.Mp + m0 + am];
+        ps = *(const sp_f32x4*)&a.Ts[(size_t)(k0 + ak) * a.Mp + m0 + am];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = k0 + bk + i * BK_STEP, n = n0 + bn + i * BN_STEP;
+            const bool in = k < a.K && n < a.N;
+            const long long q = (long long)k * a.b_sk + (long long)n * a.b_sn;
+            pr[i] = in ? Bre[q] : 0.f;
+            if (CPLX) pi[i] = in ? Bim[q] : 0.f;
+        }
+    };
+
+    sp_f32x4 acc_re[2][2], acc_im[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            acc_re[i][j] = sp_f32x4{0.f, 0.f, 0.f, 0.f};
+            acc_im[i][j] = sp_f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    const int wm = (w & 1) * 32, wn = (w >> 1) * 32;
+    const int nk = (a.K + SP_TK - 1) / SP_TK;
+    fetch(0);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();                               // the previous tile pair has been read by every wave
+        *(sp_f32x4*)&As_c[ak][am] = pc;
+        *(sp_f32x4*)&As_s[ak][am] = ps;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            Bs_r[bk + i * BK_STEP][bn + i * BN_STEP] = pr[i];
+            if (CPLX) Bs_i[bk + i * BK_STEP][bn + i * BN_STEP] = pi[i];
+        }
+        __syncthreads();
+        if (kt + 1 < nk) fetch((kt + 1) * SP_TK);      // in flight under the MFMAs below
+#pragma unroll
+        for (int s = 0; s < SP_TK / 4; ++s) {
+            const int kk = 4 * s + hi;
+            float ac[2], as[2], an[2], br[2], bi[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                ac[i] = As_c[kk][wm + 16 * i + lo];
+                as[i] = As_s[kk][wm + 16 * i + lo];
+                an[i] = -as[i];
+                br[i] = Bs_r[kk][wn + 16 * i + lo];
+                bi[i] = CPLX ? Bs_i[kk][wn + 16 * i + lo] : 0.f;
+            }
+            // (c - i s)(br + i bi) = (c br + s bi) + i (c bi - s br)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc_re[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[i], br[j], acc_re[i][j], 0, 0, 0);
+                    acc_im[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(an[i], br[j], acc_im[i][j], 0, 0, 0);
+                    if (CPLX) {
+                        acc_re[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(as[i], bi[j], acc_re[i][j], 0, 0, 0);
+                        acc_im[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[i], bi[j], acc_im[i][j], 0, 0, 0);
+                    }
+                }
+        }
+    }
+    // acc[i][j][r] = Out[m0 + wm + 16 i + 4 hi + r][n0 + wn + 16 j + lo]
+    float* __restrict__ Ore = a.Ore + (long long)blockIdx.z * a.o_sb;
+    float* __restrict__ Oim = a.Oim + (long long)blockIdx.z * a.o_sb;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + 16 * i + 4 * hi + r, n = n0 + wn + 16 * j + lo;
+                if (m < a.M && n < a.N) {
+                    const long long q = (long long)m * a.o_sm + (long long)n * a.o_sn;
+                    Ore[q] = acc_re[i][j][r];
+                    Oim[q] = acc_im[i][j][r];
+                }
+            }
+}
+
+static __device__ __forceinline__ double block_sum_256(double v, double* sh)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// One thread per cell, the frames in order: the cell's mean over its frames that are not NaN (np.nanmean(axis=0) of the float32
+// segment times datascale: a float32 sum), NaN and *flag = 1 for a cell that is NaN throughout.  part[block] = the fp64 sum of
+// the block's cells after the fill (the cells of all-NaN columns count as 0).
+__global__ void __launch_bounds__(256) k_seg_cell(const float* __restrict__ src, long long st, long long sy, int nt, int ny, int nx, float ds,
+                                                  float* __restrict__ cellmean, double* __restrict__ part, int* __restrict__ flag)
+{
+    __shared__ double sh[256];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    double tot = 0.0;
+    if (i < ny * nx) {
+        const float* p = src + (long long)(i / nx) * sy + (i % nx);
+        float s = 0.f;
+        double sd = 0.0;
+        int cnt = 0;
+        for (int t = 0; t < nt; ++t) {
+            const float v = p[(long long)t * st] * ds;
+            if (!isnan(v)) { s += v; sd += (double)v; ++cnt; }
+        }
+        const float m = cnt ? s / (float)cnt : __builtin_nanf("");
+        cellmean[i] = m;
+        if (!cnt) *flag = 1;
+        else tot = sd + (double)(nt - cnt) * (double)m;
+    }
+    tot = block_sum_256(tot, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// mean[0] = (the partials, thread-strided then a tree) / count
+__global__ void __launch_bounds__(256) k_seg_mean(const double* __restrict__ part, int npart, double count, double* __restrict__ mean)
+{
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < npart; i += 256) s += part[i];
+    s = block_sum_256(s, sh);
+    if (threadIdx.x == 0) mean[0] = s / count;
+}
+
+// out[t][y][x] = (fill(src * datascale) - mean) * ((wy[y] wx[x]) wt[t]): float32 up to the subtraction like the reference, the window
+// product in fp64, then f32 for the MFMA.  A cell that is NaN throughout gives 0 (the flag has recorded it): no NaN reaches the MFMA.
+__global__ void __launch_bounds__(256) k_seg_window(const float* __restrict__ src, long long st, long long sy, int nt, int ny, int nx, float ds,
+                                                    const float* __restrict__ cellmean, const double* __restrict__ mean,
+                                                    const double* __restrict__ wt, const double* __restrict__ wy, const double* __restrict__ wx,
+                                                    float* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, cells = (size_t)ny * nx;
+    if (i >= (size_t)nt * cells) return;
+    const int t = (int)(i / cells), c = (int)(i % cells), y = c / nx, x = c % nx;
+    float v = src[(long long)t * st + (long long)y * sy + x] * ds;
+    if (isnan(v)) v = cellmean[c];
+    float r = 0.f;
+    if (!isnan(v)) r = (float)((double)(v - (float)mean[0]) * ((wy[y] * wx[x]) * wt[t]));
+    out[i] = r;
+}
+
+// S[it][iy][ix] (np.fft.fftshift on the three axes) += |X(f, ky, kx)|^2 in fp64.  Only kx <= nx / 2 was computed: the rest is read
+// at (-f, -ky, -kx), where the spectrum of a real input has the same modulus -- nx - kx <= nx / 2 for even and odd nx alike.
+__global__ void __launch_bounds__(256) k_spec_power(const float* __restrict__ Xre, const float* __restrict__ Xim, int nt, int ny, int nx, int nxh,
+                                                    double* __restrict__ S)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, cells = (size_t)ny * nx;
+    if (i >= (size_t)nt * cells) return;
+    const int it = (int)(i / cells), c = (int)(i % cells), iy = c / nx, ix = c % nx;
+    int f = (it + nt - nt / 2) % nt, ky = (iy + ny - ny / 2) % ny, kx = (ix + nx - nx / 2) % nx;
+    if (kx > nx / 2) {
+        kx = nx - kx;
+        ky = (ny - ky) % ny;
+        f = (nt - f) % nt;
+    }
+    const size_t q = ((size_t)f * ny + ky) * nxh + kx;
+    const double re = (double)Xre[q], im = (double)Xim[q];
+    S[i] += re * re + im * im;
+}
+
+__global__ void __launch_bounds__(256) k_spec_scale(double* __restrict__ S, size_t n, double scale)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) S[i] *= scale;
+}
+
+// ---- the batched 1-D Welch estimate -----------------------------------------------------------------------------------------
+// smean[k] = mean over the series of (float)(x * scale), fp64, thread-strided then a tree
+__global__ void __launch_bounds__(256) k_w1_mean(const float* __restrict__ x, int T, float scale, double* __restrict__ smean)
+{
+    __shared__ double sh[256];
+    x += (size_t)blockIdx.x * T;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < T; i += 256) s += (double)(x[i] * scale);
+    s = block_sum_256(s, sh);
+    if (threadIdx.x == 0) smean[blockIdx.x] = s / (double)T;
+}
+
+// Segment blockIdx.x of series blockIdx.y: d = x * scale - smean, minus the segment's own mean (detrend='constant'), times the
+// window; written as column (series * nseg + segment) of B[nps][ncol], the layout k_dft_stage contracts.
+__global__ void __launch_bounds__(256) k_w1_prep(const float* __restrict__ x, int T, float scale, const double* __restrict__ smean, int nps, int step,
+                                                 int nseg, const double* __restrict__ win, float* __restrict__ B)
+{
+    __shared__ double sh[256];
+    const int seg = blockIdx.x, ser = blockIdx.y;
+    const size_t ncol = (size_t)gridDim.y * nseg, col = (size_t)ser * nseg + seg;
+    const float* p = x + (size_t)ser * T + (size_t)seg * step;
+    const double m = smean[ser];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nps; i += 256) s += (double)(p[i] * scale) - m;
+    const double sm = block_sum_256(s, sh) / (double)nps;
+    for (int i = threadIdx.x; i < nps; i += 256) B[(size_t)i * ncol + col] = (float)((((double)(p[i] * scale) - m) - sm) * win[i]);
+}
+
+// out[m] = factor[m] * sum over the columns (series-major, segments in order) of |X[m][col]|^2, fp64
+__global__ void __launch_bounds__(256) k_w1_power(const float* __restrict__ Xre, const float* __restrict__ Xim, size_t ncol, double dens, int nps,
+                                                  double* __restrict__ out)
+{
+    __shared__ double sh[256];
+    const int m = blockIdx.x;
+    double s = 0.0;
+    for (size_t i = threadIdx.x; i < ncol; i += 256) {
+        const double re = (double)Xre[(size_t)m * ncol + i], im = (double)Xim[(size_t)m * ncol + i];
+        s += re * re + im * im;
+    }
+    s = block_sum_256(s, sh);
+    // one-sided: every bin but DC and (even nps) Nyquist stands for two
+    const bool twice = m != 0 && !(nps % 2 == 0 && m == nps / 2);
+    if (threadIdx.x == 0) out[m] = s * dens * (twice ? 2.0 : 1.0);
+}
+
+static int launch_dft(wass_ctx* c, hipStream_t s, const DftArgs& a, bool cplx, bool kcontig, int batch)
+{
+    const dim3 grid((a.N + SP_TN - 1) / SP_TN, (a.M + SP_TM - 1) / SP_TM, batch);
+    if (grid.y > 65535 || grid.z > 65535) return set_err(c, WASS_ERR_UNSUPPORTED, "transform too large");
+    if (cplx && kcontig) hipLaunchKernelGGL((k_dft_stage<true, true>), grid, dim3(256), 0, s, a);
+    else if (cplx) hipLaunchKernelGGL((k_dft_stage<true, false>), grid, dim3(256), 0, s, a);
+    else if (kcontig) hipLaunchKernelGGL((k_dft_stage<false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_dft_stage<false, false>), grid, dim3(256), 0, s, a);
+    WASS_HIP(c, hipGetLastError());
+    return WASS_OK;
+}
+
+struct Twiddle {
+    float* c = nullptr;
+    float* s = nullptr;
+    int Kp = 0, Mp = 0;
+    static size_t bytes(int n, int nm) { return (size_t)2 * sp_round_up(n, SP_TK) * sp_round_up(nm, SP_TM) * 4; }
+};
+
+// carve one twiddle pair out of mem (bytes(n, nm) of it) and fill it
+static int make_twiddle(wass_ctx* c, hipStream_t s, char*& mem, int n, int nm, Twiddle& t)
+{
+    t.Kp = sp_round_up(n, SP_TK);
+    t.Mp = sp_round_up(nm, SP_TM);
+    t.c = (float*)mem;
+    t.s = t.c + (size_t)t.Kp * t.Mp;
+    mem += Twiddle::bytes(n, nm);
+    hipLaunchKernelGGL(k_dft_twiddle, dim3((t.Mp + 255) / 256, t.Kp), dim3(256), 0, s, t.c, t.s, n, nm, t.Mp);
+    WASS_HIP(c, hipGetLastError());
+    return WASS_OK;
+}
+
+static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace wass
+
+using namespace wass;
+
+struct wass_spec3d {
+    wass_ctx* c = nullptr;
+    int nt = 0, ny = 0, nx = 0, nxh = 0;
+    char* mem = nullptr;           // one allocation, carved below
+    float* raw = nullptr;          // staging of a host segment, [nt][ny][nx]
+    float* prep = nullptr;         // the prepared segment
+    float* a_re = nullptr; float* a_im = nullptr;   // [nt][ny][nxh]: x stage out, t stage out
+    float* b_re = nullptr; float* b_im = nullptr;   // y stage out
+    double* S = nullptr;           // the Welch sum, fftshifted
+    double* wt = nullptr; double* wy = nullptr; double* wx = nullptr;
+    float* cellmean = nullptr;
+    double* part = nullptr; double* mean = nullptr;
+    int* flag = nullptr;
+    int npart = 0, nseg = 0;
+    Twiddle tx, ty, tt;
+};
+
+namespace {
+
+struct Spec3dLayout {
+    size_t win, half, off_raw, off_prep, off_a, off_b, off_S, off_w, off_cell, off_part, off_flag, off_tw, total;
+};
+
+Spec3dLayout spec3d_layout(int nt, int ny, int nx)
+{
+    Spec3dLayout L;
+    const int nxh = nx / 2 + 1;
+    L.win = (size_t)nt * ny * nx;
+    L.half = (size_t)nt * ny * nxh;
+    size_t o = 0;
+    L.off_raw = o;  o += align256(L.win * 4);
+    L.off_prep = o; o += align256(L.win * 4);
+    L.off_a = o;    o += align256(2 * L.half * 4);
+    L.off_b = o;    o += align256(2 * L.half * 4);
+    L.off_S = o;    o += align256(L.win * 8);
+    L.off_w = o;    o += align256((size_t)(nt + ny + nx) * 8);
+    L.off_cell = o; o += align256((size_t)ny * nx * 4);
+    L.off_part = o; o += align256((((size_t)ny * nx + 255) / 256 + 1) * 8);
+    L.off_flag = o; o += 256;
+    L.off_tw = o;   o += Twiddle::bytes(nx, nxh) + Twiddle::bytes(ny, ny) + Twiddle::bytes(nt, nt);
+    L.total = o;
+    return L;
+}
+
+bool spec3d_dims_ok(int nt, int ny, int nx)
+{
+    return nt >= 1 && ny >= 1 && nx >= 1 && nt <= SPEC_MAX_AXIS && ny <= SPEC_MAX_AXIS && nx <= SPEC_MAX_AXIS;
+}
+
+// symmetric Hann, scipy.signal.windows.hann(n): 0.5 - 0.5 cos(2 pi i / (n - 1)); hann(1) = [1]
+void hann_symmetric(int n, double* w)
+{
+    for (int i = 0; i < n; ++i) w[i] = n == 1 ? 1.0 : 0.5 - 0.5 * cos(6.283185307179586476925286766559 * (double)i / (double)(n - 1));
+}
+
+int spec3d_run(wass_spec3d* h, const float* d_seg, size_t stride_t, size_t stride_y, double datascale)
+{
+    wass_ctx* c = h->c;
+    hipStream_t s = c->ts();
+    const int nt = h->nt, ny = h->ny, nx = h->nx, nxh = h->nxh;
+    const size_t win = (size_t)nt * ny * nx;
+    const float ds = (float)datascale;
+    hipLaunchKernelGGL(k_seg_cell, dim3(h->npart), dim3(256), 0, s, d_seg, (long long)stride_t, (long long)stride_y, nt, ny, nx, ds, h->cellmean,
+                       h->part, h->flag);
+    hipLaunchKernelGGL(k_seg_mean, dim3(1), dim3(256), 0, s, (const double*)h->part, h->npart, (double)win, h->mean);
+    hipLaunchKernelGGL(k_seg_window, dim3((unsigned)((win + 255) / 256)), dim3(256), 0, s, d_seg, (long long)stride_t, (long long)stride_y, nt, ny,
+                       nx, ds, (const float*)h->cellmean, (const double*)h->mean, (const double*)h->wt, (const double*)h->wy,
+                       (const double*)h->wx, h->prep);
+    WASS_HIP(c, hipGetLastError());
+    int rc;
+    const long long plane = (long long)ny * nxh;
+    DftArgs x = {h->tx.c, h->tx.s, h->tx.Mp, h->prep, nullptr, h->a_re, h->a_im, nxh, nt * ny, nx, 1, nx, 0, 1, nxh, 0};
+    if ((rc = launch_dft(c, s, x, false, true, 1))) return rc;
+    DftArgs y = {h->ty.c, h->ty.s, h->ty.Mp, h->a_re, h->a_im, h->b_re, h->b_im, ny, nxh, ny, nxh, 1, plane, nxh, 1, plane};
+    if ((rc = launch_dft(c, s, y, true, false, nt))) return rc;
+    DftArgs t = {h->tt.c, h->tt.s, h->tt.Mp, h->b_re, h->b_im, h->a_re, h->a_im, nt, (int)plane, nt, plane, 1, 0, plane, 1, 0};
+    if ((rc = launch_dft(c, s, t, true, false, 1))) return rc;
+    hipLaunchKernelGGL(k_spec_power, dim3((unsigned)((win + 255) / 256)), dim3(256), 0, s, (const float*)h->a_re, (const float*)h->a_im, nt, ny, nx,
+                       nxh, h->S);
+    WASS_HIP(c, hipGetLastError());
+    ++h->nseg;
+    return WASS_OK;
+}
+
+}  // namespace
+
+extern "C" int wass_spec3d_scratch_bytes(int nt, int ny, int nx, size_t* bytes)
+{
+    if (!bytes || !spec3d_dims_ok(nt, ny, nx)) return WASS_ERR_INVALID_ARG;
+    *bytes = spec3d_layout(nt, ny, nx).total;
+    return WASS_OK;
+}
+
+extern "C" void wass_spec3d_destroy(wass_spec3d* h)
+{
+    if (!h) return;
+    if (h->c) (void)hipSetDevice(h->c->device);
+    if (h->mem) (void)hipFree(h->mem);
+    delete h;
+}
+
+extern "C" int wass_spec3d_create(wass_ctx* c, int nt, int ny, int nx, const double* win_t, const double* win_y, const double* win_x,
+                                  wass_spec3d** out)
+{
+    if (!c || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!spec3d_dims_ok(nt, ny, nx)) return set_err(c, WASS_ERR_INVALID_ARG, "bad window size %d x %d x %d (each axis 1 .. %d)", nt, ny, nx, SPEC_MAX_AXIS);
+    const Spec3dLayout L = spec3d_layout(nt, ny, nx);
+    if ((size_t)ny * (nx / 2 + 1) > 0x7fffffffu || (size_t)nt * ny > 0x7fffffffu) return set_err(c, WASS_ERR_UNSUPPORTED, "window too large");
+    if (L.total > SPEC_SCRATCH_CAP)
+        return set_err(c, WASS_ERR_NO_MEMORY, "a %d x %d x %d window needs %zu bytes of scratch, the cap is %zu", nt, ny, nx, L.total, SPEC_SCRATCH_CAP);
+    WASS_HIP(c, hipSetDevice(c->device));
+    wass_spec3d* h = new (std::nothrow) wass_spec3d;
+    if (!h) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
+    h->c = c; h->nt = nt; h->ny = ny; h->nx = nx; h->nxh = nx / 2 + 1;
+    hipError_t e = hipMalloc((void**)&h->mem, L.total);
+    if (e != hipSuccess) {
+        h->mem = nullptr;
+        wass_spec3d_destroy(h);
+        return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the spectrum scratch: %s", L.total, hipGetErrorString(e));
+    }
+    h->raw = (float*)(h->mem + L.off_raw);
+    h->prep = (float*)(h->mem + L.off_prep);
+    h->a_re = (float*)(h->mem + L.off_a); h->a_im = h->a_re + L.half;
+    h->b_re = (float*)(h->mem + L.off_b); h->b_im = h->b_re + L.half;
+    h->S = (double*)(h->mem + L.off_S);
+    h->wt = (double*)(h->mem + L.off_w); h->wy = h->wt + nt; h->wx = h->wy + ny;
+    h->cellmean = (float*)(h->mem + L.off_cell);
+    h->part = (double*)(h->mem + L.off_part);
+    h->npart = (int)(((size_t)ny * nx + 255) / 256);
+    h->mean = h->part + h->npart;
+    h->flag = (int*)(h->mem + L.off_flag);
+    hipStream_t s = c->ts();
+    std::vector<double> w((size_t)nt + ny + nx);
+    if (win_t) memcpy(&w[0], win_t, (size_t)nt * 8); else hann_symmetric(nt, &w[0]);
+    if (win_y) memcpy(&w[nt], win_y, (size_t)ny * 8); else hann_symmetric(ny, &w[nt]);
+    if (win_x) memcpy(&w[(size_t)nt + ny], win_x, (size_t)nx * 8); else hann_symmetric(nx, &w[(size_t)nt + ny]);
+    int rc = WASS_OK;
+    char* tw = h->mem + L.off_tw;
+    if (hipMemcpyAsync(h->wt, w.data(), w.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(h->S, 0, L.win * 8, s) != hipSuccess || hipMemsetAsync(h->flag, 0, 256, s) != hipSuccess)
+        rc = set_err(c, WASS_ERR_DEVICE, "spectrum set-up failed");
+    if (!rc) rc = make_twiddle(c, s, tw, nx, h->nxh, h->tx);
+    if (!rc) rc = make_twiddle(c, s, tw, ny, ny, h->ty);
+    if (!rc) rc = make_twiddle(c, s, tw, nt, nt, h->tt);
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "spectrum set-up failed");   // w leaves scope
+    if (rc) {
+        wass_spec3d_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return WASS_OK;
+}
+
+extern "C" int wass_spec3d_push_dev(wass_spec3d* h, const float* d_seg, size_t stride_t, size_t stride_y, double datascale)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    if (!d_seg || stride_y < (size_t)h->nx || stride_t < (size_t)h->nx) return set_err(c, WASS_ERR_INVALID_ARG, "bad segment pointer or strides");
+    WASS_HIP(c, hipSetDevice(c->device));
+    return spec3d_run(h, d_seg, stride_t, stride_y, datascale);
+}
+
+extern "C" int wass_spec3d_push(wass_spec3d* h, const float* seg, size_t stride_t, size_t stride_y, double datascale)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    if (!seg || stride_y < (size_t)h->nx || stride_t < (size_t)h->nx) return set_err(c, WASS_ERR_INVALID_ARG, "bad segment pointer or strides");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    const size_t slab = (size_t)h->ny * h->nx, row = (size_t)h->nx * 4;
+    for (int t = 0; t < h->nt; ++t)
+        WASS_HIP(c, hipMemcpy2DAsync(h->raw + t * slab, row, seg + t * stride_t, stride_y * 4, row, h->ny, hipMemcpyHostToDevice, s));
+    return spec3d_run(h, h->raw, slab, h->nx, datascale);
+}
+
+extern "C" int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* n_segments, int* had_all_nan_cell)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    if (!S) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (!h->nseg) return set_err(c, WASS_ERR_INVALID_ARG, "no segment was pushed");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    const size_t win = (size_t)h->nt * h->ny * h->nx;
+    int flag = 0;
+    hipLaunchKernelGGL(k_spec_scale, dim3((unsigned)((win + 255) / 256)), dim3(256), 0, s, h->S, win, scale);
+    WASS_HIP(c, hipGetLastError());
+    WASS_HIP(c, hipMemcpyAsync(S, h->S, win * 8, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemcpyAsync(&flag, h->flag, sizeof flag, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemsetAsync(h->S, 0, win * 8, s));          // the handle starts over
+    WASS_HIP(c, hipMemsetAsync(h->flag, 0, 256, s));
+    WASS_HIP(c, hipStreamSynchronize(s));
+    if (n_segments) *n_segments = h->nseg;
+    if (had_all_nan_cell) *had_all_nan_cell = flag;
+    h->nseg = 0;
+    return WASS_OK;
+}
+
+extern "C" int wass_spec1d_welch(wass_ctx* c, const float* series, int n_series, int n_samples, int nperseg, double fs, double scale, double* S)
+{
+    if (!c || !series || !S) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (n_series < 1 || n_series > 65535 || n_samples < 2 || nperseg < 2 || !(fs > 0))
+        return set_err(c, WASS_ERR_INVALID_ARG, "bad argument (series %d, samples %d, nperseg %d, fs %g)", n_series, n_samples, nperseg, fs);
+    const int nps = nperseg < n_samples ? nperseg : n_samples;       // scipy.signal.csd shrinks nperseg to the series
+    if (nps > SPEC_MAX_AXIS) return set_err(c, WASS_ERR_UNSUPPORTED, "nperseg %d > %d", nps, SPEC_MAX_AXIS);
+    const int nov = nps / 2, step = nps - nov, nseg = (n_samples - nov) / step, nf = nps / 2 + 1;
+    if (nseg < 1 || nseg > 65535) return set_err(c, WASS_ERR_INVALID_ARG, "no segment fits");
+    const size_t ncol = (size_t)n_series * nseg;
+    if (ncol > 0x7fffffffu) return set_err(c, WASS_ERR_UNSUPPORTED, "too many segments");
+    size_t o = 0;
+    const size_t off_x = o;   o += align256((size_t)n_series * n_samples * 4);
+    const size_t off_m = o;   o += align256((size_t)n_series * 8);
+    const size_t off_w = o;   o += align256((size_t)nps * 8);
+    const size_t off_B = o;   o += align256((size_t)nps * ncol * 4);
+    const size_t off_X = o;   o += align256((size_t)2 * nf * ncol * 4);
+    const size_t off_o = o;   o += align256((size_t)nf * 8);
+    const size_t off_tw = o;  o += Twiddle::bytes(nps, nf);
+    if (o > SPEC_SCRATCH_CAP) return set_err(c, WASS_ERR_NO_MEMORY, "the Welch estimate needs %zu bytes of scratch, the cap is %zu", o, SPEC_SCRATCH_CAP);
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    char* mem = nullptr;
+    if (hipMalloc((void**)&mem, o) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the Welch scratch failed", o);
+    float* d_x = (float*)(mem + off_x);
+    double* d_m = (double*)(mem + off_m);
+    double* d_w = (double*)(mem + off_w);
+    float* d_B = (float*)(mem + off_B);
+    float* d_Xre = (float*)(mem + off_X);
+    float* d_Xim = d_Xre + (size_t)nf * ncol;
+    double* d_o = (double*)(mem + off_o);
+    // periodic Hann (scipy's get_window('hann', n)): 0.5 - 0.5 cos(2 pi i / n)
+    std::vector<double> w(nps);
+    double sw2 = 0.0;
+    for (int i = 0; i < nps; ++i) {
+        w[i] = 0.5 - 0.5 * cos(6.283185307179586476925286766559 * (double)i / (double)nps);
+        sw2 += w[i] * w[i];
+    }
+    const double dens = 1.0 / (fs * sw2) / (double)nseg;             // density scaling, mean over the segments
+    int rc = WASS_OK;
+    Twiddle tw;
+    char* twm = mem + off_tw;
+    hipError_t e = hipMemcpyAsync(d_x, series, (size_t)n_series * n_samples * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_w, w.data(), (size_t)nps * 8, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "upload of the series: %s", hipGetErrorString(e));
+    if (!rc) rc = make_twiddle(c, s, twm, nps, nf, tw);
+    if (!rc) {
+        const float sc = (float)scale;
+        hipLaunchKernelGGL(k_w1_mean, dim3(n_series), dim3(256), 0, s, (const float*)d_x, n_samples, sc, d_m);
+        hipLaunchKernelGGL(k_w1_prep, dim3(nseg, n_series), dim3(256), 0, s, (const float*)d_x, n_samples, sc, (const double*)d_m, nps, step, nseg,
+                           (const double*)d_w, d_B);
+        DftArgs a = {tw.c, tw.s, tw.Mp, d_B, nullptr, d_Xre, d_Xim, nf, (int)ncol, nps, (long long)ncol, 1, 0, (long long)ncol, 1, 0};
+        rc = launch_dft(c, s, a, false, false, 1);
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(k_w1_power, dim3(nf), dim3(256), 0, s, (const float*)d_Xre, (const float*)d_Xim, ncol, dens, nps, d_o);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(S, d_o, (size_t)nf * 8, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "Welch estimate: %s", hipGetErrorString(e));
+    }
+    e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "Welch estimate: %s", hipGetErrorString(e));
+    (void)hipFree(mem);
+    return rc;
+}
