@@ -628,6 +628,40 @@ void wass_spec3d_destroy(wass_spec3d* h);
 int wass_spec1d_welch(wass_ctx* ctx, const float* series, int n_series, int n_samples, int nperseg, double fs, double scale,
                       double* S);
 
+/* ---- Butterworth filters of the gridded cube: wasspost filter / filter_fast (wasspost.py:149-314) and spatial_lowpass
+ * (:318-371) as array functions.  The host designs the filters (wass_amd/postproc.py: butter_sos, sosfilt_zi).
+ * wass_sosfiltfilt: scipy.signal.sosfiltfilt(sos, x, axis=0) with scipy's defaults for every cell of a count x H x W float32
+ * cube, cell (t, y, x) at in[t * stride_t + y * stride_y + x] (strides in elements), the result as float32 at out with its own
+ * strides (out may be in).  sos is n_sections x 6 doubles (b0 b1 b2 1 a1 a2, 1 .. 6 sections), zi n_sections x 2 doubles
+ * (sosfilt_zi), padlen scipy's default for these sections (count > padlen, else WASS_ERR_INVALID_ARG).  The odd padding is
+ * built in float32 as scipy builds it; both passes run in fp64 in scipy's order of operations and hand over in fp64;
+ * remove_mean != 0 subtracts every series' fp64 time mean (summed first frame to last) before the cast.  A series that holds
+ * a NaN comes out NaN throughout, no other is touched.  Rows are filtered in slabs of at most slab_rows (0: as many as fit
+ * 16 GiB of scratch: (count + 2 padlen) * rows * W * 8 bytes, plus count * rows * W * 4 for the host form);
+ * wass_sosfiltfilt_scratch_bytes says how much and how many rows, without a GPU.  The result does not depend on the slab
+ * height and is the same bits on every run.  The host form returns with out filled; the device form enqueues on the
+ * context's stream and frees its scratch after a synchronisation. */
+int wass_sosfiltfilt_scratch_bytes(int count, int H, int W, int padlen, int slab_rows, int host, size_t* bytes, int* rows_per_slab);
+int wass_sosfiltfilt(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride_y, int count, int H, int W, const double* sos,
+                     int n_sections, const double* zi, int padlen, int remove_mean, int slab_rows, float* out, size_t out_stride_t,
+                     size_t out_stride_y);
+int wass_sosfiltfilt_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W,
+                         const double* sos, int n_sections, const double* zi, int padlen, int remove_mean, int slab_rows,
+                         float* d_out, size_t out_stride_t, size_t out_stride_y);
+/* Spatial2DButterworth (spectra.py:176-202): out = real(ifft2(fft2(frame) * H)) per rows x cols float32 frame, H the UN-shifted
+ * transfer function (rows x cols doubles, real and even: np.fft.ifftshift of the reference's array).  The transforms are the
+ * DFT stages of the spectrum on the f32 MFMA, `batch` frames per launch (halved until the scratch fits 16 GiB;
+ * wass_spatial_filter_scratch_bytes says how much).  A frame that holds a NaN comes out all NaN, no other is touched.  apply:
+ * host frames, returns with out filled; apply_dev: device frames, enqueued on the context's stream (out may be the input). */
+typedef struct wass_spatial_filter wass_spatial_filter;
+int wass_spatial_filter_scratch_bytes(int rows, int cols, int batch, size_t* bytes);
+int wass_spatial_filter_create(wass_ctx* ctx, int rows, int cols, const double* H, int batch, wass_spatial_filter** out);
+int wass_spatial_filter_apply(wass_spatial_filter* h, const float* frames, size_t stride_t, size_t stride_y, int n_frames,
+                              float* out, size_t out_stride_t, size_t out_stride_y);
+int wass_spatial_filter_apply_dev(wass_spatial_filter* h, const float* d_frames, size_t stride_t, size_t stride_y, int n_frames,
+                                  float* d_out, size_t out_stride_t, size_t out_stride_y);
+void wass_spatial_filter_destroy(wass_spatial_filter* h);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

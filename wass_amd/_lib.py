@@ -205,6 +205,14 @@ SYMBOLS = {
     "wass_spec3d_finish": (_i, [_vp, C.c_double, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "wass_spec3d_destroy": (None, [_vp]),
     "wass_spec1d_welch": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, _vp]),
+    "wass_sosfiltfilt_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_sosfiltfilt": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_sosfiltfilt_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_spatial_filter_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "wass_spatial_filter_create": (_i, [_vp, _i, _i, _vp, _i, C.POINTER(_vp)]),
+    "wass_spatial_filter_apply": (_i, [_vp, _vp, _sz, _sz, _i, _vp, _sz, _sz]),
+    "wass_spatial_filter_apply_dev": (_i, [_vp, _vp, _sz, _sz, _i, _vp, _sz, _sz]),
+    "wass_spatial_filter_destroy": (None, [_vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

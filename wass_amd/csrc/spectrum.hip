@@ -601,3 +601,199 @@ extern "C" int wass_spec1d_welch(wass_ctx* c, const float* series, int n_series,
     (void)hipFree(mem);
     return rc;
 }
+
+// ---- the spatial Butterworth low-pass (postproc/wasspost/spectra.py:176-202, wasspost spatial_lowpass) -------------------------
+// real(ifft2(fft2(z) * H)) per frame with the stages above, a batch of frames per launch (blockIdx.z):
+//   x   real [b][r][x]      -> complex [b][r][kx], kx = 0 .. cols / 2
+//   y   complex [b][r][kx]  -> complex [b][ky][kx]
+//   k_spat_mul              X -> conj(X) * H[ky][kx] * w[kx] / (rows cols), fp64 product, one rounding; w = 2 for the columns that
+//                           stand for their mirror image too (all but kx = 0 and, cols even, Nyquist)
+//   y   again: H is real and even, so the inverse is the conjugate of the forward transform of the conjugate
+//   x   complex [b][r][kx]  -> [b][r][x], contraction over kx <= cols / 2 only; its real part is the result: the row's spectrum
+//                           is Hermitian, Re(conj(Z) e^{+i a}) = Re(Z e^{-i a}) is what the forward stage computes
+// H comes from the host un-shifted: the reference's fftshift / ifftshift pair around the product is a permutation of H.
+// A NaN spreads over its frame in the x and y stages and over no other: the frames of a batch share no tile.
+namespace wass {
+
+__global__ void __launch_bounds__(256) k_spat_mul(float* __restrict__ re, float* __restrict__ im, const double* __restrict__ Hw, size_t plane,
+                                                  size_t total)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const double h = Hw[i % plane];
+    re[i] = (float)((double)re[i] * h);
+    im[i] = (float)(-((double)im[i] * h));
+}
+
+}  // namespace wass
+
+struct wass_spatial_filter {
+    wass_ctx* c = nullptr;
+    int rows = 0, cols = 0, ch = 0, batch = 0;
+    char* mem = nullptr;
+    float* io = nullptr;            // [batch][rows][cols]: staged input of the host entry, then the result
+    float* dump = nullptr;          // the last stage's imaginary part
+    float* a_re = nullptr; float* a_im = nullptr;   // [batch][rows][ch]
+    float* b_re = nullptr; float* b_im = nullptr;
+    double* Hw = nullptr;           // [rows][ch]
+    Twiddle tx, ty;
+};
+
+namespace {
+
+struct SpatLayout {
+    size_t frame, half, off_io, off_dump, off_a, off_b, off_H, off_tw, total;
+};
+
+bool spat_dims_ok(int rows, int cols, int batch)
+{
+    return rows >= 1 && cols >= 1 && rows <= SPEC_MAX_AXIS && cols <= SPEC_MAX_AXIS && batch >= 1 && batch <= 65535;
+}
+
+SpatLayout spat_layout(int rows, int cols, int batch)
+{
+    SpatLayout L;
+    const int ch = cols / 2 + 1;
+    L.frame = (size_t)rows * cols;
+    L.half = (size_t)rows * ch;
+    size_t o = 0;
+    L.off_io = o;   o += align256(L.frame * batch * 4);
+    L.off_dump = o; o += align256(L.frame * batch * 4);
+    L.off_a = o;    o += align256(2 * L.half * batch * 4);
+    L.off_b = o;    o += align256(2 * L.half * batch * 4);
+    L.off_H = o;    o += align256(L.half * 8);
+    L.off_tw = o;   o += Twiddle::bytes(cols, cols) + Twiddle::bytes(rows, rows);
+    L.total = o;
+    return L;
+}
+
+// nb frames at d_in (element strides st, sy) -> h->io, [nb][rows][cols]
+int spat_run(wass_spatial_filter* h, const float* d_in, long long st, long long sy, int nb)
+{
+    wass_ctx* c = h->c;
+    hipStream_t s = c->ts();
+    const int R = h->rows, Cn = h->cols, ch = h->ch;
+    const long long half = (long long)R * ch, frame = (long long)R * Cn;
+    int rc;
+    DftArgs x = {h->tx.c, h->tx.s, h->tx.Mp, d_in, nullptr, h->a_re, h->a_im, ch, R, Cn, 1, sy, st, 1, ch, half};
+    if ((rc = launch_dft(c, s, x, false, true, nb))) return rc;
+    DftArgs y = {h->ty.c, h->ty.s, h->ty.Mp, h->a_re, h->a_im, h->b_re, h->b_im, R, ch, R, ch, 1, half, ch, 1, half};
+    if ((rc = launch_dft(c, s, y, true, false, nb))) return rc;
+    const size_t total = (size_t)half * nb;
+    hipLaunchKernelGGL(k_spat_mul, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->b_re, h->b_im, (const double*)h->Hw, (size_t)half, total);
+    WASS_HIP(c, hipGetLastError());
+    DftArgs yi = {h->ty.c, h->ty.s, h->ty.Mp, h->b_re, h->b_im, h->a_re, h->a_im, R, ch, R, ch, 1, half, ch, 1, half};
+    if ((rc = launch_dft(c, s, yi, true, false, nb))) return rc;
+    DftArgs xi = {h->tx.c, h->tx.s, h->tx.Mp, h->a_re, h->a_im, h->io, h->dump, Cn, R, ch, 1, ch, half, 1, Cn, frame};
+    return launch_dft(c, s, xi, true, true, nb);
+}
+
+int spat_apply(wass_spatial_filter* h, bool host, const float* in, size_t st, size_t sy, int n, float* out, size_t ost, size_t osy)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    if (!in || !out || n < 0 || sy < (size_t)h->cols || osy < (size_t)h->cols || (n > 1 && (st < (size_t)h->cols || ost < (size_t)h->cols)))
+        return set_err(c, WASS_ERR_INVALID_ARG, "bad frame pointer, count or strides");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    const size_t frame = (size_t)h->rows * h->cols, rowb = (size_t)h->cols * 4;
+    const hipMemcpyKind up = hipMemcpyHostToDevice, down = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    for (int f0 = 0; f0 < n; f0 += h->batch) {
+        const int nb = n - f0 < h->batch ? n - f0 : h->batch;
+        int rc;
+        if (host) {
+            for (int b = 0; b < nb; ++b)
+                WASS_HIP(c, hipMemcpy2DAsync(h->io + b * frame, rowb, in + (f0 + b) * st, sy * 4, rowb, h->rows, up, s));
+            rc = spat_run(h, h->io, (long long)frame, h->cols, nb);
+        } else {
+            rc = spat_run(h, in + (size_t)f0 * st, (long long)st, (long long)sy, nb);
+        }
+        if (rc) return rc;
+        for (int b = 0; b < nb; ++b)
+            WASS_HIP(c, hipMemcpy2DAsync(out + (f0 + b) * ost, osy * 4, h->io + b * frame, rowb, rowb, h->rows, down, s));
+    }
+    if (host) WASS_HIP(c, hipStreamSynchronize(s));
+    return WASS_OK;
+}
+
+}  // namespace
+
+extern "C" int wass_spatial_filter_scratch_bytes(int rows, int cols, int batch, size_t* bytes)
+{
+    if (!bytes || !spat_dims_ok(rows, cols, batch)) return WASS_ERR_INVALID_ARG;
+    *bytes = spat_layout(rows, cols, batch).total;
+    return WASS_OK;
+}
+
+extern "C" void wass_spatial_filter_destroy(wass_spatial_filter* h)
+{
+    if (!h) return;
+    if (h->c) (void)hipSetDevice(h->c->device);
+    if (h->mem) {
+        (void)hipDeviceSynchronize();
+        (void)hipFree(h->mem);
+    }
+    delete h;
+}
+
+extern "C" int wass_spatial_filter_create(wass_ctx* c, int rows, int cols, const double* H, int batch, wass_spatial_filter** out)
+{
+    if (!c || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!H) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (!spat_dims_ok(rows, cols, batch))
+        return set_err(c, WASS_ERR_INVALID_ARG, "bad frame size %d x %d (each axis 1 .. %d) or batch %d", rows, cols, SPEC_MAX_AXIS, batch);
+    // no more frames per batch than the cap allows
+    while (batch > 1 && spat_layout(rows, cols, batch).total > SPEC_SCRATCH_CAP) batch /= 2;
+    const SpatLayout L = spat_layout(rows, cols, batch);
+    if (L.total > SPEC_SCRATCH_CAP)
+        return set_err(c, WASS_ERR_NO_MEMORY, "a %d x %d frame needs %zu bytes of scratch, the cap is %zu", rows, cols, L.total, SPEC_SCRATCH_CAP);
+    WASS_HIP(c, hipSetDevice(c->device));
+    wass_spatial_filter* h = new (std::nothrow) wass_spatial_filter;
+    if (!h) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
+    h->c = c; h->rows = rows; h->cols = cols; h->ch = cols / 2 + 1; h->batch = batch;
+    hipError_t e = hipMalloc((void**)&h->mem, L.total);
+    if (e != hipSuccess) {
+        h->mem = nullptr;
+        wass_spatial_filter_destroy(h);
+        return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the spatial filter's scratch: %s", L.total, hipGetErrorString(e));
+    }
+    h->io = (float*)(h->mem + L.off_io);
+    h->dump = (float*)(h->mem + L.off_dump);
+    h->a_re = (float*)(h->mem + L.off_a); h->a_im = h->a_re + L.half * batch;
+    h->b_re = (float*)(h->mem + L.off_b); h->b_im = h->b_re + L.half * batch;
+    h->Hw = (double*)(h->mem + L.off_H);
+    const int ch = h->ch;
+    std::vector<double> hw(L.half);
+    const double inv = 1.0 / ((double)rows * (double)cols);
+    for (int ky = 0; ky < rows; ++ky)
+        for (int kx = 0; kx < ch; ++kx) {
+            const bool alone = kx == 0 || (cols % 2 == 0 && kx == cols / 2);
+            hw[(size_t)ky * ch + kx] = H[(size_t)ky * cols + kx] * (alone ? 1.0 : 2.0) * inv;
+        }
+    hipStream_t s = c->ts();
+    int rc = WASS_OK;
+    char* tw = h->mem + L.off_tw;
+    if (hipMemcpyAsync(h->Hw, hw.data(), L.half * 8, hipMemcpyHostToDevice, s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "spatial filter set-up failed");
+    if (!rc) rc = make_twiddle(c, s, tw, cols, cols, h->tx);
+    if (!rc) rc = make_twiddle(c, s, tw, rows, rows, h->ty);
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "spatial filter set-up failed");   // hw leaves scope
+    if (rc) {
+        wass_spatial_filter_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return WASS_OK;
+}
+
+extern "C" int wass_spatial_filter_apply(wass_spatial_filter* h, const float* frames, size_t stride_t, size_t stride_y, int n_frames, float* out,
+                                         size_t out_stride_t, size_t out_stride_y)
+{
+    return spat_apply(h, true, frames, stride_t, stride_y, n_frames, out, out_stride_t, out_stride_y);
+}
+
+extern "C" int wass_spatial_filter_apply_dev(wass_spatial_filter* h, const float* d_frames, size_t stride_t, size_t stride_y, int n_frames,
+                                             float* d_out, size_t out_stride_t, size_t out_stride_y)
+{
+    return spat_apply(h, false, d_frames, stride_t, stride_y, n_frames, d_out, out_stride_t, out_stride_y);
+}

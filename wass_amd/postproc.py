@@ -199,3 +199,316 @@ def spectrum_statistics(freq, S) -> dict:
     pp = float(freq[np.argmax(S)])
     return {"Hm0": float(4.0 * np.sqrt(m0)), "peak_frequency": pp, "peak_period": float(1.0 / pp) if pp != 0 else float("inf"),
             "Tm01": float(m0 / m1)}
+
+
+# ---- Butterworth filters of the cube: wasspost filter / filter_fast (wasspost.py:149-314) and spatial_lowpass (:318-371) --------
+def _conjugate_halves(v):
+    """Roots of a real polynomial as (one of every conjugate pair, imaginary part > 0; the real ones), sorted like scipy's
+    _cplxreal: by real part, ties by |imaginary part|; a pair is the mean of one root and its partner's conjugate."""
+    v = np.atleast_1d(np.asarray(v, np.complex128))
+    tol = 100.0 * np.finfo(np.float64).eps
+    v = v[np.lexsort((np.abs(v.imag), v.real))]
+    is_real = np.abs(v.imag) <= tol * np.abs(v)
+    reals, v = v[is_real].real, v[~is_real]
+    up, dn = v[v.imag > 0], v[v.imag < 0]
+    if len(up) != len(dn):
+        raise ValueError("roots are not conjugate pairs")
+    # runs of the same real part are ordered by |imaginary part| in both halves, so that partners meet
+    same = np.diff(up.real) <= tol * np.abs(up[:-1])
+    edges = np.diff(np.concatenate(([0], same.astype(int), [0])))
+    for a, b in zip(np.nonzero(edges > 0)[0], np.nonzero(edges < 0)[0]):
+        for half in (up, dn):
+            half[a:b + 1] = half[a:b + 1][np.lexsort([np.abs(half[a:b + 1].imag)])]
+    return (up + dn.conj()) / 2.0, reals
+
+
+def _nearest(values, to, real):
+    """Index of the element of `values` nearest to `to` among the real (or, real=False, the complex) ones."""
+    order = np.argsort(np.abs(values - to))
+    mask = np.isreal(values[order])
+    return order[np.nonzero(mask if real else ~mask)[0][0]]
+
+
+def _section(zeros, poles) -> np.ndarray:
+    """[b0 b1 b2 a0 a1 a2] of one section with gain 1; a pair of conjugates gives real coefficients."""
+    def poly(r):
+        c = np.ones(1, np.complex128)
+        for v in r:
+            c = np.convolve(c, np.array([1.0, -v], np.complex128))
+        return c.real
+    out = np.zeros(6)
+    b, a = poly(zeros), poly(poles)
+    out[3 - len(b):3] = b
+    out[6 - len(a):6] = a
+    return out
+
+
+def butter_sos(order: int, cutoff: float, btype: str = "lowpass", fs: float = 2.0) -> np.ndarray:
+    """scipy.signal.butter(order, cutoff, btype=btype, output='sos', fs=fs) for 'lowpass' and 'highpass', float64 [n_sections, 6]:
+    the analog prototype's poles on the unit circle, the cutoff pre-warped, the bilinear transform, then scipy's pairing
+    (zpk2sos, 'nearest'): the pole nearest the unit circle is picked first and lands in the LAST section, every pole takes the
+    zero nearest to it, the gain goes into section 0."""
+    order = int(order)
+    if order < 1:
+        raise ValueError("order must be at least 1")
+    if btype not in ("lowpass", "highpass"):
+        raise ValueError("btype must be 'lowpass' or 'highpass'")
+    wn = 2.0 * float(cutoff) / float(fs)
+    if not 0.0 < wn < 1.0:
+        raise ValueError("the cutoff must lie between 0 and fs / 2")
+    m = np.arange(-order + 1, order, 2)
+    p = -np.exp(1j * np.pi * m / (2 * order))                  # prototype: no zeros, gain 1
+    warped = 4.0 * np.tan(np.pi * wn / 2.0)                    # 2 fs tan(pi wn / fs) with the design's fs = 2
+    if btype == "lowpass":
+        p, z, k = warped * p, np.zeros(0, np.complex128), warped ** order
+    else:
+        k = float(np.real(1.0 / np.prod(-p)))
+        p, z = warped / p, np.zeros(order, np.complex128)
+    # bilinear transform, fs2 = 2 * 2
+    k = k * float(np.real(np.prod(4.0 - z) / np.prod(4.0 - p)))
+    z = np.append((4.0 + z) / (4.0 - z), -np.ones(order - len(z)))
+    p = (4.0 + p) / (4.0 - p)
+    # sections
+    n_sections = (order + 1) // 2
+    if order % 2:
+        p, z = np.append(p, 0.0), np.append(z, 0.0)
+    z = np.concatenate(_conjugate_halves(z))
+    p = np.concatenate(_conjugate_halves(p))
+    worst = lambda q: int(np.argmin(np.abs(1.0 - np.abs(q))))
+    sos = np.zeros((n_sections, 6))
+    for si in range(n_sections - 1, -1, -1):
+        i = worst(p)
+        p1, p = p[i], np.delete(p, i)
+        if np.isreal(p1) and np.isreal(p).sum() == 0:          # the last real pole
+            i = _nearest(z, p1, True)
+            z1, z = z[i], np.delete(z, i)
+            sos[si] = _section([z1, 0.0], [p1, 0.0])
+        elif len(p) + 1 == len(z) and not np.isreal(p1) and np.isreal(p).sum() == 1 and np.isreal(z).sum() == 1:
+            i = _nearest(z, p1, False)                         # one real pole and one real zero are left: take a complex zero
+            z1, z = z[i], np.delete(z, i)
+            sos[si] = _section([z1, z1.conj()], [p1, p1.conj()])
+        else:
+            if np.isreal(p1):
+                ri = np.flatnonzero(np.isreal(p))
+                i = ri[worst(p[ri])]
+                p2, p = p[i], np.delete(p, i)
+            else:
+                p2 = p1.conj()
+            i = int(np.argmin(np.abs(p1 - z)))
+            z1, z = z[i], np.delete(z, i)
+            if not np.isreal(z1):
+                sos[si] = _section([z1, z1.conj()], [p1, p2])
+            else:
+                i = _nearest(z, p1, True)
+                z2, z = z[i], np.delete(z, i)
+                sos[si] = _section([z1, z2], [p1, p2])
+    assert len(p) == 0 and len(z) == 0
+    sos[0, :3] *= k
+    return sos
+
+
+def _check_sos(sos) -> np.ndarray:
+    sos = np.ascontiguousarray(sos, np.float64)
+    if sos.ndim != 2 or sos.shape[1] != 6 or sos.shape[0] < 1:
+        raise ValueError("sos must be n_sections x 6")
+    if sos.shape[0] > 6:
+        raise ValueError("at most 6 sections (order 12)")
+    if not (sos[:, 3] == 1.0).all():
+        raise ValueError("sos[:, 3] should be all ones")
+    return sos
+
+
+def sos_padlen(sos) -> int:
+    """sosfiltfilt's default padlen: 3 * (2 n_sections + 1 - min(#(b2 == 0), #(a2 == 0)))."""
+    sos = _check_sos(sos)
+    return 3 * (2 * sos.shape[0] + 1 - int(min((sos[:, 2] == 0).sum(), (sos[:, 5] == 0).sum())))
+
+
+def sosfilt_zi(sos) -> np.ndarray:
+    """scipy.signal.sosfilt_zi: the state [n_sections, 2] of the step response's steady state, in closed form per section
+    (zi0 = (B0 + B1) / (1 + a1 + a2), zi1 = (1 + a1) zi0 - B0 with B = b[1:] - a[1:] b0), scaled by the DC gain of the sections before."""
+    sos = _check_sos(sos)
+    zi = np.empty((sos.shape[0], 2))
+    scale = 1.0
+    for s in range(sos.shape[0]):
+        b, a = sos[s, :3], sos[s, 3:]
+        B = b[1:] - a[1:] * b[0]
+        z0 = B.sum() / (1.0 + a[1] + a[2])
+        zi[s] = scale * np.array([z0, (1.0 + a[1]) * z0 - B[0]])
+        scale *= b.sum() / a.sum()
+    return zi
+
+
+def sosfiltfilt_scratch_bytes(count: int, H: int, W: int, padlen: int, slab_rows: int = 0, host: bool = True):
+    """(bytes of device scratch, rows per slab) of one sosfiltfilt call; no GPU needed."""
+    from . import _lib
+    b, r = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_sosfiltfilt_scratch_bytes(int(count), int(H), int(W), int(padlen), int(slab_rows), int(bool(host)), C.byref(b), C.byref(r))
+    if rc:
+        raise ValueError(f"wass_sosfiltfilt_scratch_bytes({count}, {H}, {W}, padlen {padlen}): error {rc}")
+    return b.value, r.value
+
+
+def _is_device(a) -> bool:
+    return hasattr(a, "data_ptr")
+
+
+def _host_f32_rows(a) -> np.ndarray:
+    """a count x H x W float32 host array whose last axis is contiguous and whose other strides are whole, positive elements (a
+    slice or a memmap passes as it is)."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.strides[2] != 4 or a.strides[0] % 4 or a.strides[1] % 4 \
+            or a.strides[0] <= 0 or a.strides[1] <= 0:
+        a = np.ascontiguousarray(a, np.float32)
+    return a
+
+
+def sosfiltfilt(sos, data, remove_mean: bool = False, ctx: Context | None = None, out=None, slab_rows: int = 0):
+    """scipy.signal.sosfiltfilt(sos, data, axis=0) with scipy's defaults (odd padding of sos_padlen samples built in float32, both
+    passes started from sosfilt_zi times their first sample, fp64 throughout), the result cast to float32; remove_mean=True
+    subtracts the fp64 time mean of every filtered series before the cast.  `data` is count x H x W float32: a host array or
+    memmap (the result is a host array, or `out`) or a device tensor (the result is a device tensor, or `out`; `out` may be
+    `data`).  slab_rows > 0 caps the rows filtered at a time (the result does not depend on it)."""
+    sos = _check_sos(sos)
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W = (int(v) for v in data.shape)
+    padlen = sos_padlen(sos)
+    if count <= padlen:
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {padlen}.")
+    if H < 1 or W < 1:
+        raise ValueError("empty grid")
+    zi = np.ascontiguousarray(sosfilt_zi(sos))
+    if ctx is None:
+        ctx = Context(0)
+    args = (sos.ctypes.data, sos.shape[0], zi.ctypes.data, padlen, int(bool(remove_mean)), int(slab_rows))
+    if _is_device(data):
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+        if out is None:
+            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
+        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or out.stride(2) != 1:
+            raise ValueError("out must be a float32 device tensor of the input's shape with a contiguous last axis")
+        torch.cuda.current_stream(data.device).synchronize()
+        ctx._check(ctx._lib.wass_sosfiltfilt_dev(ctx._h, data.data_ptr(), data.stride(0), data.stride(1), count, H, W, *args,
+                                                 out.data_ptr(), out.stride(0), out.stride(1)))
+        ctx.synchronize()
+        return out
+    src = _host_f32_rows(data)
+    if out is None:
+        out = np.empty((count, H, W), np.float32)
+    elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or out.strides[2] != 4 \
+            or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0:
+        raise ValueError("out must be a float32 host array of the input's shape with a contiguous last axis")
+    ctx._check(ctx._lib.wass_sosfiltfilt(ctx._h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W, *args,
+                                         out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4))
+    return out
+
+
+def butterworth_filter(data, dt: float, cutoff: float = 1.0, type: str = "lowpass", fast: bool = False, order: int = 8,
+                       ctx: Context | None = None, out=None, slab_rows: int = 0):
+    """wasspost filter as a function: an 8th-order zero-phase Butterworth filter along time with fs = 1 / dt; 'highpass' also
+    removes the time mean.  fast=True is wasspost filter_fast: fs = round(1 / dt) and no mean removal."""
+    if int(data.shape[0]) <= 10:
+        raise ValueError("more than 10 frames are needed")
+    if not dt > 0:
+        raise ValueError("dt must be positive")
+    fs = float(np.round(1.0 / dt)) if fast else 1.0 / dt
+    sos = butter_sos(order, cutoff, type, fs)
+    return sosfiltfilt(sos, data, remove_mean=(type == "highpass" and not fast), ctx=ctx, out=out, slab_rows=slab_rows)
+
+
+class Spatial2DButterworth:
+    """The reference's class (spectra.py:176-202) on the GPU.  It is called there with W, H = XX.shape, so W is the number of ROWS
+    of a surface and H the number of columns; butterworth_filter is the fftshifted transfer function [rows, cols], float64."""
+
+    def __init__(self, W: int, H: int, du: float, cutoff_fs: float, order: int, ctx: Context | None = None, batch: int = 16):
+        W, H = int(W), int(H)
+        if W < 1 or H < 1 or not du > 0:
+            raise ValueError("W, H >= 1 and du > 0 are needed")
+        fx = np.fft.fftshift(np.fft.fftfreq(W, d=du))
+        fy = np.fft.fftshift(np.fft.fftfreq(H, d=du))
+        FX, FY = np.meshgrid(fy, fx)                           # [rows, cols]: FX varies along the columns
+        R = np.sqrt(FX ** 2 + FY ** 2)
+        with np.errstate(divide="ignore"):
+            self.butterworth_filter = 1.0 / np.sqrt(1.0 + (R / cutoff_fs) ** (2 * order))
+        self.rows, self.cols, self.batch = W, H, max(1, int(batch))
+        self._ctx, self._h = ctx, None
+
+    def _handle(self):
+        if self._h is None:
+            if self._ctx is None:
+                self._ctx = Context(0)
+            # the fftshift / ifftshift pair around the product is an index permutation of the transfer function
+            Hu = np.ascontiguousarray(np.fft.ifftshift(self.butterworth_filter), np.float64)
+            h = C.c_void_p()
+            self._ctx._check(self._ctx._lib.wass_spatial_filter_create(self._ctx._h, self.rows, self.cols, Hu.ctypes.data, self.batch, C.byref(h)))
+            self._h = h
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._ctx._lib.wass_spatial_filter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply_batch(self, frames, out=None):
+        """frames: n x rows x cols float32, host or device; the filtered frames, float32, on the same side.  A frame that holds a NaN
+        comes out all NaN."""
+        if len(frames.shape) != 3 or tuple(int(v) for v in frames.shape[1:]) != (self.rows, self.cols):
+            raise ValueError(f"frames of shape {tuple(frames.shape)}, expected n x {self.rows} x {self.cols}")
+        n = int(frames.shape[0])
+        h, ctx = self._handle(), self._ctx
+        if _is_device(frames):
+            import torch
+            if frames.dtype != torch.float32 or frames.stride(2) != 1 or frames.stride(0) <= 0 or frames.stride(1) <= 0:
+                frames = frames.to(torch.float32).contiguous()
+            if out is None:
+                out = torch.empty((n, self.rows, self.cols), dtype=torch.float32, device=frames.device)
+            elif not _is_device(out) or tuple(out.shape) != tuple(frames.shape) or out.dtype != torch.float32 or out.stride(2) != 1:
+                raise ValueError("out must be a float32 device tensor of the input's shape with a contiguous last axis")
+            if n:
+                torch.cuda.current_stream(frames.device).synchronize()
+                ctx._check(ctx._lib.wass_spatial_filter_apply_dev(h, frames.data_ptr(), frames.stride(0), frames.stride(1), n,
+                                                                  out.data_ptr(), out.stride(0), out.stride(1)))
+                ctx.synchronize()
+            return out
+        src = _host_f32_rows(frames)
+        if out is None:
+            out = np.empty((n, self.rows, self.cols), np.float32)
+        elif not isinstance(out, np.ndarray) or out.shape != src.shape or out.dtype != np.float32 or out.strides[2] != 4 \
+                or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0:
+            raise ValueError("out must be a float32 host array of the input's shape with a contiguous last axis")
+        if n:
+            ctx._check(ctx._lib.wass_spatial_filter_apply(h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, n,
+                                                          out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4))
+        return out
+
+    def apply(self, surface):
+        """One rows x cols surface, as the reference's apply."""
+        if len(surface.shape) != 2:
+            raise ValueError("a 2-D surface is expected")
+        return self.apply_batch(surface[None])[0]
+
+
+def spatial_lowpass_filter(H: int, W: int, du: float, cutoff_in_hz: float = 1.0, order: int = 4, ctx: Context | None = None,
+                           batch: int = 16) -> Spatial2DButterworth:
+    """The filter wasspost spatial_lowpass builds for an H x W grid: the cutoff is the deep-water wavenumber of cutoff_in_hz,
+    2 pi f^2 / 9.81, taken in cycles per metre as the reference does."""
+    return Spatial2DButterworth(int(H), int(W), du, 2.0 * np.pi * cutoff_in_hz ** 2 / 9.81, order, ctx=ctx, batch=batch)
+
+
+def spatial_lowpass(data, du: float, cutoff_in_hz: float = 1.0, order: int = 4, ctx: Context | None = None, out=None, batch: int = 16):
+    """wasspost spatial_lowpass as a function: every frame of the count x H x W cube through spatial_lowpass_filter."""
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    filt = spatial_lowpass_filter(data.shape[1], data.shape[2], du, cutoff_in_hz, order, ctx=ctx, batch=batch)
+    try:
+        return filt.apply_batch(data, out=out)
+    finally:
+        filt.close()
