@@ -662,6 +662,37 @@ int wass_spatial_filter_apply_dev(wass_spatial_filter* h, const float* d_frames,
                                   float* d_out, size_t out_stride_t, size_t out_stride_y);
 void wass_spatial_filter_destroy(wass_spatial_filter* h);
 
+/* ---- Visibility map of the gridded cube: wasspost visibilitymap (wasspost.py:495-621, geometry.py:5-100) as an array function.
+ * For every frame of a count x H x W float32 cube (cell (t, y, x) at in[t * stride_t + y * stride_y + x], strides in elements) and
+ * every cell: zf = in * (float)datascale is the height in metres; the unit ray d from (XX, YY, zf) to the camera `origin` (grid
+ * coordinates; XX, YY are H x W doubles with XX[0][1] > XX[0][0] and YY[1][0] > YY[0][0], H, W >= 2); the surface normal from
+ * np.gradient(zf, dy, dx) as numpy computes it for a float32 array; angles = (float) degrees(acos(n . d)); mask = 1 where the
+ * ray, marched one cell of its dominant axis per step over zf / dx with rounding half to even, meets a cell at least as high
+ * as itself before it leaves the grid or rises above the frame's maximum, or where the angle is >= angle_limit (a negative or
+ * infinite angle_limit switches that rule off).  The ray, the step and the accumulated position are fp64 in numpy's order of
+ * operations: the march is the reference's bit for bit.  NaN cells never occlude, have mask 0 and a NaN angle; a cell exactly
+ * under the camera has mask 0 from the march; finite cells at or above the camera keep mask 0 and are counted in *not_upward
+ * (the reference asserts there).  mask and angles are count x H x W, tightly packed; occluded[t] = the number of mask cells of
+ * frame t (may be NULL, as may not_upward).  Frames are processed `batch` at a time (0: 8), halved until the scratch fits
+ * 16 GiB; wass_visibility_scratch_bytes says how much and which batch, without a GPU.  The result does not depend on the batch
+ * and is the same bits on every run.  wass_visibility: everything on the host, returns with the outputs filled.
+ * wass_visibility_dev: in, XX, YY, mask and angles are device memory (origin, occluded, not_upward stay host memory); the work is
+ * enqueued on the context's stream, and the call returns after a synchronisation, when it frees its scratch. */
+int wass_visibility_scratch_bytes(int count, int H, int W, int batch, int host, size_t* bytes, int* batch_used);
+int wass_visibility(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride_y, int count, int H, int W, const double* XX,
+                    const double* YY, const double origin[3], double datascale, double angle_limit, int batch, uint8_t* mask,
+                    float* angles, uint64_t* occluded, uint64_t* not_upward);
+int wass_visibility_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, const double* d_XX,
+                        const double* d_YY, const double origin[3], double datascale, double angle_limit, int batch, uint8_t* d_mask,
+                        float* d_angles, uint64_t* occluded, uint64_t* not_upward);
+/* compute_occlusion_mask (geometry.py:21-100) in its general form: one H x W fp64 surface in cell units and an H x W x 3 fp64 ray
+ * field; the step of a cell is its ray divided by max(|ray0|, |ray1|), its y component negated if invert_y_axis.  Cells whose
+ * ray does not have ray2 > 0 keep mask 0 and are counted in *not_upward.  _dev: ZZ, rays and mask are device memory. */
+int wass_occlusion_rays(wass_ctx* ctx, const double* ZZ, const double* rays, int H, int W, int invert_y_axis, uint8_t* mask,
+                        uint64_t* not_upward);
+int wass_occlusion_rays_dev(wass_ctx* ctx, const double* d_ZZ, const double* d_rays, int H, int W, int invert_y_axis, uint8_t* d_mask,
+                            uint64_t* not_upward);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

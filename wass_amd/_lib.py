@@ -213,6 +213,11 @@ SYMBOLS = {
     "wass_spatial_filter_apply": (_i, [_vp, _vp, _sz, _sz, _i, _vp, _sz, _sz]),
     "wass_spatial_filter_apply_dev": (_i, [_vp, _vp, _sz, _sz, _i, _vp, _sz, _sz]),
     "wass_spatial_filter_destroy": (None, [_vp]),
+    "wass_visibility_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_visibility": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
+    "wass_visibility_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
+    "wass_occlusion_rays": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "wass_occlusion_rays_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

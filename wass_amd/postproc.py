@@ -512,3 +512,150 @@ def spatial_lowpass(data, du: float, cutoff_in_hz: float = 1.0, order: int = 4, 
         return filt.apply_batch(data, out=out)
     finally:
         filt.close()
+
+
+# ---- visibility map of the cube: wasspost visibilitymap (wasspost.py:495-621) and geometry.py -----------------------------------
+def _gradient_line(f: np.ndarray, d, axis: int) -> np.ndarray:
+    """np.gradient(f, d, axis=axis) with edge_order 1, restated: interior (f[k+1] - f[k-1]) / (2 d), edges (f[1] - f[0]) / d.  As
+    numpy does, a float32 `f` gives float32: the differences are taken in float32 and the quotients, formed in fp64, are
+    rounded to float32 (the explicit casts keep this independent of numpy's promotion rules)."""
+    f = np.moveaxis(f, axis, 0)
+    wide = np.float64
+    out = np.empty(f.shape, f.dtype)
+    d = wide(d)
+    out[1:-1] = (f[2:] - f[:-2]).astype(wide) / (wide(2.0) * d)
+    out[0] = (f[1] - f[0]).astype(wide) / d
+    out[-1] = (f[-1] - f[-2]).astype(wide) / d
+    return np.moveaxis(out, 0, axis)
+
+
+def compute_slope_and_normals(XX, YY, ZZ):
+    """geometry.py's function on the host: (slope [H, W, 2] = (d/dx, d/dy), unit normals [H, W, 3] = (-sx, -sy, 1) / |.|).  A
+    float32 ZZ gives float32 slopes, as np.gradient does; the normals are float64."""
+    XX, YY, ZZ = np.asarray(XX), np.asarray(YY), np.asarray(ZZ)
+    if ZZ.ndim != 2 or XX.shape != ZZ.shape or YY.shape != ZZ.shape:
+        raise ValueError("XX, YY and ZZ must be H x W")
+    if ZZ.shape[0] < 2 or ZZ.shape[1] < 2:
+        raise ValueError("H and W must be at least 2")
+    if not np.issubdtype(ZZ.dtype, np.floating):
+        ZZ = ZZ.astype(np.float64)
+    dx = XX[0, 1] - XX[0, 0]
+    dy = YY[1, 0] - YY[0, 0]
+    if not (dx > 0.0 and dy > 0.0):
+        raise ValueError("dx and dy must be positive")
+    slope_y, slope_x = _gradient_line(ZZ, dy, 0), _gradient_line(ZZ, dx, 1)
+    slope = np.dstack((slope_x[:, :, None], slope_y[:, :, None]))
+    normals = np.dstack((slope_x[:, :, None], slope_y[:, :, None], -np.ones((ZZ.shape[0], ZZ.shape[1], 1))))
+    normals = -normals / np.sqrt(np.add.reduce(normals * normals, axis=-1, keepdims=True))
+    return slope, normals
+
+
+def visibility_scratch_bytes(count: int, H: int, W: int, batch: int = 8, host: bool = True):
+    """(bytes of device scratch, frames per launch) of one visibility_map call; no GPU needed."""
+    from . import _lib
+    b, n = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_visibility_scratch_bytes(int(count), int(H), int(W), int(batch), int(bool(host)), C.byref(b), C.byref(n))
+    if rc:
+        raise ValueError(f"wass_visibility_scratch_bytes({count}, {H}, {W}, batch {batch}): error {rc}")
+    return b.value, n.value
+
+
+def _check_grid(XX, YY, H: int, W: int):
+    XX, YY = np.ascontiguousarray(XX, np.float64), np.ascontiguousarray(YY, np.float64)
+    if H < 2 or W < 2:
+        raise ValueError("H and W must be at least 2")
+    if XX.shape != (H, W) or YY.shape != (H, W):
+        raise ValueError(f"XX and YY must be {H} x {W}, like a frame")
+    dx, dy = XX[0, 1] - XX[0, 0], YY[1, 0] - YY[0, 0]
+    if not (dx > 0.0 and dy > 0.0):
+        raise ValueError("dx and dy must be positive")
+    if not np.allclose(dx, dy):
+        raise ValueError("grid cells must be square")
+    return XX, YY
+
+
+def visibility_map(data, XX, YY, cam_to_grid, datascale: float = 1e-3, angle_limit: float = 88.0, ctx: Context | None = None,
+                   out_occlusion=None, out_angles=None, batch: int = 8):
+    """wasspost visibilitymap as a function: (occlusion uint8 [count, H, W], incident_angles float32 [count, H, W] in degrees,
+    occluded_percent float64 [count]).  `data` is the count x H x W float32 cube in the unit that `datascale` turns into metres: a
+    host array or memmap (host results) or a device tensor (device results); XX, YY are the H x W grid coordinates in metres,
+    cam_to_grid the 4 x 4 Cam{n}toGrid matrix, whose last column is the camera.  A cell is occluded if its ray to the camera
+    meets the surface, or if its incident angle is at least angle_limit (None, a negative or an infinite value: no such rule).
+    The march is the reference's bit for bit; where the reference is undefined: NaN cells never occlude and have mask 0 and a
+    NaN angle, a cell exactly under the camera is not occluded, and a finite cell at or above the camera raises ValueError."""
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W = (int(v) for v in data.shape)
+    if count < 1:
+        raise ValueError("no frames")
+    XX, YY = _check_grid(XX, YY, H, W)
+    cam = np.asarray(cam_to_grid, np.float64)
+    if cam.shape != (4, 4):
+        raise ValueError("cam_to_grid must be 4 x 4")
+    origin = np.ascontiguousarray(cam[:3, -1])
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    limit = -1.0 if angle_limit is None else float(angle_limit)
+    if ctx is None:
+        ctx = Context(0)
+    counts = np.zeros(count, np.uint64)
+    up = C.c_uint64()
+    tail = (origin.ctypes.data, float(datascale), limit, int(batch))
+    if _is_device(data):
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+        outs = []
+        for o, dt in ((out_occlusion, torch.uint8), (out_angles, torch.float32)):
+            if o is None:
+                o = torch.empty((count, H, W), dtype=dt, device=data.device)
+            elif not _is_device(o) or tuple(o.shape) != (count, H, W) or o.dtype != dt or not o.is_contiguous():
+                raise ValueError("the outputs must be contiguous device tensors of the input's shape, uint8 and float32")
+            outs.append(o)
+        dXX, dYY = torch.from_numpy(XX).to(data.device), torch.from_numpy(YY).to(data.device)
+        torch.cuda.current_stream(data.device).synchronize()
+        ctx._check(ctx._lib.wass_visibility_dev(ctx._h, data.data_ptr(), data.stride(0), data.stride(1), count, H, W, dXX.data_ptr(),
+                                                dYY.data_ptr(), *tail, outs[0].data_ptr(), outs[1].data_ptr(), counts.ctypes.data, C.byref(up)))
+    else:
+        src = _host_f32_rows(data)
+        outs = []
+        for o, dt in ((out_occlusion, np.uint8), (out_angles, np.float32)):
+            if o is None:
+                o = np.empty((count, H, W), dt)
+            elif not isinstance(o, np.ndarray) or o.shape != (count, H, W) or o.dtype != dt or not o.flags.c_contiguous:
+                raise ValueError("the outputs must be contiguous host arrays of the input's shape, uint8 and float32")
+            outs.append(o)
+        ctx._check(ctx._lib.wass_visibility(ctx._h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W, XX.ctypes.data,
+                                            YY.ctypes.data, *tail, outs[0].ctypes.data, outs[1].ctypes.data, counts.ctypes.data, C.byref(up)))
+    if up.value:
+        raise ValueError(f"rays must go upward: {up.value} cells lie at or above the camera")
+    return outs[0], outs[1], 100.0 * counts.astype(np.float64) / float(H * W)
+
+
+def compute_occlusion_mask(ZZ, ray_d, invert_y_axis: bool = False, ctx: Context | None = None):
+    """geometry.py's compute_occlusion_mask on the GPU: ZZ is an H x W surface in cell units, ray_d the H x W x 3 ray of every cell
+    (ray_d[..., 2] > 0); the uint8 mask is 1 where the cell's ray, marched one cell of its dominant axis per step, meets the
+    surface.  Host arrays give a host mask, device tensors a device mask.  The reference's assertions raise ValueError."""
+    if len(ZZ.shape) != 2 or tuple(ray_d.shape) != (int(ZZ.shape[0]), int(ZZ.shape[1]), 3):
+        raise ValueError("ray_d must be H x W x 3 for an H x W surface")
+    H, W = (int(v) for v in ZZ.shape)
+    if H < 1 or W < 1:
+        raise ValueError("empty surface")
+    if ctx is None:
+        ctx = Context(0)
+    up = C.c_uint64()
+    if _is_device(ZZ):
+        import torch
+        if not _is_device(ray_d):
+            raise ValueError("ZZ and ray_d must be on the same side")
+        z, r = ZZ.to(torch.float64).contiguous(), ray_d.to(torch.float64).contiguous()
+        mask = torch.empty((H, W), dtype=torch.uint8, device=z.device)
+        torch.cuda.current_stream(z.device).synchronize()
+        ctx._check(ctx._lib.wass_occlusion_rays_dev(ctx._h, z.data_ptr(), r.data_ptr(), H, W, int(bool(invert_y_axis)), mask.data_ptr(), C.byref(up)))
+    else:
+        z, r = np.ascontiguousarray(ZZ, np.float64), np.ascontiguousarray(ray_d, np.float64)
+        mask = np.empty((H, W), np.uint8)
+        ctx._check(ctx._lib.wass_occlusion_rays(ctx._h, z.ctypes.data, r.ctypes.data, H, W, int(bool(invert_y_axis)), mask.ctypes.data, C.byref(up)))
+    if up.value:
+        raise ValueError("rays must go upward")
+    return mask
