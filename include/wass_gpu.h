@@ -693,6 +693,72 @@ int wass_occlusion_rays(wass_ctx* ctx, const double* ZZ, const double* rays, int
 int wass_occlusion_rays_dev(wass_ctx* ctx, const double* d_ZZ, const double* d_rays, int H, int W, int invert_y_axis, uint8_t* d_mask,
                             uint64_t* not_upward);
 
+/* ---- Radiance of the gridded cube: wasspost radiance (wasspost.py:813-919), bgimage (:1010-1074) and radiance_threshold
+ * (:1079-1145) as array functions.
+ *
+ * wass_remap_lanczos4: cv::remap(src, dst, map_x, map_y, INTER_LANCZOS4) for CV_8UC1 / CV_32FC1 maps, BORDER_CONSTANT 0:
+ * X = cvRound(map_x * 32) (float product, nearest even), the window of 8 x 8 taps starts at (X >> 5) - 3 (saturated to int16
+ * first), the 64 int16 weights of phase (Y & 31) * 32 + (X & 31) from OpenCV's fixed-point table (wass_lanczos4_table writes
+ * its 1024 x 8 x 8 entries; no GPU needed), int32 sum, (v + 2^14) >> 15 clamped to 0 .. 255; taps outside the picture count 0.
+ * A map value that is NaN, infinite or whose product with 32 leaves the int32 range gives 0.  The sides of the picture are
+ * below 32767.  Written from knowledge of OpenCV 4.5.5 and not pinned against it.  dst and the maps are dw x dh, tightly packed.
+ *
+ * wass_radiance: out[t][y][x] = remap(images[t]) / 255 (float32) at mapx = (float)(r_0 / r_2), mapy = (float)(r_1 / r_2) with
+ * r_k = ((P[k][0] XX + P[k][1] YY) + P[k][2] zf) + P[k][3] in fp64 and zf = in * (float)datascale in float32; Pcam is the 3 x 4
+ * row-major projection into picture pixels.  images: count pictures of Ih x Iw bytes, picture t at images + t * image_stride_t,
+ * rows image_stride_y apart; the cube as for wass_visibility; out is count x H x W, tightly packed.  Frames go `batch` at a
+ * time (0: 8).  The device form needs no scratch and only enqueues on the context's stream; the host form stages XX, YY and
+ * the frames of a batch (wass_radiance_scratch_bytes says how much, without a GPU) and returns with out filled.
+ *
+ * wass_bgimage: scipy.ndimage.uniform_filter1d(in, size, axis=0, mode='reflect') of the float32 cube, bit for bit as scipy 1.15
+ * computes it: the window at t covers t - size / 2 .. t + size - size / 2 - 1, indices reflected half-sample symmetric as often
+ * as needed, the sum of the first window in fp64, then sum += in[new] - in[old], out[t] = (float)(sum / size).  A NaN poisons
+ * its series from the first window that holds it to the end.  out must not be in.  The host form works in slabs of rows
+ * (slab_rows > 0 caps them; the result does not depend on it) under 16 GiB of scratch; the device form needs none.
+ *
+ * The threshold, per frame and in float32: m = min(Ibg) (NaN if Ibg holds one), Isub = I - (Ibg - m).
+ *   wass_radiance_range  bgmin[t] = m, lo[t] / hi[t] = the smallest / largest finite Isub (NaN if there is none),
+ *                        nonfinite[t] = the cells of Isub that are NaN or infinite
+ *   wass_radiance_hist   counts[t][30] = the histogram of Isub against edges[t][31] as np.histogram counts: the left edge
+ *                        inclusive, the last bin closed, the edges themselves deciding; values outside are not counted
+ *   wass_radiance_mask   mask[t][y][x] = Isub > thr[t]
+ * bgmin, lo, hi, nonfinite, edges, counts and thr are host memory in both forms; I, Ibg (element strides as for the cube) and
+ * mask (count x H x W, tightly packed) are host memory or, in the _dev forms, device memory.  Every call returns after a
+ * synchronisation.  Integer atomics only: the same input gives the same bits. */
+int wass_lanczos4_table(int16_t* out /* 1024 * 64 */);
+int wass_remap_lanczos4(wass_ctx* ctx, const uint8_t* src, int sw, int sh, size_t src_stride, const float* map_x, const float* map_y,
+                        int dw, int dh, uint8_t* dst);
+int wass_remap_lanczos4_dev(wass_ctx* ctx, const uint8_t* d_src, int sw, int sh, size_t src_stride, const float* d_map_x,
+                            const float* d_map_y, int dw, int dh, uint8_t* d_dst);
+int wass_radiance_scratch_bytes(int count, int H, int W, int Ih, int Iw, int batch, int host, size_t* bytes, int* batch_used);
+int wass_radiance(wass_ctx* ctx, const uint8_t* images, size_t image_stride_t, size_t image_stride_y, int Ih, int Iw, const float* in,
+                  size_t stride_t, size_t stride_y, int count, int H, int W, const double* XX, const double* YY, const double Pcam[12],
+                  double datascale, int batch, float* out);
+int wass_radiance_dev(wass_ctx* ctx, const uint8_t* d_images, size_t image_stride_t, size_t image_stride_y, int Ih, int Iw,
+                      const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, const double* d_XX,
+                      const double* d_YY, const double Pcam[12], double datascale, int batch, float* d_out);
+int wass_bgimage_scratch_bytes(int count, int H, int W, int size, int slab_rows, int host, size_t* bytes, int* rows_per_slab);
+int wass_bgimage(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride_y, int count, int H, int W, int size, int slab_rows,
+                 float* out, size_t out_stride_t, size_t out_stride_y);
+int wass_bgimage_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, int size,
+                     int slab_rows, float* d_out, size_t out_stride_t, size_t out_stride_y);
+int wass_radiance_threshold_scratch_bytes(int count, int H, int W, int batch, int host, size_t* bytes, int* batch_used);
+int wass_radiance_range(wass_ctx* ctx, const float* I, size_t stride_t, size_t stride_y, const float* Ibg, size_t bg_stride_t,
+                        size_t bg_stride_y, int count, int H, int W, int batch, float* bgmin, float* lo, float* hi, uint32_t* nonfinite);
+int wass_radiance_range_dev(wass_ctx* ctx, const float* d_I, size_t stride_t, size_t stride_y, const float* d_Ibg, size_t bg_stride_t,
+                            size_t bg_stride_y, int count, int H, int W, int batch, float* bgmin, float* lo, float* hi,
+                            uint32_t* nonfinite);
+int wass_radiance_hist(wass_ctx* ctx, const float* I, size_t stride_t, size_t stride_y, const float* Ibg, size_t bg_stride_t,
+                       size_t bg_stride_y, int count, int H, int W, int batch, const float* bgmin, const float* edges, uint32_t* counts);
+int wass_radiance_hist_dev(wass_ctx* ctx, const float* d_I, size_t stride_t, size_t stride_y, const float* d_Ibg, size_t bg_stride_t,
+                           size_t bg_stride_y, int count, int H, int W, int batch, const float* bgmin, const float* edges,
+                           uint32_t* counts);
+int wass_radiance_mask(wass_ctx* ctx, const float* I, size_t stride_t, size_t stride_y, const float* Ibg, size_t bg_stride_t,
+                       size_t bg_stride_y, int count, int H, int W, int batch, const float* bgmin, const float* thr, uint8_t* mask);
+int wass_radiance_mask_dev(wass_ctx* ctx, const float* d_I, size_t stride_t, size_t stride_y, const float* d_Ibg, size_t bg_stride_t,
+                           size_t bg_stride_y, int count, int H, int W, int batch, const float* bgmin, const float* thr,
+                           uint8_t* d_mask);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

@@ -218,6 +218,22 @@ SYMBOLS = {
     "wass_visibility_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "wass_occlusion_rays": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "wass_occlusion_rays_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "wass_lanczos4_table": (_i, [_vp]),
+    "wass_remap_lanczos4": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _i, _i, _vp]),
+    "wass_remap_lanczos4_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _i, _i, _vp]),
+    "wass_radiance_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_radiance": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, _i, _vp]),
+    "wass_radiance_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, _i, _vp]),
+    "wass_bgimage_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_bgimage": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_bgimage_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_radiance_threshold_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_radiance_range": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "wass_radiance_range_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "wass_radiance_hist": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wass_radiance_hist_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wass_radiance_mask": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wass_radiance_mask_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

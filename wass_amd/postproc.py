@@ -659,3 +659,328 @@ def compute_occlusion_mask(ZZ, ray_d, invert_y_axis: bool = False, ctx: Context 
     if up.value:
         raise ValueError("rays must go upward")
     return mask
+
+
+# ---- radiance of the cube: wasspost radiance (wasspost.py:813-919), bgimage (:1010-1074), radiance_threshold (:1079-1145) --------
+def lanczos4_table() -> np.ndarray:
+    """The fixed-point table of the Lanczos4 sampler, int16 [32, 32, 8, 8] = [fy, fx, ky, kx] (OpenCV's initInterTab2D, restated);
+    no GPU needed."""
+    from . import _lib
+    tab = np.empty((32, 32, 8, 8), np.int16)
+    rc = _lib.load().wass_lanczos4_table(tab.ctypes.data)
+    if rc:
+        raise ValueError(f"wass_lanczos4_table: error {rc}")
+    return tab
+
+
+def _check_picture(shape):
+    if len(shape) != 2 or not (1 <= int(shape[0]) < 32767 and 1 <= int(shape[1]) < 32767):
+        raise ValueError("a picture is Ih x Iw uint8 with sides from 1 to 32766")
+
+
+def remap_lanczos4(image, mapx, mapy, ctx: Context | None = None):
+    """cv.remap(image, mapx, mapy, cv.INTER_LANCZOS4) for a uint8 picture and float32 maps, constant border 0, in OpenCV's own
+    fixed-point arithmetic (1/32 pixel phases, int16 weights scaled by 2^15).  Host arrays give a host result, device tensors a
+    device tensor.  Where OpenCV is undefined -- a map value that is NaN, infinite or beyond +-2^26 -- the result is 0."""
+    _check_picture(image.shape)
+    if len(mapx.shape) != 2 or tuple(mapx.shape) != tuple(mapy.shape) or min(int(v) for v in mapx.shape) < 1:
+        raise ValueError("mapx and mapy must be two h x w maps of one shape")
+    sh, sw = (int(v) for v in image.shape)
+    dh, dw = (int(v) for v in mapx.shape)
+    if ctx is None:
+        ctx = Context(0)
+    if _is_device(image):
+        import torch
+        if not (_is_device(mapx) and _is_device(mapy)):
+            raise ValueError("the picture and the maps must be on the same side")
+        src = image.to(torch.uint8).contiguous()
+        mx, my = mapx.to(torch.float32).contiguous(), mapy.to(torch.float32).contiguous()
+        dst = torch.empty((dh, dw), dtype=torch.uint8, device=src.device)
+        torch.cuda.current_stream(src.device).synchronize()
+        ctx._check(ctx._lib.wass_remap_lanczos4_dev(ctx._h, src.data_ptr(), sw, sh, sw, mx.data_ptr(), my.data_ptr(), dw, dh, dst.data_ptr()))
+        ctx.synchronize()
+        return dst
+    src = np.ascontiguousarray(image, np.uint8)
+    mx, my = np.ascontiguousarray(mapx, np.float32), np.ascontiguousarray(mapy, np.float32)
+    dst = np.empty((dh, dw), np.uint8)
+    ctx._check(ctx._lib.wass_remap_lanczos4(ctx._h, src.ctypes.data, sw, sh, sw, mx.ctypes.data, my.ctypes.data, dw, dh, dst.ctypes.data))
+    return dst
+
+
+def radiance_pcam(Pplane, Iw: int, Ih: int) -> np.ndarray:
+    """The 4 x 4 projection from grid coordinates into pixels of an Iw x Ih picture: inv(toNorm) @ P{cam}plane, where toNorm
+    takes pixels to the square [-1, 1]^2 (x * 2 / Iw - 1, y * 2 / Ih - 1).  numpy's inv and matmul, as the reference uses them."""
+    Pplane = np.asarray(Pplane, np.float64)
+    if Pplane.shape != (4, 4):
+        raise ValueError("Pplane must be 4 x 4")
+    to_norm = np.eye(4)
+    to_norm[0, 0], to_norm[0, 2] = 2.0 / Iw, -1
+    to_norm[1, 1], to_norm[1, 2] = 2.0 / Ih, -1
+    return np.linalg.inv(to_norm) @ Pplane
+
+
+def workspace_images(wassdir: str, cam: int, count: int):
+    """Yields the undistorted pictures of camera `cam` of a WASS output directory, frame by frame, as grey uint8 arrays:
+    <wassdir>/%06d_wd/undistorted/%08d.png."""
+    import os
+    from PIL import Image
+    for idx in range(int(count)):
+        with Image.open(os.path.join(wassdir, "%06d_wd" % idx, "undistorted", "%08d.png" % int(cam))) as im:
+            yield np.asarray(im.convert("L"), np.uint8)
+
+
+def radiance_scratch_bytes(count: int, H: int, W: int, Ih: int, Iw: int, batch: int = 8, host: bool = True):
+    """(bytes of device scratch, frames per launch) of one radiance call; no GPU needed."""
+    from . import _lib
+    b, n = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_radiance_scratch_bytes(int(count), int(H), int(W), int(Ih), int(Iw), int(batch), int(bool(host)), C.byref(b), C.byref(n))
+    if rc:
+        raise ValueError(f"wass_radiance_scratch_bytes({count}, {H}, {W}, pictures {Ih} x {Iw}, batch {batch}): error {rc}")
+    return b.value, n.value
+
+
+def _radiance_chunk(ctx, imgs, data, XX, YY, dgrid, pcam, datascale, batch, out):
+    """frames of one picture size: imgs n x Ih x Iw (host array or device tensor), data and out n x H x W on the cube's side"""
+    n, H, W = (int(v) for v in data.shape)
+    Ih, Iw = int(imgs.shape[1]), int(imgs.shape[2])
+    P = np.ascontiguousarray(pcam[:3], np.float64)
+    if _is_device(data):
+        import torch
+        if not _is_device(imgs):
+            imgs = torch.from_numpy(np.ascontiguousarray(imgs, np.uint8)).to(data.device)
+        imgs = imgs.to(torch.uint8).contiguous()
+        torch.cuda.current_stream(data.device).synchronize()
+        ctx._check(ctx._lib.wass_radiance_dev(ctx._h, imgs.data_ptr(), Ih * Iw, Iw, Ih, Iw, data.data_ptr(), data.stride(0), data.stride(1), n, H, W,
+                                              dgrid[0].data_ptr(), dgrid[1].data_ptr(), P.ctypes.data, float(datascale), int(batch), out.data_ptr()))
+        ctx.synchronize()
+        return
+    if _is_device(imgs):
+        imgs = imgs.cpu().numpy()
+    imgs = np.ascontiguousarray(imgs, np.uint8)
+    ctx._check(ctx._lib.wass_radiance(ctx._h, imgs.ctypes.data, Ih * Iw, Iw, Ih, Iw, data.ctypes.data, data.strides[0] // 4, data.strides[1] // 4, n, H, W,
+                                      XX.ctypes.data, YY.ctypes.data, P.ctypes.data, float(datascale), int(batch), out.ctypes.data))
+
+
+def radiance(images, data, XX, YY, Pplane, datascale: float = 1e-3, upscalefactor: int = 1, ctx: Context | None = None, out=None,
+             batch: int = 8):
+    """wasspost radiance as a function: float32 [count, H, W], the camera picture sampled at every cell of every frame and divided
+    by 255.  `images` is a count x Ih x Iw uint8 array or tensor, or an iterable of Ih x Iw frames (workspace_images); `data` the
+    count x H x W float32 cube in the unit that `datascale` turns into metres, a host array or memmap (host result) or a device
+    tensor (device result); XX, YY the H x W grid in metres; Pplane the 4 x 4 P{cam}plane matrix.  Per cell the height is
+    data * float32(datascale) in float32, the projection ((P0 X + P1 Y) + P2 z) + P3 per row in fp64, the maps its quotients cast
+    to float32, and the sampler remap_lanczos4.  Cells whose height is NaN, or that project outside the picture, are 0."""
+    if int(upscalefactor) != 1:
+        raise NotImplementedError("upscalefactor other than 1 needs cv.pyrUp, which is not implemented")
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W = (int(v) for v in data.shape)
+    if count < 1 or H < 1 or W < 1:
+        raise ValueError("no frames")
+    XX, YY = np.ascontiguousarray(XX, np.float64), np.ascontiguousarray(YY, np.float64)
+    if XX.shape != (H, W) or YY.shape != (H, W):
+        raise ValueError(f"XX and YY must be {H} x {W}, like a frame")
+    if np.asarray(Pplane).shape != (4, 4):
+        raise ValueError("Pplane must be 4 x 4")
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    whole = hasattr(images, "shape") and len(images.shape) == 3
+    if whole:
+        if int(images.shape[0]) != count:
+            raise ValueError(f"{int(images.shape[0])} pictures for {count} frames")
+        _check_picture(images.shape[1:])
+    if ctx is None:
+        ctx = Context(0)
+    dgrid = None
+    if _is_device(data):
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+        if out is None:
+            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
+        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 device tensor of the input's shape")
+        dgrid = (torch.from_numpy(XX).to(data.device), torch.from_numpy(YY).to(data.device))
+    else:
+        data = _host_f32_rows(data)
+        if out is None:
+            out = np.empty((count, H, W), np.float32)
+        elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous float32 host array of the input's shape")
+    if whole:
+        pcam = radiance_pcam(Pplane, int(images.shape[2]), int(images.shape[1]))
+        _radiance_chunk(ctx, images, data, XX, YY, dgrid, pcam, datascale, batch, out)
+        return out
+    t0, pending = 0, []
+
+    def flush():
+        nonlocal t0, pending
+        if pending:
+            stack = np.stack(pending)
+            pcam = radiance_pcam(Pplane, stack.shape[2], stack.shape[1])
+            _radiance_chunk(ctx, stack, data[t0:t0 + len(pending)], XX, YY, dgrid, pcam, datascale, batch, out[t0:t0 + len(pending)])
+            t0 += len(pending)
+            pending = []
+
+    for frame in images:
+        frame = frame.cpu().numpy() if _is_device(frame) else np.asarray(frame)
+        _check_picture(frame.shape)
+        if t0 + len(pending) >= count:
+            raise ValueError(f"more than {count} pictures")
+        if pending and pending[0].shape != frame.shape:
+            flush()                                     # the projection depends on the picture's size
+        pending.append(np.ascontiguousarray(frame, np.uint8))
+        if len(pending) == int(batch):
+            flush()
+    flush()
+    if t0 != count:
+        raise ValueError(f"{t0} pictures for {count} frames")
+    return out
+
+
+def bgimage_scratch_bytes(count: int, H: int, W: int, filtersize: int = 2000, slab_rows: int = 0, host: bool = True):
+    """(bytes of device scratch, rows per slab) of one bgimage call; no GPU needed."""
+    from . import _lib
+    b, r = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_bgimage_scratch_bytes(int(count), int(H), int(W), int(filtersize), int(slab_rows), int(bool(host)), C.byref(b), C.byref(r))
+    if rc:
+        raise ValueError(f"wass_bgimage_scratch_bytes({count}, {H}, {W}, size {filtersize}): error {rc}")
+    return b.value, r.value
+
+
+def bgimage(data, filtersize: int = 2000, ctx: Context | None = None, out=None, slab_rows: int = 0):
+    """wasspost bgimage as a function: scipy.ndimage.uniform_filter1d(data, filtersize, axis=0, mode='reflect') of the count x H x W
+    float32 cube, bit for bit (the whole series in one run: no chunks, so no restart of the running sum).  A host array or memmap
+    gives a host array, a device tensor a device tensor; `out` must not be `data`.  slab_rows > 0 caps the rows filtered at a
+    time (the result does not depend on it)."""
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W = (int(v) for v in data.shape)
+    if count < 1 or H < 1 or W < 1:
+        raise ValueError("empty cube")
+    if int(filtersize) < 1:
+        raise ValueError("filtersize must be at least 1")
+    if ctx is None:
+        ctx = Context(0)
+    if _is_device(data):
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+        if out is None:
+            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
+        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or out.stride(2) != 1 \
+                or out.data_ptr() == data.data_ptr():
+            raise ValueError("out must be another float32 device tensor of the input's shape with a contiguous last axis")
+        torch.cuda.current_stream(data.device).synchronize()
+        ctx._check(ctx._lib.wass_bgimage_dev(ctx._h, data.data_ptr(), data.stride(0), data.stride(1), count, H, W, int(filtersize), int(slab_rows),
+                                             out.data_ptr(), out.stride(0), out.stride(1)))
+        ctx.synchronize()
+        return out
+    src = _host_f32_rows(data)
+    if out is None:
+        out = np.empty((count, H, W), np.float32)
+    elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or out.strides[2] != 4 \
+            or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0 or np.shares_memory(out, src):
+        raise ValueError("out must be another float32 host array of the input's shape with a contiguous last axis")
+    ctx._check(ctx._lib.wass_bgimage(ctx._h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W, int(filtersize), int(slab_rows),
+                                     out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4))
+    return out
+
+
+VATS_BINS = 30
+
+
+def radiance_threshold_scratch_bytes(count: int, H: int, W: int, batch: int = 8, host: bool = True):
+    """(bytes of device scratch, frames per launch) of one pass of radiance_threshold; no GPU needed."""
+    from . import _lib
+    b, n = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_radiance_threshold_scratch_bytes(int(count), int(H), int(W), int(batch), int(bool(host)), C.byref(b), C.byref(n))
+    if rc:
+        raise ValueError(f"wass_radiance_threshold_scratch_bytes({count}, {H}, {W}, batch {batch}): error {rc}")
+    return b.value, n.value
+
+
+def vats_threshold(counts, bin_edges):
+    """The threshold wasspost derives from the histogram of a frame (density=True): among the bins from the peak on, the one
+    farthest from the straight line through the peak and the last bin, in (bin number, density) coordinates; its right edge."""
+    counts, bin_edges = np.asarray(counts), np.asarray(bin_edges)
+    density = counts / np.array(np.diff(bin_edges), float) / counts.sum()          # np.histogram's own expression
+    nbins = density.shape[0]
+    pts = np.vstack((np.arange(nbins), density, np.ones(nbins)))                    # homogeneous points, one per column
+    peak = int(np.argmax(density))
+    line = np.cross(pts[:, peak], pts[:, -1])
+    far = int(np.argmax(np.abs(line @ pts)[peak:])) + peak
+    return bin_edges[far + 1]
+
+
+def _threshold_sides(radiance, radiance_bg):
+    if len(radiance.shape) != 3 or tuple(radiance.shape) != tuple(radiance_bg.shape):
+        raise ValueError("radiance and radiance_bg must be two count x H x W cubes of one shape")
+    if min(int(v) for v in radiance.shape) < 1:
+        raise ValueError("empty cube")
+    if _is_device(radiance) != _is_device(radiance_bg):
+        raise ValueError("radiance and radiance_bg must be on the same side")
+    if _is_device(radiance):
+        import torch
+        both = []
+        for a in (radiance, radiance_bg):
+            if a.dtype != torch.float32 or a.stride(2) != 1 or a.stride(0) <= 0 or a.stride(1) <= 0:
+                a = a.to(torch.float32).contiguous()
+            both.append(a)
+        torch.cuda.current_stream(both[0].device).synchronize()
+        return both[0], both[1], "_dev", [v for a in both for v in (a.data_ptr(), a.stride(0), a.stride(1))]
+    a, b = _host_f32_rows(radiance), _host_f32_rows(radiance_bg)
+    return a, b, "", [v for x in (a, b) for v in (x.ctypes.data, x.strides[0] // 4, x.strides[1] // 4)]
+
+
+def radiance_histogram(radiance, radiance_bg, ctx: Context | None = None, batch: int = 8):
+    """What the VATS rule sees, per frame: (counts int64 [count, 30], bin_edges float32 [count, 31], min(Ibg) float32 [count]) of
+    Isub = I - (Ibg - min(Ibg)), equal to np.histogram(Isub, bins=30).  ValueError if Isub holds a value that is not finite."""
+    I, B, suffix, ptrs = _threshold_sides(radiance, radiance_bg)
+    count, H, W = (int(v) for v in I.shape)
+    if ctx is None:
+        ctx = Context(0)
+    lib = ctx._lib
+    m, lo, hi = (np.empty(count, np.float32) for _ in range(3))
+    bad = np.zeros(count, np.uint32)
+    ctx._check(getattr(lib, "wass_radiance_range" + suffix)(ctx._h, *ptrs, count, H, W, int(batch), m.ctypes.data, lo.ctypes.data, hi.ctypes.data,
+                                                           bad.ctypes.data))
+    if bad.any():
+        t = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"frame {t}: {int(bad[t])} cells of the background-subtracted radiance are not finite; the histogram has no range")
+    edges = np.stack([np.histogram_bin_edges(np.array([lo[t], hi[t]], np.float32), bins=VATS_BINS) for t in range(count)])
+    edges = np.ascontiguousarray(edges, np.float32)
+    counts = np.zeros((count, VATS_BINS), np.uint32)
+    ctx._check(getattr(lib, "wass_radiance_hist" + suffix)(ctx._h, *ptrs, count, H, W, int(batch), m.ctypes.data, edges.ctypes.data, counts.ctypes.data))
+    return counts.astype(np.int64), edges, m
+
+
+def radiance_threshold(radiance, radiance_bg, threshold_val: float = 0.35, use_vats: bool = False, ctx: Context | None = None, batch: int = 8):
+    """wasspost radiance_threshold as a function: (mask uint8 [count, H, W], thresholds float32 [count]).  Per frame, in float32,
+    Isub = I - (Ibg - min(Ibg)) and mask = Isub > threshold, the threshold being threshold_val or, with use_vats, the one
+    vats_threshold derives from the 30-bin histogram of Isub (counted on the device, equal to np.histogram's).  Host arrays or
+    memmaps give a host mask, device tensors a device mask; the thresholds are a host array.  With use_vats a frame with a value
+    that is not finite raises ValueError, as numpy's histogram does; without, such cells compare false."""
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    I, B, suffix, ptrs = _threshold_sides(radiance, radiance_bg)
+    count, H, W = (int(v) for v in I.shape)
+    if ctx is None:
+        ctx = Context(0)
+    lib = ctx._lib
+    if use_vats:
+        counts, edges, m = radiance_histogram(I, B, ctx=ctx, batch=batch)
+        thr = np.array([vats_threshold(counts[t], edges[t]) for t in range(count)], np.float32)
+    else:
+        m, lo, hi = (np.empty(count, np.float32) for _ in range(3))
+        bad = np.zeros(count, np.uint32)
+        ctx._check(getattr(lib, "wass_radiance_range" + suffix)(ctx._h, *ptrs, count, H, W, int(batch), m.ctypes.data, lo.ctypes.data,
+                                                               hi.ctypes.data, bad.ctypes.data))
+        thr = np.full(count, np.float32(threshold_val), np.float32)
+    if suffix:
+        import torch
+        mask = torch.empty((count, H, W), dtype=torch.uint8, device=I.device)
+        ctx._check(lib.wass_radiance_mask_dev(ctx._h, *ptrs, count, H, W, int(batch), m.ctypes.data, thr.ctypes.data, mask.data_ptr()))
+    else:
+        mask = np.empty((count, H, W), np.uint8)
+        ctx._check(lib.wass_radiance_mask(ctx._h, *ptrs, count, H, W, int(batch), m.ctypes.data, thr.ctypes.data, mask.ctypes.data))
+    return mask, thr
