@@ -759,6 +759,82 @@ int wass_radiance_mask_dev(wass_ctx* ctx, const float* d_I, size_t stride_t, siz
                            size_t bg_stride_y, int count, int H, int W, int batch, const float* bgmin, const float* thr,
                            uint8_t* d_mask);
 
+/* ---- Polarimetric set-up of the gridded cube: wasspost polarimetric_setup (wasspost.py:627-805), clip and zeromean as array
+ * functions.
+ *
+ * wass_remap_linear_f32: cv::remap(src, dst, map_x, map_y, INTER_LINEAR) for CV_32FC1 / CV_32FC1 maps, BORDER_CONSTANT 0:
+ * X = cvRound(map_x * 32) (float product, nearest even), the window of 2 x 2 taps at (X >> 5, Y >> 5) (saturated to int16), the
+ * four float32 weights of phase (Y & 31) * 32 + (X & 31) (wass_bilinear_table_f32 writes the 1024 x 2 x 2 table, w[ky][kx] =
+ * ty[ky] * tx[kx] with t = (1 - f / 32, f / 32); no GPU needed), ((v00 w00 + v01 w01) + v10 w10) + v11 w11 in float32 without
+ * contraction; each tap outside the picture counts 0, NaN and infinite samples propagate.  A map value that is NaN, infinite
+ * or whose product with 32 leaves the int32 range gives 0.  The sides of the picture are below 32767; src_stride is in
+ * elements.  Written from knowledge of OpenCV 4.5.5 and not pinned against it.  dst and the maps are dw x dh, tightly packed.
+ *
+ * wass_polarimetric: per frame t and cell, zf = in * (float)datascale, (u, v) = the projection of wass_radiance in fp64, the
+ * camera-frame ray q / |q| with q = ((Kinv[r][0] u + Kinv[r][1] v) + Kinv[r][2]), the mask and the incident angle of
+ * wass_visibility (origin, angle_limit: negative or infinite = no angle rule), the three pictures of stokes sampled with
+ * wass_remap_linear_f32 at ((float)u, (float)v) and set to NaN where the mask is 1, DOLP = sqrt(S1^2 + S2^2) / S0 in float32,
+ * the unit normal (-sx, -sy, 1) / |.| from the float32 slopes of np.gradient.  stokes: picture k of frame t at
+ * stokes + t * stokes_stride_t + k * stokes_stride_c, rows stokes_stride_y apart (elements); the cube as for wass_visibility.
+ * acc holds 8 * H * W doubles, [Savg H x W x 3 | Navg H x W x 3 | Zavg H x W | valid H x W]: the frames are ADDED to it in order,
+ * one fp64 addition per frame and value (nan_to_num(S), the normal, zf, 1 - mask), so the caller zeroes it before the first
+ * call and may split a sequence over calls.  With total_frames > 0 the call ends the sequence: Savg / valid, Navg / |Navg|,
+ * Zavg / total_frames, in place.  out (may be NULL) names the per-frame results wanted, each count frames, tightly packed; NULL
+ * members are not produced.  occluded[count] (may be NULL) and *not_upward as for wass_visibility; if *not_upward is not 0 the
+ * sequence is not ended.  Frames go `batch` at a time (0: 8).  The host form stages a batch (wass_polarimetric_scratch_bytes says
+ * how much, without a GPU; outputs = the WASS_POL_* bits of the results wanted); the device form needs scratch only for what
+ * the visibility map needs and for S, the mask and the angles where they are not wanted.  Both return after a synchronisation.
+ *
+ * wass_clip_cube: out = min(max(in, lo), hi) in float32, NaN kept; *vmin, *vmax = the range of the values of out that are not
+ * NaN (NaN if there are none).  wass_zeromean: per cell the fp64 sum of the frames in order, divided by count; out =
+ * (float)((double)in - mean).  out may be in.  Strides in elements; _dev: in and out are device memory. */
+#define WASS_POL_S 1
+#define WASS_POL_OCCLUSION 2
+#define WASS_POL_ANGLES 4
+#define WASS_POL_DOLP 8
+#define WASS_POL_NORMALS 16
+#define WASS_POL_RAYS_CAM 32
+typedef struct wass_pol_params {
+    double Pcam[12];        /* projection into picture pixels, row-major 3 x 4 */
+    double Kinv[9];         /* inverse of the camera's intrinsic matrix, row-major */
+    double origin[3];       /* the camera in grid coordinates */
+    double datascale;
+    double angle_limit;     /* degrees */
+    int batch;
+    int total_frames;       /* 0: the sequence goes on */
+} wass_pol_params;
+typedef struct wass_pol_out {
+    float* S;               /* [count][H][W][3] */
+    uint8_t* occlusion;     /* [count][H][W] */
+    float* angles;          /* [count][H][W] */
+    float* dolp;            /* [count][H][W] */
+    double* normals;        /* [count][H][W][3] */
+    double* rays_cam;       /* [count][3][H * W] */
+} wass_pol_out;
+int wass_bilinear_table_f32(float* out /* 1024 * 4 */);
+int wass_remap_linear_f32(wass_ctx* ctx, const float* src, int sw, int sh, size_t src_stride, const float* map_x, const float* map_y,
+                          int dw, int dh, float* dst);
+int wass_remap_linear_f32_dev(wass_ctx* ctx, const float* d_src, int sw, int sh, size_t src_stride, const float* d_map_x,
+                              const float* d_map_y, int dw, int dh, float* d_dst);
+int wass_polarimetric_scratch_bytes(int count, int H, int W, int Ih, int Iw, int batch, int host, int outputs, size_t* bytes,
+                                    int* batch_used);
+int wass_polarimetric(wass_ctx* ctx, const float* stokes, size_t stokes_stride_t, size_t stokes_stride_c, size_t stokes_stride_y, int Ih,
+                      int Iw, const float* in, size_t stride_t, size_t stride_y, int count, int H, int W, const double* XX,
+                      const double* YY, const wass_pol_params* params, double* acc, const wass_pol_out* out, uint64_t* occluded,
+                      uint64_t* not_upward);
+int wass_polarimetric_dev(wass_ctx* ctx, const float* d_stokes, size_t stokes_stride_t, size_t stokes_stride_c, size_t stokes_stride_y,
+                          int Ih, int Iw, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W,
+                          const double* d_XX, const double* d_YY, const wass_pol_params* params, double* d_acc,
+                          const wass_pol_out* out, uint64_t* occluded, uint64_t* not_upward);
+int wass_clip_cube(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride_y, int count, int H, int W, float lo, float hi,
+                   float* out, size_t out_stride_t, size_t out_stride_y, float* vmin, float* vmax);
+int wass_clip_cube_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, float lo, float hi,
+                       float* d_out, size_t out_stride_t, size_t out_stride_y, float* vmin, float* vmax);
+int wass_zeromean(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride_y, int count, int H, int W, float* out,
+                  size_t out_stride_t, size_t out_stride_y);
+int wass_zeromean_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, float* d_out,
+                      size_t out_stride_t, size_t out_stride_y);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

@@ -103,6 +103,17 @@ class PlaneResult(C.Structure):
                 ("kept_final", C.c_uint64)]
 
 
+class PolParams(C.Structure):
+    """wass_pol_params"""
+    _fields_ = [("Pcam", C.c_double * 12), ("Kinv", C.c_double * 9), ("origin", C.c_double * 3), ("datascale", C.c_double),
+                ("angle_limit", C.c_double), ("batch", C.c_int), ("total_frames", C.c_int)]
+
+
+class PolOut(C.Structure):
+    """wass_pol_out"""
+    _fields_ = [(n, C.c_void_p) for n in ("S", "occlusion", "angles", "dolp", "normals", "rays_cam")]
+
+
 def default_sgm_params(num_disp: int, ndirs: int = 5, min_disp: int = 1, win: int = 13, p1_mult: int = 2,
                        p2_mult: int = 64, disp_offset: int = 0) -> SgmParams:
     """Defaults of SURVEY.md Appendix C (wass_stereo.cpp:742-759)."""
@@ -234,6 +245,19 @@ SYMBOLS = {
     "wass_radiance_hist_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wass_radiance_mask": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wass_radiance_mask_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wass_bilinear_table_f32": (_i, [_vp]),
+    "wass_remap_linear_f32": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _i, _i, _vp]),
+    "wass_remap_linear_f32_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _i, _i, _vp]),
+    "wass_polarimetric_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_polarimetric": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, C.POINTER(PolParams), _vp,
+                               C.POINTER(PolOut), _vp, C.POINTER(C.c_uint64)]),
+    "wass_polarimetric_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, C.POINTER(PolParams), _vp,
+                                   C.POINTER(PolOut), _vp, C.POINTER(C.c_uint64)]),
+    "wass_clip_cube": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, C.c_float, C.c_float, _vp, _sz, _sz, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wass_clip_cube_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, C.c_float, C.c_float, _vp, _sz, _sz, C.POINTER(C.c_float),
+                                C.POINTER(C.c_float)]),
+    "wass_zeromean": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_zeromean_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _sz, _sz]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

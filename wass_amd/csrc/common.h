@@ -190,6 +190,8 @@ struct wass_ctx {
     wass::Buf rect_mx, rect_my;    // staging for host-pointer map uploads
     wass::Buf lanczos_tab;         // the 1024 x 8 x 8 fixed-point Lanczos4 table of the radiance sampler (radiance.hip)
     bool lanczos_tab_ready = false;
+    wass::Buf bilinear_tab;        // the 1024 x 2 x 2 float32 table of the bilinear sampler (polarimetric.hip)
+    bool bilinear_tab_ready = false;
     // cv::undistort's normalised coordinate tables depend on (K, w, h) only: kept per camera so that the per-frame call of a
     // sequence neither recomputes nor synchronises (wass_undistort_dev)
     struct UndCache { double K[9] = {}; int w = 0, h = 0; bool valid = false; wass::Buf xy; } und_cache[2];

@@ -18,6 +18,7 @@
 // own ray is dropped at once.  The loop is bounded by max(H, W) steps whatever the input.
 // The only atomics are integer ones (a maximum of order-preserving keys, counts): the same input gives the same bits.
 #include "common.h"
+#include "surface.h"     // vis_slope: shared with polarimetric.hip
 
 namespace wass {
 
@@ -101,14 +102,6 @@ __device__ __forceinline__ bool vis_march(const double* __restrict__ Zc, int H, 
         }
     }
     return false;
-}
-
-// np.gradient of a float32 line with spacing d: the difference in float32, the quotient rounded to float32
-__device__ __forceinline__ double vis_slope(float lo, float here, float hi, bool first, bool last, double d)
-{
-    if (first) return (double)(float)((double)(hi - here) / d);
-    if (last) return (double)(float)((double)(here - lo) / d);
-    return (double)(float)((double)(hi - lo) / (2.0 * d));
 }
 
 struct VisGeom {

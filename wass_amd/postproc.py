@@ -984,3 +984,285 @@ def radiance_threshold(radiance, radiance_bg, threshold_val: float = 0.35, use_v
         mask = np.empty((count, H, W), np.uint8)
         ctx._check(lib.wass_radiance_mask(ctx._h, *ptrs, count, H, W, int(batch), m.ctypes.data, thr.ctypes.data, mask.ctypes.data))
     return mask, thr
+
+
+# ---- polarimetric set-up of the cube: wasspost polarimetric_setup (wasspost.py:627-805), clip and zeromean ------------------------
+POL_OUTPUTS = ("S", "occlusion", "angles", "dolp", "normals", "rays_cam")       # bit k of the C entry's `outputs` is POL_OUTPUTS[k]
+
+
+def bilinear_table() -> np.ndarray:
+    """The weights of the bilinear sampler, float32 [32, 32, 2, 2] = [fy, fx, ky, kx] (OpenCV's initInterTab2D for INTER_LINEAR,
+    restated): ty[ky] * tx[kx] with t = (1 - f / 32, f / 32); no GPU needed."""
+    from . import _lib
+    tab = np.empty((32, 32, 2, 2), np.float32)
+    rc = _lib.load().wass_bilinear_table_f32(tab.ctypes.data)
+    if rc:
+        raise ValueError(f"wass_bilinear_table_f32: error {rc}")
+    return tab
+
+
+def remap_linear_f32(image, mapx, mapy, ctx: Context | None = None):
+    """cv.remap(image, mapx, mapy, cv.INTER_LINEAR) for a float32 picture and float32 maps, constant border 0, in OpenCV's float
+    pipeline: 1/32 pixel phases, the four float32 weights of bilinear_table(), ((v00 w00 + v01 w01) + v10 w10) + v11 w11 in float32.
+    Host arrays give a host result, device tensors a device tensor.  Each tap outside the picture counts 0; NaN and infinite
+    samples propagate; a map value that is NaN, infinite or beyond +-2^26 gives 0."""
+    if len(image.shape) != 2 or not (1 <= int(image.shape[0]) < 32767 and 1 <= int(image.shape[1]) < 32767):
+        raise ValueError("a picture is Ih x Iw float32 with sides from 1 to 32766")
+    if len(mapx.shape) != 2 or tuple(mapx.shape) != tuple(mapy.shape) or min(int(v) for v in mapx.shape) < 1:
+        raise ValueError("mapx and mapy must be two h x w maps of one shape")
+    sh, sw = (int(v) for v in image.shape)
+    dh, dw = (int(v) for v in mapx.shape)
+    if ctx is None:
+        ctx = Context(0)
+    if _is_device(image):
+        import torch
+        if not (_is_device(mapx) and _is_device(mapy)):
+            raise ValueError("the picture and the maps must be on the same side")
+        src = image.to(torch.float32).contiguous()
+        mx, my = mapx.to(torch.float32).contiguous(), mapy.to(torch.float32).contiguous()
+        dst = torch.empty((dh, dw), dtype=torch.float32, device=src.device)
+        torch.cuda.current_stream(src.device).synchronize()
+        ctx._check(ctx._lib.wass_remap_linear_f32_dev(ctx._h, src.data_ptr(), sw, sh, sw, mx.data_ptr(), my.data_ptr(), dw, dh, dst.data_ptr()))
+        ctx.synchronize()
+        return dst
+    src = np.ascontiguousarray(image, np.float32)
+    mx, my = np.ascontiguousarray(mapx, np.float32), np.ascontiguousarray(mapy, np.float32)
+    dst = np.empty((dh, dw), np.float32)
+    ctx._check(ctx._lib.wass_remap_linear_f32(ctx._h, src.ctypes.data, sw, sh, sw, mx.ctypes.data, my.ctypes.data, dw, dh, dst.ctypes.data))
+    return dst
+
+
+def _pol_outputs(outputs) -> int:
+    outputs = tuple(outputs)
+    for name in outputs:
+        if name not in POL_OUTPUTS:
+            raise ValueError(f"unknown output {name!r}: choose among {POL_OUTPUTS}")
+    return sum(1 << k for k, name in enumerate(POL_OUTPUTS) if name in outputs)
+
+
+def polarimetric_scratch_bytes(count: int, H: int, W: int, Ih: int, Iw: int, batch: int = 8, host: bool = True,
+                               outputs=("S", "occlusion")):
+    """(bytes of device scratch, frames per launch) of one polarimetric_setup call; no GPU needed."""
+    from . import _lib
+    b, n = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_polarimetric_scratch_bytes(int(count), int(H), int(W), int(Ih), int(Iw), int(batch), int(bool(host)),
+                                                     _pol_outputs(outputs), C.byref(b), C.byref(n))
+    if rc:
+        raise ValueError(f"wass_polarimetric_scratch_bytes({count}, {H}, {W}, pictures {Ih} x {Iw}, batch {batch}): error {rc}")
+    return b.value, n.value
+
+
+@dataclass
+class PolarimetricResult:
+    """What polarimetric_setup returns.  The per-frame arrays are None unless named in `outputs`."""
+    Savg: object                    # float64 [H, W, 3]: the mean Stokes vector over the frames in which the cell is visible
+    Navg: object                    # float64 [H, W, 3]: the mean normal, unit length
+    Zavg: object                    # float64 [H, W]: the mean height in metres (not NaN-aware)
+    valid: object                   # float64 [H, W]: in how many frames the cell is visible
+    occluded_percent: np.ndarray    # float64 [count]
+    S: object = None                # float32 [count, H, W, 3], NaN in occluded cells
+    occlusion: object = None        # uint8 [count, H, W]
+    angles: object = None           # float32 [count, H, W], degrees
+    dolp: object = None             # float32 [count, H, W]
+    normals: object = None          # float64 [count, H, W, 3]
+    rays_cam: object = None         # float64 [count, 3, H * W]
+
+
+_POL_SHAPES = {"S": (lambda H, W: (H, W, 3), "float32"), "occlusion": (lambda H, W: (H, W), "uint8"),
+               "angles": (lambda H, W: (H, W), "float32"), "dolp": (lambda H, W: (H, W), "float32"),
+               "normals": (lambda H, W: (H, W, 3), "float64"), "rays_cam": (lambda H, W: (3, H * W), "float64")}
+
+
+def polarimetric_setup(stokes, data, XX, YY, Pplane, cam_to_grid, K, datascale: float = 1e-3, angle_limit: float = 85.0,
+                       outputs=("S", "occlusion"), total_frames: int | None = None, ctx: Context | None = None, batch: int = 8):
+    """wasspost polarimetric_setup as a function.  `stokes` holds the float32 pictures S0, S1, S2 of every frame: a
+    count x 3 x Ih x Iw host array, memmap or device tensor, or an iterable of (S0, S1, S2) triples; `data` is the count x H x W
+    float32 cube in the unit that `datascale` turns into metres, a host array or memmap (host results) or a device tensor (device
+    results); XX, YY the H x W grid in metres; Pplane, cam_to_grid and K the matrices P{cam}plane (4 x 4), Cam{cam}toGrid (4 x 4)
+    and intr{cam} (3 x 3).  Per frame and cell: the projection of `radiance`, the camera-frame viewing ray, the normals of
+    compute_slope_and_normals, the mask and angles of visibility_map(..., angle_limit), the three pictures sampled with
+    remap_linear_f32 and blanked (NaN) in occluded cells, DOLP = sqrt(S1^2 + S2^2) / S0 in float32.  The averages are fp64 sums in
+    frame order: Savg = sum(nan_to_num(S)) / valid, Navg = sum(normals), normalised, Zavg = sum(z) / total_frames (default: the
+    number of frames), valid = sum(1 - mask).  Only the per-frame arrays named in `outputs` are produced (normals and rays_cam
+    are 48 bytes per cell and frame).  A finite cell at or above the camera raises ValueError."""
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W = (int(v) for v in data.shape)
+    if count < 1:
+        raise ValueError("no frames")
+    XX, YY = _check_grid(XX, YY, H, W)
+    cam = np.asarray(cam_to_grid, np.float64)
+    if cam.shape != (4, 4):
+        raise ValueError("cam_to_grid must be 4 x 4")
+    K = np.asarray(K, np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("K must be 3 x 3")
+    if np.asarray(Pplane).shape != (4, 4):
+        raise ValueError("Pplane must be 4 x 4")
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    if total_frames is None:
+        total_frames = count
+    if int(total_frames) < 1:
+        raise ValueError("total_frames must be at least 1")
+    bits = _pol_outputs(outputs)
+    whole = hasattr(stokes, "shape")
+    if whole:
+        if len(stokes.shape) != 4 or int(stokes.shape[0]) != count or int(stokes.shape[1]) != 3:
+            raise ValueError(f"stokes must be {count} x 3 x Ih x Iw")
+    Kinv = np.linalg.inv(K)
+    if ctx is None:
+        ctx = Context(0)
+    dev = _is_device(data)
+    if dev:
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+        new = lambda shape, dt: torch.empty(shape, dtype=getattr(torch, dt), device=data.device)
+        acc = torch.zeros(8 * H * W, dtype=torch.float64, device=data.device)
+        grid = (torch.tensor(XX).to(data.device), torch.tensor(YY).to(data.device))      # a copy: the caller's may be read-only
+        ptr = lambda a: a.data_ptr()
+        entry = ctx._lib.wass_polarimetric_dev
+    else:
+        data = _host_f32_rows(data)
+        new = lambda shape, dt: np.empty(shape, getattr(np, dt))
+        acc = np.zeros(8 * H * W, np.float64)
+        grid = (XX, YY)
+        ptr = lambda a: a.ctypes.data
+        entry = ctx._lib.wass_polarimetric
+    per_frame = {name: new((count,) + _POL_SHAPES[name][0](H, W), _POL_SHAPES[name][1])
+                 for k, name in enumerate(POL_OUTPUTS) if bits >> k & 1}
+    counts = np.zeros(count, np.uint64)
+    from ._lib import PolOut, PolParams
+
+    def run(pics, t0, n):
+        """frames t0 .. t0 + n - 1 from pics, n x 3 x Ih x Iw on any side"""
+        Ih, Iw = int(pics.shape[2]), int(pics.shape[3])
+        if not (1 <= Ih < 32767 and 1 <= Iw < 32767):
+            raise ValueError("a picture is Ih x Iw float32 with sides from 1 to 32766")
+        pcam = radiance_pcam(Pplane, Iw, Ih)
+        p = PolParams()
+        p.Pcam[:] = [float(v) for v in pcam[:3].ravel()]
+        p.Kinv[:] = [float(v) for v in Kinv.ravel()]
+        p.origin[:] = [float(v) for v in cam[:3, -1]]
+        p.datascale = float(datascale)
+        p.angle_limit = -1.0 if angle_limit is None else float(angle_limit)
+        p.batch = int(batch)
+        p.total_frames = int(total_frames) if t0 + n == count else 0
+        o = PolOut()
+        for name, a in per_frame.items():
+            setattr(o, name, ptr(a[t0:t0 + n]))
+        up = C.c_uint64()
+        cube = data[t0:t0 + n]
+        if dev:
+            if not _is_device(pics):
+                pics = torch.from_numpy(np.ascontiguousarray(pics, np.float32)).to(data.device)
+            if pics.dtype != torch.float32 or pics.stride(3) != 1 or min(pics.stride(k) for k in range(3)) <= 0:
+                pics = pics.to(torch.float32).contiguous()
+            torch.cuda.current_stream(data.device).synchronize()
+            ss = [pics.stride(k) for k in range(3)]
+            cs = (cube.stride(0), cube.stride(1))
+        else:
+            if _is_device(pics):
+                pics = pics.cpu().numpy()
+            if not isinstance(pics, np.ndarray) or pics.dtype != np.float32 or pics.strides[3] != 4 or any(s % 4 or s <= 0 for s in pics.strides[:3]):
+                pics = np.ascontiguousarray(pics, np.float32)
+            ss = [s // 4 for s in pics.strides[:3]]
+            cs = (cube.strides[0] // 4, cube.strides[1] // 4)
+        ctx._check(entry(ctx._h, ptr(pics), ss[0], ss[1], ss[2], Ih, Iw, ptr(cube), cs[0], cs[1], n, H, W, ptr(grid[0]), ptr(grid[1]),
+                         C.byref(p), ptr(acc), C.byref(o), counts[t0:].ctypes.data, C.byref(up)))
+        if up.value:
+            raise ValueError(f"rays must go upward: {up.value} cells lie at or above the camera")
+
+    if whole:
+        run(stokes, 0, count)
+    else:
+        t0, pending = 0, []
+
+        def flush():
+            nonlocal t0, pending
+            if pending:
+                if dev and all(_is_device(a) for tr in pending for a in tr):
+                    import torch
+                    stack = torch.stack([torch.stack(list(tr)) for tr in pending])
+                else:
+                    stack = np.stack([np.stack([a.cpu().numpy() if _is_device(a) else np.asarray(a, np.float32) for a in tr]) for tr in pending])
+                run(stack, t0, len(pending))
+                t0 += len(pending)
+                pending = []
+
+        for triple in stokes:
+            triple = tuple(triple)
+            if len(triple) != 3 or any(len(a.shape) != 2 or tuple(a.shape) != tuple(triple[0].shape) for a in triple):
+                raise ValueError("every frame needs three pictures S0, S1, S2 of one shape")
+            if t0 + len(pending) >= count:
+                raise ValueError(f"more than {count} frames of pictures")
+            if pending and tuple(pending[0][0].shape) != tuple(triple[0].shape):
+                flush()                                 # the projection depends on the picture's size
+            pending.append(triple)
+            if len(pending) == int(batch) and t0 + len(pending) < count:
+                flush()                                 # the last chunk is flushed below: it ends the sequence
+        if t0 + len(pending) != count:
+            raise ValueError(f"{t0 + len(pending)} frames of pictures for {count} frames")
+        flush()
+    if dev:
+        ctx.synchronize()
+    HW = H * W
+    return PolarimetricResult(Savg=acc[:3 * HW].reshape(H, W, 3), Navg=acc[3 * HW:6 * HW].reshape(H, W, 3), Zavg=acc[6 * HW:7 * HW].reshape(H, W),
+                              valid=acc[7 * HW:].reshape(H, W), occluded_percent=100.0 * counts.astype(np.float64) / float(HW), **per_frame)
+
+
+def _cube_io(data, out, what):
+    """(data, out, suffix, pointers and strides) of a float32 cube and its result, on one side"""
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W = (int(v) for v in data.shape)
+    if count < 1 or H < 1 or W < 1:
+        raise ValueError("empty cube")
+    if _is_device(data):
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+        if out is None:
+            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
+        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or out.stride(2) != 1 \
+                or out.stride(0) <= 0 or out.stride(1) <= 0:
+            raise ValueError(f"{what}: out must be a float32 device tensor of the input's shape with a contiguous last axis")
+        torch.cuda.current_stream(data.device).synchronize()
+        return data, out, "_dev", (data.data_ptr(), data.stride(0), data.stride(1), count, H, W), (out.data_ptr(), out.stride(0), out.stride(1))
+    src = _host_f32_rows(data)
+    if out is None:
+        out = np.empty((count, H, W), np.float32)
+    elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or out.strides[2] != 4 \
+            or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0:
+        raise ValueError(f"{what}: out must be a float32 host array of the input's shape with a contiguous last axis")
+    return src, out, "", (src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W), \
+        (out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4)
+
+
+def clip_cube(data, minval: float, maxval: float, out=None, ctx: Context | None = None):
+    """wasspost clip as a function: (np.clip(data, float32(minval), float32(maxval)) in float32 with NaN kept, vmin, vmax), vmin
+    and vmax the smallest and largest value of the result that is not NaN (NaN if there is none).  A host array or memmap gives
+    a host array, a device tensor a device tensor; `out` may be `data`."""
+    lo, hi = np.float32(minval), np.float32(maxval)
+    if np.isnan(lo) or np.isnan(hi):
+        raise ValueError("minval and maxval must be numbers")
+    data, out, suffix, a, b = _cube_io(data, out, "clip_cube")
+    if ctx is None:
+        ctx = Context(0)
+    vmin, vmax = C.c_float(), C.c_float()
+    ctx._check(getattr(ctx._lib, "wass_clip_cube" + suffix)(ctx._h, *a, float(lo), float(hi), *b, C.byref(vmin), C.byref(vmax)))
+    return out, np.float32(vmin.value), np.float32(vmax.value)
+
+
+def zeromean(data, out=None, ctx: Context | None = None):
+    """wasspost zeromean as a function: float32(double(data) - mean), the mean of every cell over time an fp64 sum in frame order
+    divided by the number of frames.  A cell that is NaN in any frame is NaN in all.  A host array or memmap gives a host
+    array, a device tensor a device tensor; `out` may be `data`."""
+    data, out, suffix, a, b = _cube_io(data, out, "zeromean")
+    if ctx is None:
+        ctx = Context(0)
+    ctx._check(getattr(ctx._lib, "wass_zeromean" + suffix)(ctx._h, *a, *b))
+    if suffix:
+        ctx.synchronize()
+    return out
