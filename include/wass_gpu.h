@@ -893,6 +893,56 @@ int wass_clahe(wass_ctx* ctx, const uint8_t* src, int w, int h, size_t src_strid
                uint8_t* dst);
 int wass_clahe_dev(wass_ctx* ctx, const uint8_t* d_src, int w, int h, size_t src_stride, double clip_limit, int tiles_x, int tiles_y,
                    uint8_t* d_dst);
+/* ---- Polarimetric preparation: process_image with do_demosaic of wass_prepare (wass_prepare.cpp:52-85, :103-255) in one pass.
+ * mosaic is the u8 picture of a polarising-filter-array camera, rows x cols, macro-pixels  I90 I45 / I135 I0 ; m = rows / 2,
+ * n = cols / 2 (an odd last row or column is dropped) and every result is 2m x 2n, tightly packed.  Per pixel: the four quarter
+ * pictures as float32, u8 * (1.0f / 255.0f); upscaled x2 as cv::resize INTER_LINEAR does for floats, along x and then along y
+ * (weights 0.25 / 0.75; first and last row and column copied); undistorted with the map of the undistort entry above for
+ * (K, dist) -- K applies to the 2m x 2n picture -- and the float32 sampler of the remap_linear_f32 entry (its 1024 x 2 x 2 table, the
+ * same order of the sum, taps outside the picture 0); mixed so that I0 + I90 = I45 + I135 (k1 = 0.75, k2 = 0.25, left to right);
+ * S0 = (((I0 + I45) + I90) + I135) * 0.5f, S1 = I0 - I90, S2 = I45 - I135.  Every float32 product and sum is rounded on its own.
+ *   image      u8, always: sat_u8(rint(S0 * 127.0f)), or with hdr != 0 sat_u8(rint(HDR * 255.0f)), HDR = sum(w I) / sum(w) over the
+ *              four channels in the order 0, 45, 90, 135, w = float32(exp(double(arg))), arg = (-1.0f * (d * d)) / (2.0f * 0.3f * 0.3f),
+ *              d = I - 0.5f; then, with clahe_tiles > 0, the CLAHE entry above with (clahe_clip, clahe_tiles, clahe_tiles) applied
+ *   S          float32 [3][2m][2n]
+ *   dolp       u8: sat_u8(rint(dolp * 255.0f)), dolp = sqrt(S1 S1 + S2 S2) / S0 in float32
+ *   aolp       u8: sat_u8(rint(a * float32(255.0 / 3.1415) + 127.0f)), a = (float32(ang) - 3.1415f) * 0.5f, ang = atan2(S1, S2) in
+ *              fp64 plus 2 pi where negative (the reference's cartToPolar is a 0.3 degree approximation; this is the arctangent)
+ *   channels   u8 [4][2m][2n]: sat_u8(rint(I * 255.0f)) of the mixed I0, I45, I90, I135
+ *   image_f32, aolp_f32   float32: the value of image (before CLAHE) and of aolp before rint and sat_u8
+ * sat_u8 clamps to 0 ... 255 and turns NaN into 0; rint rounds half to even.  Only the results named in params->outputs are written
+ * (their pointers must not be NULL); image is always written.  ranges = min and max of S0, S1, S2 and dolp, NaN skipped (dolp: NaN
+ * unless WASS_PREP_DOLP).  Errors as for the undistort entry; rows or cols below 2: WASS_ERR_INVALID_ARG; 2m or 2n above 32767:
+ * WASS_ERR_UNSUPPORTED.  stride is in bytes.  _dev: mosaic and the results are device memory.  Both return after a synchronisation.
+ * Written from knowledge of OpenCV 4.5.5 and not pinned against it. */
+#define WASS_PREP_STOKES 1
+#define WASS_PREP_DOLP 2
+#define WASS_PREP_AOLP 4
+#define WASS_PREP_CHANNELS 8
+#define WASS_PREP_IMAGE_F32 16
+#define WASS_PREP_AOLP_F32 32
+#define WASS_PREP_ALL 63
+typedef struct wass_pol_prep_params {
+    int hdr;                /* 0: image = S0 x 127; otherwise the HDR picture x 255 */
+    int outputs;            /* WASS_PREP_* bits */
+    double clahe_clip;
+    int clahe_tiles;        /* 0: no CLAHE */
+    int reserved;
+} wass_pol_prep_params;
+typedef struct wass_pol_prep_out {
+    float* S;
+    uint8_t* image;
+    uint8_t* dolp;
+    uint8_t* aolp;
+    uint8_t* channels;
+    float* image_f32;
+    float* aolp_f32;
+    float ranges[8];        /* S0 min, S0 max, S1 min, S1 max, S2 min, S2 max, dolp min, dolp max */
+} wass_pol_prep_out;
+int wass_prepare_pol(wass_ctx* ctx, const uint8_t* mosaic, int cols, int rows, size_t stride, const double K[9], const double* dist,
+                     int n_dist, const wass_pol_prep_params* params, wass_pol_prep_out* out);
+int wass_prepare_pol_dev(wass_ctx* ctx, const uint8_t* d_mosaic, int cols, int rows, size_t stride, const double K[9],
+                         const double* dist, int n_dist, const wass_pol_prep_params* params, wass_pol_prep_out* out);
 /* cv::warpPerspective(src, dst, H, Size(dw,dh)) with the default INTER_LINEAR / BORDER_CONSTANT 0
  * (wass_stereo.cpp:515-516); H maps source to destination pixels (it is inverted internally). */
 int wass_warp_perspective(wass_ctx* ctx, const uint8_t* src, int sw, int sh, size_t src_stride, const double H[9],

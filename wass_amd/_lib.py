@@ -114,6 +114,16 @@ class PolOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("S", "occlusion", "angles", "dolp", "normals", "rays_cam")]
 
 
+class PolPrepParams(C.Structure):
+    """wass_pol_prep_params"""
+    _fields_ = [("hdr", C.c_int), ("outputs", C.c_int), ("clahe_clip", C.c_double), ("clahe_tiles", C.c_int), ("reserved", C.c_int)]
+
+
+class PolPrepOut(C.Structure):
+    """wass_pol_prep_out"""
+    _fields_ = [(n, C.c_void_p) for n in ("S", "image", "dolp", "aolp", "channels", "image_f32", "aolp_f32")] + [("ranges", C.c_float * 8)]
+
+
 def default_sgm_params(num_disp: int, ndirs: int = 5, min_disp: int = 1, win: int = 13, p1_mult: int = 2,
                        p2_mult: int = 64, disp_offset: int = 0) -> SgmParams:
     """Defaults of SURVEY.md Appendix C (wass_stereo.cpp:742-759)."""
@@ -281,6 +291,10 @@ SYMBOLS = {
     "wass_remap_cubic_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _i, _i, C.POINTER(_i), _vp]),
     "wass_undistort": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _vp]),
     "wass_undistort_dev": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _vp]),
+    "wass_prepare_pol": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(PolPrepParams),
+                              C.POINTER(PolPrepOut)]),
+    "wass_prepare_pol_dev": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(PolPrepParams),
+                                  C.POINTER(PolPrepOut)]),
     "wass_warp_perspective": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(C.c_double), _i, _i, C.POINTER(_i), _vp]),
     "wass_warp_perspective_dev": (_i, [_vp, _vp, _i, _i, _sz, C.POINTER(C.c_double), _i, _i, C.POINTER(_i), _vp]),
 }

@@ -197,6 +197,7 @@ struct wass_ctx {
     struct UndCache { double K[9] = {}; int w = 0, h = 0; bool valid = false; wass::Buf xy; } und_cache[2];
     int und_next = 0;
     wass::Buf clahe_lut;           // per-tile look-up tables of wass_clahe_dev
+    wass::Buf prep_pol;            // wass_prepare_pol: per-block range keys and the eight reduced ranges (prepare_pol.hip)
     // stage events of the SGM call, two sets used alternately so that the timings of call n can be read after call
     // n+1 has been enqueued (a lagging reader never stalls the pipeline)
     // (four sets, not two, since round 5: a driver that runs two frames ahead reads call n's timings after call n+2 has been enqueued)
@@ -330,5 +331,8 @@ int launch_select(wass_ctx* c, const SgmDims& d);
 int launch_median_crop(wass_ctx* c, const SgmDims& d, int16_t* d_out);
 int wait_uploads(wass_ctx* c, const void* p, hipStream_t s);   // order s after the pending uploads that cover p
 int launch_median_full(wass_ctx* c, const SgmDims& d, int16_t* d_padded_out);   // the whole padded map (speckle filter path)
+// rectify.hip: cv::undistort's normalised coordinates of camera (K, w, h), cached per context; *d_xy = w column values, then h row values
+int undistort_tables(wass_ctx* c, const double* K, int w, int h, const double** d_xy);
+int ensure_bilinear_tab(wass_ctx* c);         // polarimetric.hip: the 1024 x 2 x 2 float32 table in c->bilinear_tab
 
 }  // namespace wass

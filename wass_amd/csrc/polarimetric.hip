@@ -52,7 +52,7 @@ static void build_bilinear_tab(float* tab)
 
 constexpr size_t BILINEAR_TAB_BYTES = (size_t)POL_TAB2 * 4 * sizeof(float);     // 16 KiB
 
-static int ensure_bilinear_tab(wass_ctx* c)
+int ensure_bilinear_tab(wass_ctx* c)
 {
     if (c->bilinear_tab_ready) return WASS_OK;
     int rc = ensure(c, c->bilinear_tab, BILINEAR_TAB_BYTES);

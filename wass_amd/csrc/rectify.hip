@@ -10,6 +10,7 @@
 // from 32x32 tables of int16 products scaled by 2^15 (with OpenCV's sum fix-up), (sum + 2^14) >> 15, constant-0
 // border taps.
 #include "common.h"
+#include "undistort_map.h"
 
 #include <cfloat>
 #include <cmath>
@@ -183,7 +184,6 @@ __global__ __launch_bounds__(256) void k_remap_cubic(const uint8_t* __restrict__
 // cv::undistort: normalised coordinates per column / per row come from the host (the column sequence is an
 // accumulated sum in OpenCV, the row value depends on the stripe the row belongs to); the distortion polynomial,
 // the 1/32-pixel quantisation and the bilinear taps run here, one thread per pixel.
-struct Dist12 { double k[12]; };
 __global__ __launch_bounds__(256) void k_undistort(const uint8_t* __restrict__ src, int w, int h, size_t ss,
                                                    const double* __restrict__ xs, const double* __restrict__ ys, Dist12 D,
                                                    double fx, double fy, double u0, double v0, uint8_t* __restrict__ dst,
@@ -191,16 +191,8 @@ __global__ __launch_bounds__(256) void k_undistort(const uint8_t* __restrict__ s
 {
     const int tx = blockIdx.x * 64 + threadIdx.x, ty = blockIdx.y * 4 + threadIdx.y;
     if (tx >= w || ty >= h) return;
-    const double* k = D.k;
-    const double x = xs[tx], y = ys[ty];
-    const double x2 = x * x, y2 = y * y;
-    const double r2 = x2 + y2, _2xy = 2 * x * y;
-    const double kr = (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2) / (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2);
-    const double xd = (x * kr + k[2] * _2xy + k[3] * (r2 + 2 * x2) + k[8] * r2 + k[9] * r2 * r2);
-    const double yd = (y * kr + k[2] * (r2 + 2 * y2) + k[3] * _2xy + k[10] * r2 + k[11] * r2 * r2);
-    const double u = fx * xd + u0, v = fy * yd + v0;
-    const int iu = __double2int_rn(fmax(-2147483648.0, fmin(2147483647.0, u * 32)));
-    const int iv = __double2int_rn(fmax(-2147483648.0, fmin(2147483647.0, v * 32)));
+    int iu, iv;
+    undistort_map(xs[tx], ys[ty], D, fx, fy, u0, v0, iu, iv);
     const int a = (iv & (TAB - 1)) * TAB + (iu & (TAB - 1));
     dst[(size_t)ty * w + tx] = sample_linear(src, w, h, ss, (int)(short)(iu >> INTER_BITS), (int)(short)(iv >> INTER_BITS),
                                              tab + TAB_LIN_OFF + (size_t)a * 4);
@@ -382,21 +374,11 @@ static int resample_host(wass_ctx* c, bool cubic, const uint8_t* src, int sw, in
     return WASS_OK;
 }
 
-static int undistort_dev(wass_ctx* c, const uint8_t* d_src, int w, int h, size_t ss, const double* K, const double* dist, int n,
-                         uint8_t* d_dst)
+// The normalised coordinates of cv::undistort depend on (K, w, h) only: one table per camera is kept on the device, so the per-frame
+// call of a sequence computes nothing on the host and does not synchronise.  *dxy: w column values, then h row values.
+int undistort_tables(wass_ctx* c, const double* K, int w, int h, const double** dxy)
 {
-    if (!c) return WASS_ERR_INVALID_ARG;
-    if (!d_src || !d_dst || !K || (!dist && n) || w <= 0 || h <= 0 || ss < (size_t)w) return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
-    if (!(n == 0 || n == 4 || n == 5 || n == 8 || n == 12))
-        return set_err(c, WASS_ERR_UNSUPPORTED, "%d distortion coefficients (4, 5, 8 or 12 supported; no tilt model)", n);
-    if (w > 32767 || h > 32767) return set_err(c, WASS_ERR_UNSUPPORTED, "images larger than 32767 px are not supported");
-    Dist12 D;
-    for (int i = 0; i < 12; ++i) D.k[i] = i < n ? dist[i] : 0.0;
-    int rc = ensure_tables(c);
-    if (rc) return rc;
-    if ((rc = wait_uploads(c, d_src, c->stream))) return rc;
-    // The normalised coordinates depend on (K, w, h) only: one table per camera is kept on the device, so the per-frame call
-    // of a sequence computes nothing on the host and does not synchronise.
+    int rc;
     wass_ctx::UndCache* hit = nullptr;
     for (auto& e : c->und_cache)
         if (e.valid && e.w == w && e.h == h && memcmp(e.K, K, sizeof e.K) == 0) hit = &e;
@@ -429,7 +411,25 @@ static int undistort_dev(wass_ctx* c, const uint8_t* d_src, int w, int h, size_t
         memcpy(e.K, K, sizeof e.K); e.w = w; e.h = h; e.valid = true;
         hit = &e;
     }
-    const double* dxy = (const double*)hit->xy.p;
+    *dxy = (const double*)hit->xy.p;
+    return WASS_OK;
+}
+
+static int undistort_dev(wass_ctx* c, const uint8_t* d_src, int w, int h, size_t ss, const double* K, const double* dist, int n,
+                         uint8_t* d_dst)
+{
+    if (!c) return WASS_ERR_INVALID_ARG;
+    if (!d_src || !d_dst || !K || (!dist && n) || w <= 0 || h <= 0 || ss < (size_t)w) return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
+    if (!(n == 0 || n == 4 || n == 5 || n == 8 || n == 12))
+        return set_err(c, WASS_ERR_UNSUPPORTED, "%d distortion coefficients (4, 5, 8 or 12 supported; no tilt model)", n);
+    if (w > 32767 || h > 32767) return set_err(c, WASS_ERR_UNSUPPORTED, "images larger than 32767 px are not supported");
+    Dist12 D;
+    for (int i = 0; i < 12; ++i) D.k[i] = i < n ? dist[i] : 0.0;
+    int rc = ensure_tables(c);
+    if (rc) return rc;
+    if ((rc = wait_uploads(c, d_src, c->stream))) return rc;
+    const double* dxy = nullptr;
+    if ((rc = undistort_tables(c, K, w, h, &dxy))) return rc;
     hipLaunchKernelGGL(k_undistort, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, c->stream, d_src, w, h, ss, dxy, dxy + w, D,
                        K[0], K[4], K[2], K[5], d_dst, (const short*)c->rect_tab.p);
     WASS_HIP(c, hipGetLastError());

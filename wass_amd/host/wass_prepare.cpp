@@ -6,8 +6,9 @@
 //
 // Same options, exit codes, calibdir inputs (intrinsics_0X.xml, distortion_0X.xml, ext_R.xml, ext_T.xml,
 // prepare_config.txt), workdir outputs (undistorted/0000000X.png, intrinsics_0000000X.xml, ext_R.xml, ext_T.xml), stdout
-// progress markers and log lines as the reference.  Out of scope and rejected loudly: the polarimetric camera branch
-// (--demosaic / --hdr / --dolp-aolp / --save-channels / --save-stokes, :100-255).  Inputs: PNG, TIFF and baseline JPEG
+// progress markers and log lines as the reference.  Rejected loudly: the polarimetric camera branch
+// (--demosaic / --hdr / --dolp-aolp / --save-channels / --save-stokes, :100-255).  The library entry for it exists
+// (wass_prepare_pol, prepare_pol.hip; wass_amd.prepare in Python); only the wiring into this program waits.  Inputs: PNG, TIFF and baseline JPEG
 // (hostio.hpp, tiff.hpp, jpeg_read.hpp), the formats wasscli accepts (wasscli.py:47).
 // There is NO CPU implementation of the image work: without a GPU (or libwassgpu.so) the program fails with exit -1.
 #include <sys/stat.h>
