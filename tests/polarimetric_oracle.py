@@ -138,8 +138,11 @@ def frame(stokes3, Zframe, XX, YY, Pplane, cam_to_grid, K, datascale=1e-3, angle
 def setup(stokes, Z, XX, YY, Pplane, cam_to_grid, K, datascale=1e-3, angle_limit=85.0, total_frames=None, acc_dtype=np.float64,
           use_nan_to_num=True):
     """the sequence: per-frame arrays stacked, and Savg, Navg, Zavg, valid.  acc_dtype float32 and use_nan_to_num False are the
-    mistakes the tests must be able to see."""
+    mistakes the tests must be able to see.  `stokes` is a count x 3 x Ih x Iw array or a sequence of count (S0, S1, S2) triples
+    whose picture size may change from frame to frame: every frame is projected with the Pcam of its own pictures, and the sums
+    run over the frames in order whatever their sizes."""
     count, H, W = np.shape(Z)
+    assert len(stokes) == count and all(len(s) == 3 and np.shape(s[0]) == np.shape(s[1]) == np.shape(s[2]) for s in stokes)
     frames = [frame(stokes[t], Z[t], XX, YY, Pplane, cam_to_grid, K, datascale, angle_limit) for t in range(count)]
     Savg, Navg = np.zeros((H, W, 3), acc_dtype), np.zeros((H, W, 3), acc_dtype)
     Zavg, valid = np.zeros((H, W), acc_dtype), np.zeros((H, W), acc_dtype)
@@ -166,18 +169,36 @@ def clip_cube(x, lo, hi):
     return out, (out[ok].min() if ok.any() else F(np.nan)), (out[ok].max() if ok.any() else F(np.nan))
 
 
-def zeromean(x):
-    """the mean by an fp64 loop over the frames in order, then float32(double(x) - mean)"""
+def zeromean(x, reverse: bool = False):
+    """the mean by an fp64 loop over the frames in order, then float32(double(x) - mean).  reverse=True adds the frames from the
+    last to the first: the mistake the tests must be able to see."""
     x = np.asarray(x, F)
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         total = np.zeros(x.shape[1:], np.float64)
-        for t in range(x.shape[0]):
+        for t in (range(x.shape[0] - 1, -1, -1) if reverse else range(x.shape[0])):
             total = total + x[t].astype(np.float64)
         mean = total / np.float64(x.shape[0])
         return (x.astype(np.float64) - mean).astype(F)
 
 
 # ---- scenes -------------------------------------------------------------------------------------------------------------------------
+def spread_cube(shape, seed, pairs: bool = True):
+    """count x H x W float32: magnitudes over six decades and, in about half of the series of three frames or more, two frames that
+    hold +B and -B with B = 2^55 .. 2^69.  Between the two the running fp64 sum is a multiple of ulp(B) >= 8 and drops what it is
+    given below that, so which frames are lost depends on the order of the sum: adding the frames backwards gives another mean."""
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal(shape) * 10.0 ** rng.uniform(-2, 4, shape)).astype(F)
+    count = shape[0]
+    if pairs and count >= 3:
+        a = rng.integers(0, count, shape[1:])
+        b = (a + rng.integers(1, count, shape[1:])) % count
+        big = (2.0 ** rng.integers(55, 70, shape[1:]) * rng.choice([-1.0, 1.0], shape[1:])).astype(F)
+        on = rng.random(shape[1:]) < 0.5
+        np.put_along_axis(x, a[None], np.where(on, big, np.take_along_axis(x, a[None], 0)[0])[None], 0)
+        np.put_along_axis(x, b[None], np.where(on, -big, np.take_along_axis(x, b[None], 0)[0])[None], 0)
+    return x
+
+
 def stokes_pictures(count, h, w, seed):
     """count x 3 x h x w float32: S0 positive around 1, S1 and S2 signed and smaller, all textured so that every tap matters"""
     rng = np.random.default_rng(seed)
@@ -193,6 +214,58 @@ def stokes_pictures(count, h, w, seed):
 def intrinsics(Iw, Ih):
     f = 1.2 * Iw
     return np.array([[f, 0.0, Iw / 2.0 - 0.5], [0.0, 1.01 * f, Ih / 2.0 + 0.25], [0.0, 0.0, 1.0]])
+
+
+# ---- the seas of the edge tests (tests/test_polarimetric_edges_gpu.py) ----------------------------------------------------------------
+# name: H, W, du, seed, amp, camera side, height, back, footprint, picture (Ih, Iw).  Chosen on the CPU so that the oracle has no cell
+# at or above the camera and none whose angle lies within visibility_oracle.angle_bound of 85 degrees: test_edge_scenes_are_decided in
+# tests/test_polarimetric.py holds them to that without a GPU.
+SMALL = {
+    "2x2": (2, 2, 0.5, 21, 0.6, "west", 4.0, 3.0, "inside", (240, 320)),
+    "2x65": (2, 65, 0.25, 22, 1.0, "west", 5.0, 4.0, "inside", (240, 320)),
+    "5x3": (5, 3, 0.5, 23, 0.8, "south", 4.0, 3.0, "inside", (240, 320)),
+    "9x130": (9, 130, 0.25, 24, 1.0, "south", 5.0, 6.0, "crossing", (240, 320)),
+    "5x3, 2 x 3 pictures": (5, 3, 0.5, 23, 0.8, "south", 4.0, 3.0, "crossing", (2, 3)),
+}
+# one ragged column beyond a block of 64 x 4 cells; three frames for the strided views, five for the iterable whose pictures change
+# their size after the second frame and for `batch` with a ragged last launch
+STRIDED = (64, 65, 0.25, 31, 1.0, "west", 4.0, 12.0, "crossing", (240, 320), 3)
+FIVE_SIZES = ((240, 320), (240, 320), (120, 200), (120, 200), (120, 200))
+CHANGING = (64, 65, 0.25, 32, 1.0, "west", 4.0, 12.0, "crossing", FIVE_SIZES, 5)
+RAGGED = (64, 65, 0.25, 32, 1.0, "west", 4.0, 12.0, "crossing", (120, 200), 5)
+
+
+def make_scene(H, W, du, seed, amp, side, height, back, kind, sizes, count=3):
+    """inputs of a sea of `count` frames whose pictures have the sizes (Ih, Iw) of `sizes`, one for all frames or one per frame:
+    (stokes, Z, XX, YY, Pplane, cam, K), stokes an array where the sizes are equal and a list of count arrays of 3 x Ih x Iw if not"""
+    sizes = [sizes] * count if isinstance(sizes[0], int) else list(sizes)
+    XX, YY = VO.make_grid(H, W, du)
+    cam = VO.camera(XX, YY, side, height, back)
+    Z = np.stack([VO.make_sea(H, W, du, seed, amp, t=0.7 * t) for t in range(count)])
+    if H * W > 100:
+        Z[1, H // 2, W // 3:W // 3 + 3] = np.nan
+    cx, cy = XX.mean(), YY.mean()
+    shift = np.eye(4)
+    shift[0, 3], shift[1, 3] = -cx, -cy
+    Ih, Iw = sizes[0]
+    Pplane = RO.pplane(Iw, Ih, XX - cx, YY - cy, kind) @ shift
+    stokes = [stokes_pictures(count, h, w, seed)[t] for t, (h, w) in enumerate(sizes)]
+    if Ih * Iw > 100:                                   # propagate through the sums of their windows
+        stokes[0][1, Ih // 2, Iw // 2] = np.nan
+        stokes[-1][0, sizes[-1][0] // 2 + 7, sizes[-1][1] // 2 - 9] = np.inf
+    if len(set(sizes)) == 1:
+        stokes = np.stack(stokes)
+    return stokes, Z, XX, YY, Pplane, cam, intrinsics(Iw, Ih)
+
+
+def near_85(want, XX, YY, cam):
+    """how many cells of the oracle's frames have an angle within visibility_oracle.angle_bound of 85 degrees"""
+    near_all = 0
+    for zf in want["zf"]:
+        a64, n = VO.noise(XX, YY, zf, cam[:3, 3])
+        with np.errstate(invalid="ignore"):
+            near_all += int((np.abs(a64 - 85.0) <= VO.angle_bound(a64, n)).sum())
+    return near_all
 
 
 def ulps_f32(a, b):

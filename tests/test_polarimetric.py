@@ -223,3 +223,61 @@ def test_argument_errors():
         P.clip_cube(Z[0], 0.0, 1.0)
     with pytest.raises(ValueError):
         P.zeromean(Z[0])
+
+
+def test_zeromean_oracle_reverse_order():
+    """the mistake the GPU tests must see: the same mean but for the order of its fp64 sum.  On values of six decades alone the two
+    orders differ in the last bits of an fp64 sum, which float32 results do not show; spread_cube's cancelling pairs make them
+    differ in the float32 results at the counts the GPU tests use."""
+    for count in (16, 17, 40):
+        x = PO.spread_cube((count, 5, 257), count)
+        plain = PO.spread_cube((count, 5, 257), count, pairs=False)
+        assert x.dtype == np.float32 and np.abs(plain).max() < 1e6 and 400 < int((np.abs(x) > 1e16).any(0).sum()) < 900
+        assert np.array_equal(np.where(np.abs(x) > 1e16, x, 0).astype(np.float64).sum(0), np.zeros((5, 257)))     # +B and -B cancel
+        x[3, 4, 256] = np.nan
+        fwd, back = PO.zeromean(x), PO.zeromean(x, reverse=True)
+        assert np.array_equal(back, PO.zeromean(x[::-1])[::-1], equal_nan=True)
+        s = 0.0
+        for t in range(count - 1, -1, -1):
+            s += float(x[t, 2, 100])
+        assert np.array_equal(back[:, 2, 100], np.array([np.float32(float(v) - s / count) for v in x[:, 2, 100]], np.float32))
+        differ = int((fwd != back).sum()) - int(np.isnan(fwd).sum())
+        print(f"count {count}: the reverse order changes {differ} of {x.size} cells; without the pairs "
+              f"{int((PO.zeromean(plain) != PO.zeromean(plain, reverse=True)).sum())}")
+        assert differ > x.size // 10 and np.array_equal(np.isnan(fwd), np.isnan(back))
+    one = np.float32([[[3.5]], [[-1.25]]])
+    assert np.array_equal(PO.zeromean(one), PO.zeromean(one, reverse=True))
+
+
+@pytest.mark.parametrize("name", list(PO.SMALL) + ["STRIDED", "CHANGING", "RAGGED"])
+def test_edge_scenes_are_decided(name):
+    """make_scene, near_85 and the scene tables of the edge tests: no cell at or above the camera, none whose angle lies within the
+    visibility map's bound of 85 degrees (the GPU's mask with the rule must then equal the oracle's), something sampled, and for
+    pictures of changing size every frame equal to the oracle of that frame alone, the sums running in frame order."""
+    key = PO.SMALL[name] if name in PO.SMALL else getattr(PO, name)
+    args = PO.make_scene(*key)
+    stokes, Z, XX, YY, Pplane, cam, K = args
+    count = key[10] if len(key) > 10 else 3
+    sizes = [key[9]] * count if isinstance(key[9][0], int) else list(key[9])
+    assert Z.shape == (count,) + key[:2] and Z.dtype == np.float32 and [tuple(np.shape(f)) for f in stokes] == [(3,) + s for s in sizes]
+    assert isinstance(stokes, np.ndarray) == (len(set(sizes)) == 1)
+    want = PO.setup(*args)
+    near = PO.near_85(want, XX, YY, cam)
+    sampled = int((np.nan_to_num(want["S"]) != 0).sum())
+    print(f"{name}: not_up = {want['not_up']}, near_all = {near}, largest angle {np.nanmax(want['angles']):.2f} degrees, "
+          f"{100.0 * want['occlusion'].mean():.2f} % occluded, {sampled} of {want['S'].size} samples neither 0 nor NaN, {int(np.isnan(Z).sum())} NaN heights")
+    assert want["not_up"] == 0 and near == 0 and sampled > 0
+    with np.errstate(invalid="ignore"):
+        brute = sum(int((np.abs(a - 85.0) <= VO.angle_bound(a, VO.noise(XX, YY, zf, cam[:3, 3])[1])).sum()) for a, zf in zip(want["angles"], want["zf"]))
+    assert brute == near
+    Savg, valid = np.zeros(Z.shape[1:] + (3,)), np.zeros(Z.shape[1:])
+    for t in range(count):
+        f = PO.frame(stokes[t], Z[t], XX, YY, Pplane, cam, K)
+        assert f["mapx"].dtype == np.float32
+        assert np.array_equal(f["S"], want["S"][t], equal_nan=True) and np.array_equal(f["occlusion"], want["occlusion"][t])
+        mx, my = RO.project(Z[t], XX, YY, RO.pcam(Pplane, sizes[t][1], sizes[t][0]))
+        assert np.array_equal(f["mapx"], mx, equal_nan=True) and np.array_equal(f["mapy"], my, equal_nan=True)
+        Savg = Savg + PO.nan_to_num(f["S"]).astype(np.float64)
+        valid = valid + (1.0 - f["occlusion"])
+    with np.errstate(all="ignore"):
+        assert np.array_equal(want["Savg"], Savg / valid[..., None], equal_nan=True) and np.array_equal(want["valid"], valid)
