@@ -759,6 +759,42 @@ int wass_radiance_mask_dev(wass_ctx* ctx, const float* d_I, size_t stride_t, siz
                            size_t bg_stride_y, int count, int H, int W, int batch, const float* bgmin, const float* thr,
                            uint8_t* d_mask);
 
+/* ---- Pyramid upsampling: cv::pyrUp of float32 / float64 pictures, and wasspost radiance --upscalefactor N on it
+ * (wasspost.py:840-843, 880-896).
+ *
+ * wass_pyrup_f32 / _f64: every H x W frame (H, W >= 2) becomes 2^levels H x 2^levels W, levels from 1 to 4, each level OpenCV
+ * 4.5.5's scalar pyrUp_ restated from knowledge and not pinned against it: in the element type without contraction, x first (the
+ * two ends of a row as OpenCV writes them: r[0] = s[0]*6 + s[1]*2, r[2w-2] = s[w-2] + s[w-1]*7, r[2w-1] = s[w-1]*8; between
+ * them r[2j] = (s[j-1] + s[j]*6) + s[j+1] and r[2j+1] = (s[j] + s[j+1])*4), then y in the three-tap form on reflected rows (row
+ * -1 is row 1, row H is row H-1), times 1/64.  Strides are in elements, the last axis is contiguous, the frames of out do not
+ * overlap; the _dev forms cannot work in place.  Frames go 8 at a time; every level but the last goes through tightly packed
+ * scratch, and the host forms stage the input and the result as well (wass_pyrup_scratch_bytes says how much and which batch
+ * for elem_size 4 or 8, without a GPU; at most 16 GiB, else the batch is halved).  A side below 2 or levels outside 1 .. 4:
+ * WASS_ERR_INVALID_ARG; a side of the result above 65536: WASS_ERR_UNSUPPORTED.  The host forms return with out filled; the
+ * _dev forms enqueue on the context's stream and synchronise only when they used scratch (levels > 1).
+ *
+ * wass_radiance_up: wass_radiance on the grid and the heights upsampled by `levels` levels: zf = in * (float)datascale in
+ * float32 first (the rule of wass_radiance), then pyrUp of zf in float32 and of XX, YY in fp64 (once per call), then the
+ * projection and the sampler of wass_radiance at every cell of the finer grid.  out is count x 2^levels H x 2^levels W, tightly
+ * packed; everything else as for wass_radiance.  Both forms allocate scratch (wass_radiance_up_scratch_bytes) and return after
+ * a synchronisation. */
+int wass_pyrup_scratch_bytes(int count, int H, int W, int levels, int elem_size, int batch, int host, size_t* bytes, int* batch_used);
+int wass_pyrup_f32(wass_ctx* ctx, const float* in, size_t in_stride_t, size_t in_stride_y, int count, int H, int W, int levels, float* out,
+                   size_t out_stride_t, size_t out_stride_y);
+int wass_pyrup_f32_dev(wass_ctx* ctx, const float* d_in, size_t in_stride_t, size_t in_stride_y, int count, int H, int W, int levels,
+                       float* d_out, size_t out_stride_t, size_t out_stride_y);
+int wass_pyrup_f64(wass_ctx* ctx, const double* in, size_t in_stride_t, size_t in_stride_y, int count, int H, int W, int levels, double* out,
+                   size_t out_stride_t, size_t out_stride_y);
+int wass_pyrup_f64_dev(wass_ctx* ctx, const double* d_in, size_t in_stride_t, size_t in_stride_y, int count, int H, int W, int levels,
+                       double* d_out, size_t out_stride_t, size_t out_stride_y);
+int wass_radiance_up_scratch_bytes(int count, int H, int W, int Ih, int Iw, int levels, int batch, int host, size_t* bytes, int* batch_used);
+int wass_radiance_up(wass_ctx* ctx, const uint8_t* images, size_t image_stride_t, size_t image_stride_y, int Ih, int Iw, const float* in,
+                     size_t stride_t, size_t stride_y, int count, int H, int W, const double* XX, const double* YY, const double Pcam[12],
+                     double datascale, int batch, int levels, float* out);
+int wass_radiance_up_dev(wass_ctx* ctx, const uint8_t* d_images, size_t image_stride_t, size_t image_stride_y, int Ih, int Iw,
+                         const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, const double* d_XX,
+                         const double* d_YY, const double Pcam[12], double datascale, int batch, int levels, float* d_out);
+
 /* ---- Polarimetric set-up of the gridded cube: wasspost polarimetric_setup (wasspost.py:627-805), clip and zeromean as array
  * functions.
  *

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Pin the oracle to the real OpenCV -- for a machine that HAS OpenCV (the build image does not).
 
-    python scripts/pin_with_opencv.py            # writes tests/golden/sgbm_opencv.npz and tests/golden/opencv_other.npz
+    python scripts/pin_with_opencv.py            # writes tests/golden/sgbm_opencv.npz, opencv_other.npz and pyrup_pin.npz
     python -m pytest tests/test_oracle_pin.py    # compares oracle/*.c with them (skipped while the files are absent)
+    python -m pytest tests/test_pyramid.py       # test_opencv_pin compares tests/pyramid_oracle.py with pyrup_pin.npz
 
 One run pins every restatement of an OpenCV routine the hot path and its neighbours rest on: cv::StereoSGBM (rows a2-a6,
 below), and -- other_cases() / run_other() -- stereoRectify + initUndistortRectifyMap + remap, warpPerspective (f1),
-undistort and CLAHE (f2), resize, filterSpeckles and the Sobel / connected-component extraction (a9).
+undistort and CLAHE (f2), resize, filterSpeckles and the Sobel / connected-component extraction (a9); and -- run_pyrup() --
+cv.pyrUp of float32 and float64 pictures (wasspost radiance --upscalefactor, restated in wass_amd/csrc/pyramid.hip and
+tests/pyramid_oracle.py).
 
 The reference computes its disparity with cv::StereoSGBM (wass_stereo/wass_stereo.cpp:775-782, compute() at :837; OpenCV
 4.5.5 per meta.yaml:12-13).  OpenCV is neither vendored in the reference tree nor installed in the image this repository
@@ -173,11 +176,25 @@ def run_other(cv2, c):
     raise ValueError(k)
 
 
+def run_pyrup(cv2):
+    """cv.pyrUp of the pictures tests/test_pyramid.py holds the numpy restatement to (pyramid_oracle.pin_inputs): name__src, name__dst"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pyramid_oracle
+    store, names = {}, []
+    for name, src in pyramid_oracle.pin_inputs().items():
+        store[f"{name}__src"] = src
+        store[f"{name}__dst"] = cv2.pyrUp(src)
+        names.append(name)
+    store["names"] = np.array(names)
+    return store
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "sgbm_opencv.npz"))
     ap.add_argument("--out-other", default=os.path.join(ROOT, "tests", "golden", "opencv_other.npz"),
                     help="rectification / undistort / CLAHE / resize / filterSpeckles / component vectors")
+    ap.add_argument("--out-pyrup", default=os.path.join(ROOT, "tests", "golden", "pyrup_pin.npz"), help="cv.pyrUp vectors")
     args = ap.parse_args()
     try:
         import cv2
@@ -216,6 +233,10 @@ def main():
     other["names"] = np.array(onames)
     np.savez_compressed(args.out_other, **other)
     print(f"wrote {args.out_other}: {len(onames)} cases (rectify, warp, undistort, CLAHE, resize, filterSpeckles, component)")
+    pyr = run_pyrup(cv2)
+    pyr["opencv_version"] = np.array(ver)
+    np.savez_compressed(args.out_pyrup, **pyr)
+    print(f"wrote {args.out_pyrup}: {len(pyr['names'])} pictures through cv.pyrUp")
 
 
 if __name__ == "__main__":

@@ -255,6 +255,14 @@ SYMBOLS = {
     "wass_radiance_hist_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wass_radiance_mask": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
     "wass_radiance_mask_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wass_pyrup_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_pyrup_f32": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_pyrup_f32_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_pyrup_f64": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_pyrup_f64_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_radiance_up_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_radiance_up": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, _i, _i, _vp]),
+    "wass_radiance_up_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, _i, _i, _vp]),
     "wass_bilinear_table_f32": (_i, [_vp]),
     "wass_remap_linear_f32": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _i, _i, _vp]),
     "wass_remap_linear_f32_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _i, _i, _vp]),

@@ -334,5 +334,8 @@ int launch_median_full(wass_ctx* c, const SgmDims& d, int16_t* d_padded_out);   
 // rectify.hip: cv::undistort's normalised coordinates of camera (K, w, h), cached per context; *d_xy = w column values, then h row values
 int undistort_tables(wass_ctx* c, const double* K, int w, int h, const double** d_xy);
 int ensure_bilinear_tab(wass_ctx* c);         // polarimetric.hip: the 1024 x 2 x 2 float32 table in c->bilinear_tab
+// radiance.hip: enqueues k_radiance for nb frames of device memory (heights times `scale`); pyramid.hip samples its upsampled cube with it
+int radiance_enqueue(wass_ctx* c, const uint8_t* d_img, size_t img_t, size_t img_y, int Ih, int Iw, const float* d_z, size_t st, size_t sy, int nb,
+                     int H, int W, const double* d_XX, const double* d_YY, const double* Pcam, float scale, float* d_out, hipStream_t s);
 
 }  // namespace wass

@@ -353,6 +353,27 @@ static int rad_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, siz
     return rc;
 }
 
+// k_radiance for nb frames of device memory on stream s, for pyramid.hip: the heights arrive as the caller formed them and are
+// multiplied by `scale` (1 leaves them as they are)
+int radiance_enqueue(wass_ctx* c, const uint8_t* d_img, size_t img_t, size_t img_y, int Ih, int Iw, const float* d_z, size_t st, size_t sy, int nb,
+                     int H, int W, const double* d_XX, const double* d_YY, const double* Pcam, float scale, float* d_out, hipStream_t s)
+{
+    int rc = rad_picture_ok(c, Iw, Ih, img_y);
+    if (rc) return rc;
+    if (nb < 1 || nb > RAD_MAX_BATCH || H < 1 || W < 1 || H > 65536 || W > 65536 || (size_t)H * W > 0x7fffff00u || sy < (size_t)W)
+        return set_err(c, WASS_ERR_INVALID_ARG, "%d frames of %d x %d", nb, H, W);
+    rc = ensure_lanczos_tab(c);
+    if (rc) return rc;
+    RadProj P;
+    for (int k = 0; k < 12; ++k) P.p[k] = Pcam[k];
+    P.scale = scale;
+    const dim3 block(RAD_BX, RAD_BY), grid((W + RAD_BX - 1) / RAD_BX, (H + RAD_BY - 1) / RAD_BY, nb);
+    hipLaunchKernelGGL(k_radiance, grid, block, 0, s, d_img, img_t, img_y, Iw, Ih, d_z, (long long)st, (long long)sy, H, W, d_XX, d_YY, P, d_out,
+                       (const short*)c->lanczos_tab.p);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WASS_OK : set_err(c, WASS_ERR_DEVICE, "radiance: %s", hipGetErrorString(e));
+}
+
 // ---------------------------------------------------------------- bgimage: the box filter along time
 // `reflect` of scipy.ndimage (d c b a | a b c d | d c b a): phase a in [0, 2 n) stands for index a or 2 n - 1 - a
 struct BgPhase {

@@ -739,26 +739,29 @@ def radiance_scratch_bytes(count: int, H: int, W: int, Ih: int, Iw: int, batch: 
     return b.value, n.value
 
 
-def _radiance_chunk(ctx, imgs, data, XX, YY, dgrid, pcam, datascale, batch, out):
-    """frames of one picture size: imgs n x Ih x Iw (host array or device tensor), data and out n x H x W on the cube's side"""
+def _radiance_chunk(ctx, imgs, data, XX, YY, dgrid, pcam, datascale, batch, out, levels=0):
+    """frames of one picture size: imgs n x Ih x Iw (host array or device tensor), data n x H x W and out n x 2^levels H x 2^levels W
+    on the cube's side"""
     n, H, W = (int(v) for v in data.shape)
     Ih, Iw = int(imgs.shape[1]), int(imgs.shape[2])
     P = np.ascontiguousarray(pcam[:3], np.float64)
+    name, up = ("wass_radiance_up", (int(levels),)) if levels else ("wass_radiance", ())
     if _is_device(data):
         import torch
         if not _is_device(imgs):
             imgs = torch.from_numpy(np.ascontiguousarray(imgs, np.uint8)).to(data.device)
         imgs = imgs.to(torch.uint8).contiguous()
         torch.cuda.current_stream(data.device).synchronize()
-        ctx._check(ctx._lib.wass_radiance_dev(ctx._h, imgs.data_ptr(), Ih * Iw, Iw, Ih, Iw, data.data_ptr(), data.stride(0), data.stride(1), n, H, W,
-                                              dgrid[0].data_ptr(), dgrid[1].data_ptr(), P.ctypes.data, float(datascale), int(batch), out.data_ptr()))
+        ctx._check(getattr(ctx._lib, name + "_dev")(ctx._h, imgs.data_ptr(), Ih * Iw, Iw, Ih, Iw, data.data_ptr(), data.stride(0), data.stride(1),
+                                                    n, H, W, dgrid[0].data_ptr(), dgrid[1].data_ptr(), P.ctypes.data, float(datascale), int(batch),
+                                                    *up, out.data_ptr()))
         ctx.synchronize()
         return
     if _is_device(imgs):
         imgs = imgs.cpu().numpy()
     imgs = np.ascontiguousarray(imgs, np.uint8)
-    ctx._check(ctx._lib.wass_radiance(ctx._h, imgs.ctypes.data, Ih * Iw, Iw, Ih, Iw, data.ctypes.data, data.strides[0] // 4, data.strides[1] // 4, n, H, W,
-                                      XX.ctypes.data, YY.ctypes.data, P.ctypes.data, float(datascale), int(batch), out.ctypes.data))
+    ctx._check(getattr(ctx._lib, name)(ctx._h, imgs.ctypes.data, Ih * Iw, Iw, Ih, Iw, data.ctypes.data, data.strides[0] // 4, data.strides[1] // 4,
+                                       n, H, W, XX.ctypes.data, YY.ctypes.data, P.ctypes.data, float(datascale), int(batch), *up, out.ctypes.data))
 
 
 def radiance(images, data, XX, YY, Pplane, datascale: float = 1e-3, upscalefactor: int = 1, ctx: Context | None = None, out=None,
@@ -768,14 +771,23 @@ def radiance(images, data, XX, YY, Pplane, datascale: float = 1e-3, upscalefacto
     count x H x W float32 cube in the unit that `datascale` turns into metres, a host array or memmap (host result) or a device
     tensor (device result); XX, YY the H x W grid in metres; Pplane the 4 x 4 P{cam}plane matrix.  Per cell the height is
     data * float32(datascale) in float32, the projection ((P0 X + P1 Y) + P2 z) + P3 per row in fp64, the maps its quotients cast
-    to float32, and the sampler remap_lanczos4.  Cells whose height is NaN, or that project outside the picture, are 0."""
+    to float32, and the sampler remap_lanczos4.  Cells whose height is NaN, or that project outside the picture, are 0.
+    `upscalefactor` must be 1 here: the finer grid is radiance_upscaled's."""
     if int(upscalefactor) != 1:
-        raise NotImplementedError("upscalefactor other than 1 needs cv.pyrUp, which is not implemented")
+        raise NotImplementedError("radiance samples the grid as it is: for upscalefactor other than 1 call radiance_upscaled")
+    return _radiance_frames(images, data, XX, YY, Pplane, datascale, 0, ctx, out, batch)
+
+
+def _radiance_frames(images, data, XX, YY, Pplane, datascale, levels, ctx, out, batch):
+    """radiance and radiance_upscaled: the checks, the outputs and the chunks of pictures of one size; `levels` of pyrUp (0: none)"""
     if len(data.shape) != 3:
         raise ValueError("data must be count x H x W")
     count, H, W = (int(v) for v in data.shape)
     if count < 1 or H < 1 or W < 1:
         raise ValueError("no frames")
+    if levels and (H < 2 or W < 2):
+        raise ValueError("H and W must be at least 2 to be upsampled")
+    oshape = (count, H << levels, W << levels)
     XX, YY = np.ascontiguousarray(XX, np.float64), np.ascontiguousarray(YY, np.float64)
     if XX.shape != (H, W) or YY.shape != (H, W):
         raise ValueError(f"XX and YY must be {H} x {W}, like a frame")
@@ -796,19 +808,19 @@ def radiance(images, data, XX, YY, Pplane, datascale: float = 1e-3, upscalefacto
         if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
             data = data.to(torch.float32).contiguous()
         if out is None:
-            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
-        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 device tensor of the input's shape")
+            out = torch.empty(oshape, dtype=torch.float32, device=data.device)
+        elif not _is_device(out) or tuple(out.shape) != oshape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 device tensor of the result's shape")
         dgrid = (torch.from_numpy(XX).to(data.device), torch.from_numpy(YY).to(data.device))
     else:
         data = _host_f32_rows(data)
         if out is None:
-            out = np.empty((count, H, W), np.float32)
-        elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous float32 host array of the input's shape")
+            out = np.empty(oshape, np.float32)
+        elif not isinstance(out, np.ndarray) or out.shape != oshape or out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous float32 host array of the result's shape")
     if whole:
         pcam = radiance_pcam(Pplane, int(images.shape[2]), int(images.shape[1]))
-        _radiance_chunk(ctx, images, data, XX, YY, dgrid, pcam, datascale, batch, out)
+        _radiance_chunk(ctx, images, data, XX, YY, dgrid, pcam, datascale, batch, out, levels)
         return out
     t0, pending = 0, []
 
@@ -817,7 +829,7 @@ def radiance(images, data, XX, YY, Pplane, datascale: float = 1e-3, upscalefacto
         if pending:
             stack = np.stack(pending)
             pcam = radiance_pcam(Pplane, stack.shape[2], stack.shape[1])
-            _radiance_chunk(ctx, stack, data[t0:t0 + len(pending)], XX, YY, dgrid, pcam, datascale, batch, out[t0:t0 + len(pending)])
+            _radiance_chunk(ctx, stack, data[t0:t0 + len(pending)], XX, YY, dgrid, pcam, datascale, batch, out[t0:t0 + len(pending)], levels)
             t0 += len(pending)
             pending = []
 
@@ -835,6 +847,129 @@ def radiance(images, data, XX, YY, Pplane, datascale: float = 1e-3, upscalefacto
     if t0 != count:
         raise ValueError(f"{t0} pictures for {count} frames")
     return out
+
+
+# ---- pyramid upsampling: cv.pyrUp, and wasspost radiance --upscalefactor N on it (wasspost.py:840-843, 880-896) --------------------
+PYR_MAX_LEVELS = 4
+
+
+def pyr_up_scratch_bytes(count: int, H: int, W: int, levels: int = 1, dtype=np.float32, batch: int = 8, host: bool = True):
+    """(bytes of device scratch, frames per launch) of one pyr_up call; no GPU needed.  With e the element size, b the frames per
+    launch and every term rounded up to 256 bytes: the levels below the last, sum over l = 1 .. levels - 1 of b 4^l H W e, and from
+    the host also the input b H W e and the result b 4^levels H W e.  b is `batch` (pyr_up itself uses 8), at most count, halved
+    until the sum is at most 16 GiB."""
+    from . import _lib
+    b, n = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_pyrup_scratch_bytes(int(count), int(H), int(W), int(levels), int(np.dtype(dtype).itemsize), int(batch), int(bool(host)),
+                                              C.byref(b), C.byref(n))
+    if rc:
+        raise ValueError(f"wass_pyrup_scratch_bytes({count}, {H}, {W}, levels {levels}, {np.dtype(dtype)}, batch {batch}): error {rc}")
+    return b.value, n.value
+
+
+def _device_span(t):
+    """[first byte, one past the last byte) of a device tensor with positive strides"""
+    n = 1 + sum((int(s) - 1) * int(st) for s, st in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
+def pyr_up(a, levels: int = 1, ctx: Context | None = None, out=None):
+    """cv.pyrUp applied `levels` times (1 to 4): an H x W picture or a count x H x W cube of them, float32 or float64, H and W at
+    least 2, becomes 2^levels H x 2^levels W per frame.  A host array or memmap gives a host array, a device tensor a device
+    tensor, of the input's dtype; a strided view passes as it is where its last axis is contiguous, and so does `out`, which must
+    not overlap the input.  Each level is OpenCV 4.5.5's scalar pyrUp restated (weights 1 4 6 4 1 per axis, x first, the sums
+    in the element type in the order DESIGN.md states, times 1/64): bit for bit tests/pyramid_oracle.py, not pinned against
+    OpenCV itself.  NaN and infinite cells spread over the cells they weigh on."""
+    levels = int(levels)
+    if not 1 <= levels <= PYR_MAX_LEVELS:
+        raise ValueError(f"levels must be from 1 to {PYR_MAX_LEVELS}")
+    if len(a.shape) not in (2, 3):
+        raise ValueError("a picture is H x W, a cube count x H x W")
+    single = len(a.shape) == 2
+    dev = _is_device(a)
+    if dev:
+        import torch
+        kinds = {torch.float32: ("f32", 4), torch.float64: ("f64", 8)}
+    else:
+        if not isinstance(a, np.ndarray):
+            a = np.asarray(a)
+        kinds = {np.dtype(np.float32): ("f32", 4), np.dtype(np.float64): ("f64", 8)}
+    if a.dtype not in kinds:
+        raise ValueError(f"pyr_up takes float32 or float64, not {a.dtype}")
+    kind, e = kinds[a.dtype]
+    src = a[None] if single else a
+    count, H, W = (int(v) for v in src.shape)
+    if count < 1:
+        raise ValueError("no frames")
+    if H < 2 or W < 2:
+        raise ValueError("H and W must be at least 2")
+    if max(H, W) << levels > 65536:
+        raise ValueError("a side of the result is above 65536")
+    oshape = (count, H << levels, W << levels)
+    if out is not None and (_is_device(out) != dev or out.dtype != a.dtype or tuple(out.shape) != (oshape[1:] if single else oshape)):
+        raise ValueError(f"out must be on the input's side, of its dtype and {' x '.join(str(v) for v in (oshape[1:] if single else oshape))}")
+    if dev:
+        if src.stride(2) != 1 or (count > 1 and src.stride(0) <= 0) or src.stride(1) <= 0:      # (the stride of an axis of 1 says nothing)
+            src = src.contiguous()
+        dst = torch.empty(oshape, dtype=a.dtype, device=a.device) if out is None else (out[None] if single else out)
+        if dst.stride(2) != 1 or dst.stride(1) < oshape[2] or (count > 1 and dst.stride(0) < (oshape[1] - 1) * dst.stride(1) + oshape[2]):
+            raise ValueError("out must have a contiguous last axis and rows and frames that do not overlap")
+        (a0, a1), (b0, b1) = _device_span(src), _device_span(dst)
+        if a0 < b1 and b0 < a1:
+            raise ValueError("out must not overlap the input")
+        if ctx is None:
+            ctx = Context(0)
+        torch.cuda.current_stream(a.device).synchronize()
+        ctx._check(getattr(ctx._lib, f"wass_pyrup_{kind}_dev")(ctx._h, src.data_ptr(), src.stride(0), src.stride(1), count, H, W, levels,
+                                                               dst.data_ptr(), dst.stride(0), dst.stride(1)))
+        ctx.synchronize()
+    else:
+        if src.strides[2] != e or src.strides[1] % e or src.strides[1] <= 0 or (count > 1 and (src.strides[0] % e or src.strides[0] <= 0)):
+            src = np.ascontiguousarray(src)
+        dst = np.empty(oshape, a.dtype) if out is None else (out[None] if single else out)
+        if dst.strides[2] != e or dst.strides[1] % e or dst.strides[1] < oshape[2] * e \
+                or (count > 1 and (dst.strides[0] % e or dst.strides[0] < (oshape[1] - 1) * dst.strides[1] + oshape[2] * e)):
+            raise ValueError("out must have a contiguous last axis and rows and frames that do not overlap")
+        if np.shares_memory(src, dst):
+            raise ValueError("out must not overlap the input")
+        if ctx is None:
+            ctx = Context(0)
+        ctx._check(getattr(ctx._lib, f"wass_pyrup_{kind}")(ctx._h, src.ctypes.data, src.strides[0] // e, src.strides[1] // e, count, H, W, levels,
+                                                           dst.ctypes.data, dst.strides[0] // e, dst.strides[1] // e))
+    if out is not None:
+        return out
+    return dst[0] if single else dst
+
+
+def radiance_upscaled_scratch_bytes(count: int, H: int, W: int, Ih: int, Iw: int, upscalefactor: int = 2, batch: int = 8, host: bool = True):
+    """(bytes of device scratch, frames per launch) of one radiance_upscaled call over pictures of one size; no GPU needed.  With
+    L = upscalefactor - 1 levels, b frames per launch and every term rounded up to 256 bytes: per call the upsampled grid
+    2 x 4^L H W 8 and its lower levels, sum over l = 1 .. L - 1 of 4^l H W 8; per launch the scaled heights b H W 4, their lower
+    levels, sum of b 4^l H W 4, and the upsampled heights b 4^L H W 4.  From the host also XX and YY 2 x H W 8, the pictures
+    b Ih Iw, the heights b H W 4 and the result b 4^L H W 4.  b is `batch`, at most count, halved until the sum is at most 16 GiB.
+    upscalefactor 1 is radiance_scratch_bytes."""
+    levels = int(upscalefactor) - 1
+    if levels == 0:
+        return radiance_scratch_bytes(count, H, W, Ih, Iw, batch, host)
+    from . import _lib
+    b, n = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_radiance_up_scratch_bytes(int(count), int(H), int(W), int(Ih), int(Iw), levels, int(batch), int(bool(host)), C.byref(b),
+                                                    C.byref(n))
+    if rc:
+        raise ValueError(f"wass_radiance_up_scratch_bytes({count}, {H}, {W}, pictures {Ih} x {Iw}, levels {levels}, batch {batch}): error {rc}")
+    return b.value, n.value
+
+
+def radiance_upscaled(images, data, XX, YY, Pplane, upscalefactor: int = 2, datascale: float = 1e-3, ctx: Context | None = None, out=None,
+                      batch: int = 8):
+    """wasspost radiance --upscalefactor N as a function: the radiance on a grid finer than the cube's.  `upscalefactor` has the
+    reference's meaning: the grid XX, YY (fp64) and every frame's heights (float32, already multiplied by float32(datascale)) go
+    through pyr_up upscalefactor - 1 times, so 2 doubles H and W, 3 quadruples them, up to 5; 1 is radiance itself.  The result is
+    float32 [count, 2^(N-1) H, 2^(N-1) W].  images, data, XX, YY, Pplane, out, batch and the host / device split are radiance's."""
+    levels = int(upscalefactor) - 1
+    if not 0 <= levels <= PYR_MAX_LEVELS:
+        raise ValueError(f"upscalefactor must be from 1 to {PYR_MAX_LEVELS + 1}")
+    return _radiance_frames(images, data, XX, YY, Pplane, datascale, levels, ctx, out, batch)
 
 
 def bgimage_scratch_bytes(count: int, H: int, W: int, filtersize: int = 2000, slab_rows: int = 0, host: bool = True):
