@@ -330,14 +330,19 @@ int wass_mesh_upload(wass_ctx* ctx, int width, int height, const uint8_t* valid,
 /* ------------------------------------------------------------------------
  * PovMesh stages, rows a14-a20 (wass_stereo/PovMesh.cpp).
  * ------------------------------------------------------------------------ */
-/* compute_zgap_percentile (:888-926); exact order statistic; NaN if no gaps */
+/* compute_zgap_percentile (:888-926); exact order statistic; NaN if no gaps (always so for width < 3 or height < 2).
+ * Undefined for NaN heights: the reference sorts them. */
 int wass_mesh_zgap_percentile(wass_ctx* ctx, wass_mesh* m, double percentile, double* out, uint64_t* n_gaps);
 /* cluster_biggest_connected_component (:929-987): keep the largest 4-connected
  * component of valid points whose |dz| < zgap (first in column-major order on ties) */
 int wass_mesh_keep_biggest_component(wass_ctx* ctx, wass_mesh* m, double zgap, uint64_t* size_out);
 /* ransac_find_plane (:665-777).  uv_triplets[rounds][6] = {u1,v1,u2,v2,u3,v3}
  * drawn by the caller with rand() as in :680-691 (wass_ransac_sample does that).
- * Returns WASS_OK with *found = 0 when best < width*height/10 (:773). */
+ * Returns WASS_OK with *found = 0 when best < width*height/10 (:773).
+ * rounds: 1 .. 1800, more is WASS_ERR_UNSUPPORTED (also in wass_mesh_fit_plane and wass_mesh_finish_frame_async*); a sample
+ * outside the grid is WASS_ERR_INVALID_ARG.  A valid point with a NaN coordinate is never an inlier (fabs(NaN) < thr is false),
+ * neither here nor in wass_mesh_crop_plane, which drops it; a triple that spans no plane (two samples on one pixel, collinear
+ * points) gives a NaN candidate that counts 0. */
 int wass_ransac_sample(int width, int height, int rounds, int32_t* uv_triplets);
 /* The same draw from a PRIVATE generator that restates glibc's srand(seed) + rand(): what the reference gets for
  * RANDOM_SEED = seed (wass_stereo.cpp:1864-1872; RANSAC is its only rand() consumer), independent of whoever else in

@@ -564,6 +564,7 @@ __global__ void __launch_bounds__(256) k_ransac_score(const uint8_t* __restrict_
     unsigned long long vmask[PTS];
     double mnx = 1e300, mny = 1e300, mnz = 1e300, mxx = -1e300, mxy = -1e300, mxz = -1e300, m = 0.0;
     unsigned int nvalid = 0;
+    bool nan = false;
 #pragma unroll
     for (int k = 0; k < PTS; ++k) {
         const int row = row0 + k;
@@ -576,6 +577,8 @@ __global__ void __launch_bounds__(256) k_ransac_score(const uint8_t* __restrict_
             mnx = fmin(mnx, x); mxx = fmax(mxx, x); mny = fmin(mny, y); mxy = fmax(mxy, y); mnz = fmin(mnz, z); mxz = fmax(mxz, z);
             m = fmax(m, fmax(fabs(x), fmax(fabs(y), fabs(z))));
         }
+        const double sum = (x + y) + z;                           // NaN if a coordinate is (fmin / fmax drop it from the box)
+        nan = nan || sum != sum;
         px[k / 2][k % 2] = (float)x; py[k / 2][k % 2] = (float)y; pz[k / 2][k % 2] = (float)z;
     }
     if (nvalid) {                                                 // wave-uniform
@@ -589,6 +592,9 @@ __global__ void __launch_bounds__(256) k_ransac_score(const uint8_t* __restrict_
         const double ex = (0.5 * (mxx - mnx)) * (1.0 + 0x1p-50) + 0x1p-1000, ey = (0.5 * (mxy - mny)) * (1.0 + 0x1p-50) + 0x1p-1000,
                      ez = (0.5 * (mxz - mnz)) * (1.0 + 0x1p-50) + 0x1p-1000;
         const float up = 1.0f + 0x1p-20f, G = 0x1p-21f;
+        // a valid point with a NaN coordinate fails the reference's test but is in nvalid and not in the box: "all inside" is then
+        // not for the bound to decide (the point by point passes below leave it out)
+        const bool box_ok = __builtin_amdgcn_ballot_w64(nan) == 0ull;
         const float Mg = (float)m * up * G, thr_f = (float)thr, thr_g = (float)fabs(thr) * up * G;
         // 64 planes at a time: lane l takes the patch test for plane r0 + l (so the test costs the wave ~2 cycles per plane),
         // the planes it cannot decide are then scored point by point, one after the other
@@ -601,7 +607,7 @@ __global__ void __launch_bounds__(256) k_ransac_score(const uint8_t* __restrict_
                 const double tc = fabs(a * cx + b * cy + c * cz + d);
                 const double rad = fabs(a) * ex + fabs(b) * ey + fabs(c) * ez;
                 const double slack = 0x1p-40 * (fabs(a * cx) + fabs(b * cy) + fabs(c * cz) + fabs(d) + rad + fabs(thr));
-                dec = (tc + rad + slack < thr) ? 1 : ((tc - rad - slack >= thr) ? 2 : 0);
+                dec = (box_ok && tc + rad + slack < thr) ? 1 : ((tc - rad - slack >= thr) ? 2 : 0);
             }
             unsigned int mine = dec == 1 ? nvalid : 0u;           // lane l holds the count of round r0 + l
             unsigned long long und = __builtin_amdgcn_ballot_w64(dec == 0);
@@ -1643,7 +1649,8 @@ int wass_mesh_keep_biggest_component(wass_ctx* c, wass_mesh* m, double zgap, uin
 // copy from pageable or stack memory is only safe if the runtime happens to stage it before returning; these copies
 // are enqueued and never waited for, so their sources must outlive the call: [DevState init | limits init | uv samples].
 constexpr size_t STAGE_UV_OFF = 4096 + NSLOT * 6 * 8;
-constexpr size_t STAGE_UV_BYTES = 1800 * 24;                  // PLANE_RANSAC_ROUNDS <= 1800 (LDS limit of k_ransac_score)
+constexpr int RANSAC_MAX_ROUNDS = 1800;                       // PLANE_RANSAC_ROUNDS: k_ransac_score keeps 36 bytes of LDS per round (64 KB)
+constexpr size_t STAGE_UV_BYTES = (size_t)RANSAC_MAX_ROUNDS * 24;
 constexpr size_t STAGE_BYTES = STAGE_UV_OFF + 2 * STAGE_UV_BYTES;   // two areas, alternated: the host never waits for the previous frame's copy
 static int host_stage(wass_ctx* c, unsigned char** out)
 {
@@ -1807,7 +1814,8 @@ int wass_mesh_ransac_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rou
                        (const int32_t*)duv, rounds, cand, counts, (unsigned long long*)nullptr, 0);
     constexpr int PTS = 8;
     const size_t lds = (size_t)rounds * (32 + 4);
-    if (lds > 64 * 1024) return set_err(c, WASS_ERR_UNSUPPORTED, "PLANE_RANSAC_ROUNDS %d too large (max 1800)", rounds);
+    // (the limit the message states, not the 1820 rounds that would still fit into LDS: the pinned sample stage holds 1800)
+    if (rounds > RANSAC_MAX_ROUNDS || lds > 64 * 1024) return set_err(c, WASS_ERR_UNSUPPORTED, "PLANE_RANSAC_ROUNDS %d too large (max 1800)", rounds);
     hipLaunchKernelGGL(k_ransac_score<PTS>, dim3((m->w + 255) / 256, (m->h + PTS - 1) / PTS), dim3(256), lds, c->ts(),
                        m->valid, m->x, m->y, m->z, m->w, m->h, (const PlaneCand*)cand, rounds, thr, counts);
     std::vector<PlaneCand> hc(rounds);
@@ -1947,7 +1955,8 @@ static int enqueue_fit_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int r
     unsigned long long* kept2 = kept1 + NSLOT;
     constexpr int PTS = 8;
     const size_t lds = (size_t)rounds * (32 + 4);
-    if (lds > 64 * 1024) return set_err(c, WASS_ERR_UNSUPPORTED, "PLANE_RANSAC_ROUNDS %d too large (max 1800)", rounds);
+    // (the limit the message states, not the 1820 rounds that would still fit into LDS: the pinned sample stage holds 1800)
+    if (rounds > RANSAC_MAX_ROUNDS || lds > 64 * 1024) return set_err(c, WASS_ERR_UNSUPPORTED, "PLANE_RANSAC_ROUNDS %d too large (max 1800)", rounds);
     hipStream_t s = c->ts();
     {   // the caller's sample array may be pageable and short-lived: go through the pinned stage (the previous frame's
         // copy out of it was enqueued a whole frame ago; wait for it before overwriting)
