@@ -598,6 +598,27 @@ int wass_grid_seq_finish(wass_grid_seq* seq, int force_zero_mean, wass_grid_seq_
 int wass_grid_seq_zero_mean_dev(wass_grid_seq* seq, float* d_z_mm, int n_frames);
 void wass_grid_seq_destroy(wass_grid_seq* seq);
 
+/* Grid set-up (wassgridsurface.py:57-231, `--action setup`): the one step with real work in it, np.quantile over the heights of
+ * the first frame's aligned cloud (:122-123), as exact order statistics on the device (grid_setup.hip).
+ * wass_quantiles_f64_dev: out[i] = np.quantile(values, q[i]) (method "linear") over n doubles of device memory, i < nq, 1 <= nq <= 8,
+ * every q[i] in [0, 1] (else WASS_ERR_INVALID_ARG).  Each double becomes an order-preserving 64-bit key; an MSD radix select in
+ * 11-bit digits finds the order statistic a[lo] of every q in the same six passes, a[hi] is a[lo] where ties reach past lo and
+ * the smallest key above a[lo] otherwise (one more pass); every decision stays on the device.  numpy's virtual index
+ * (n - 1) * q and its _lerp (with the t >= 0.5 branch) are restated in fp64 on the host from those 2 nq values.  -0.0 sorts below
+ * +0.0 (numpy leaves their order open; the values agree).  One NaN among the values makes every out[i] NaN, as np.quantile does.
+ * n == 0: every out[i] is NaN and the call returns WASS_OK.
+ * wass_mesh_aligned_z_quantiles: the same over the valid points of a mesh, of
+ *     z = -(((R[6] x + R[7] y) + R[8] zc) + T[2]) * baseline
+ * in fp64, every product and sum rounded on its own (no FMA): the third row of align_on_sea_plane_RT (wass_utils.py:54-61)
+ * times the baseline.  R: 9 row-major doubles, T: 3.  n_points (may be NULL) receives the number of valid points; a mesh without
+ * one gives NaN and WASS_OK.  The coordinates of invalid points are never read into the result.
+ * Both return after a synchronisation.  wass_quantiles_launch_shape: the elements one workgroup takes per sweep and the elements
+ * one launch takes per sweep (longer arrays are walked in several sweeps by the same launch), for tests that want those edges. */
+int wass_quantiles_f64_dev(wass_ctx* ctx, const double* d_values, size_t n, const double* q, int nq, double* out);
+int wass_mesh_aligned_z_quantiles(wass_ctx* ctx, const wass_mesh* m, const double R[9], const double T[3], double baseline,
+                                  const double* q, int nq, double* out, uint64_t* n_points);
+void wass_quantiles_launch_shape(int* per_block, int* per_launch);
+
 /* ---- wave spectra of the gridded cube: postproc/wasspost/spectra.py as array functions ----------
  * compute_3D_spectrum (:53-171): Welch's method over 3-D segments of nt x ny x nx cells.  The host computes axes, windows
  * and the scale (wass_amd/postproc.py); one segment per push:

@@ -219,6 +219,10 @@ SYMBOLS = {
     "wass_grid_seq_finish": (_i, [_vp, _i, C.POINTER(GridSeqStats), _vp, _vp, _vp, _vp]),
     "wass_grid_seq_zero_mean_dev": (_i, [_vp, _vp, _i]),
     "wass_grid_seq_destroy": (None, [_vp]),
+    "wass_quantiles_f64_dev": (_i, [_vp, _vp, _sz, C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
+    "wass_mesh_aligned_z_quantiles": (_i, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double), _i,
+                                           C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "wass_quantiles_launch_shape": (None, [C.POINTER(_i), C.POINTER(_i)]),
     "wass_spec3d_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
     "wass_spec3d_create": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp)]),
     "wass_spec3d_push": (_i, [_vp, _vp, _sz, _sz, C.c_double]),

@@ -11,6 +11,11 @@ grid_sequence(wass_frames, gridsetup, ...) is the tool's `--action grid` for `--
 file output: every frame's mesh_cam.xyzC binned, solved (several frames per set of launches), masked, median filtered (mf),
 turned into the millimetre cube, with the sequence's zmin / zmax / zmean, the per-point mean and the force_zero_mean pass.
 load_camera_mesh(path) is the reference's mesh_cam.xyzC reader (wass_utils.py:22-35).
+
+setup_grid(wdir, meanplane, baseline, ...) is the tool's `--action setup` (wassgridsurface.py:57-231): the dict of its config.mat
+from the first frame of a sequence, with the quantiles of the aligned heights taken on the GPU; generate_gridconfig / read_gridconfig
+are `--action generateconfig` and the reader of that file.  `python -m wass_amd.gridding WORKDIR OUTDIR --action ...` runs them
+with the reference's option names.  The plots (area_grid.png, grid_projected_cam0.jpg), the JPEG and the NetCDF file stay out.
 """
 from __future__ import annotations
 
@@ -20,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from .stereo import Context, GridSequence, grid_setup
+from .stereo import Context, GridSequence, grid_setup, planes_mean_accumulate, planes_mean_finish
 
 _DEFAULTS = {"Nfreqs": 150, "MAX_ITERS": 500, "TOLERANCE_CHANGE": 1e-4, "REGULARIZER_ALPHA": 8e-7, "LEARNING_RATE": 5.0}
 
@@ -175,3 +180,323 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
     return GridSequenceResult(Z=out, time=idx / fps if fps > 0 else np.zeros(count), workdir=workdir, zmin=st["zmin"], zmax=st["zmax"],
                               zmean=st["zmean"], mean_perpoint_mm=st["mean_perpoint_mm"], dct_info=infos, empty_frames=empty,
                               frame_mean=st["frame_mean"], frame_min=st["frame_min"], frame_max=st["frame_max"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- grid set-up
+GRIDCONFIG_DEFAULTS = (("area_center_x", "0.0"), ("area_center_y", "-35.0"), ("area_size", "50"), ("N", "1024"))
+# every key of the reference's savemat call (wassgridsurface.py:194-231), in its order
+CONFIG_MAT_KEYS = ("xmin", "xmax", "ymin", "ymax", "zmin", "zmax", "P0cam", "P1cam", "Hcam0toGrid", "Hcam1toGrid", "Cam0toGrid", "Cam1toGrid",
+                   "Hcam0toTexture", "Nx", "Ny", "N", "R", "T", "RTplane", "K0", "K1", "Rpl", "Tpl", "P0plane", "P1plane", "CAM_BASELINE",
+                   "scale", "XX", "YY", "KX_ab", "KY_ab", "spec_scale", "x_spacing", "y_spacing", "fps", "timestring")
+
+
+def generate_gridconfig(outdir) -> str:
+    """`--action generateconfig` (:650-661): writes <outdir>/gridconfig.txt with the reference's defaults and returns its path."""
+    path = os.path.join(os.fspath(outdir), "gridconfig.txt")
+    with open(path, "w") as f:
+        f.write("[Area]\n")
+        for k, v in GRIDCONFIG_DEFAULTS:
+            f.write(f"{k}={v}\n")
+    return path
+
+
+def read_gridconfig(path) -> dict:
+    """The [Area] section of a gridconfig.txt: area_center (2 floats), area_size_x, area_size_y, Nx, Ny.  As in the reference
+    (:697-718) a pair is taken only when both of its options are there (area_size_x and area_size_y, Nx and Ny); otherwise the
+    single option (area_size, N) stands for both."""
+    import configparser
+    parser = configparser.ConfigParser()
+    if not parser.read(os.fspath(path)):
+        raise FileNotFoundError(os.fspath(path))
+    area = parser["Area"]
+
+    def pair(first, second, single, convert):
+        if first in area and second in area:
+            return convert(area[first]), convert(area[second])
+        both = convert(area[single])
+        return both, both
+
+    size_x, size_y = pair("area_size_x", "area_size_y", "area_size", float)
+    nx, ny = pair("Nx", "Ny", "N", int)
+    return {"area_center": np.array([float(area["area_center_x"]), float(area["area_center_y"])]),
+            "area_size_x": size_x, "area_size_y": size_y, "Nx": nx, "Ny": ny}
+
+
+def mean_plane(planes) -> np.ndarray:
+    """np.nanmean(planes, axis=0) of a sequence's planes.txt (:672-678): the path of the file or an n x 4 array."""
+    if isinstance(planes, (str, os.PathLike)):
+        planes = np.loadtxt(os.fspath(planes))
+    planes = np.asarray(planes, np.float64).reshape(-1, 4)
+    mean, n = planes_mean_finish(planes_mean_accumulate(planes))
+    if n == 0:
+        raise ValueError("planes: no row without a NaN")
+    return mean
+
+
+def read_opencv_matrix(path, node: str) -> np.ndarray:
+    """The matrix <node> of an OpenCV FileStorage XML file (intrinsics_0000000X.xml has `intr`): rows, cols, dt d (float64) or f
+    (float32), the data on one or several lines.  What cv.FileStorage(...).getNode(node).mat() returns for such a node."""
+    import re
+    with open(os.fspath(path)) as f:
+        text = f.read()
+    m = re.search(r"<%s(\s[^>]*)?>(.*?)</%s>" % (re.escape(node), re.escape(node)), text, re.S)
+    if m is None or "<opencv_storage>" not in text:
+        raise ValueError(f"{path}: no node <{node}> in an <opencv_storage>")
+    body = m.group(2)
+
+    def field(name):
+        f = re.search(r"<%s>(.*?)</%s>" % (name, name), body, re.S)
+        if f is None:
+            raise ValueError(f"{path}: <{node}> has no <{name}>")
+        return f.group(1).strip()
+
+    rows, cols, dt = int(field("rows")), int(field("cols")), field("dt")
+    if dt not in ("d", "f"):
+        raise ValueError(f"{path}: <{node}> has dt {dt!r}; d or f expected")
+    vals = np.array(field("data").split(), np.float64)
+    if vals.size != rows * cols:
+        raise ValueError(f"{path}: <{node}> holds {vals.size} numbers for {rows} x {cols}")
+    return vals.reshape(rows, cols).astype(np.float64 if dt == "d" else np.float32)
+
+
+def homography_4pt(src, dst) -> np.ndarray:
+    """The homography that takes four points onto four points (4 x 2 each), H[2, 2] = 1: what cv.findHomography returns for four
+    correspondences (its normalised DLT, no refinement), to rounding.  Both sets are cast to float32 first, as the reference's call
+    does, and the system is solved in fp64.  Three collinear points on either side raise ValueError."""
+    src = np.asarray(src, np.float32).astype(np.float64)
+    dst = np.asarray(dst, np.float32).astype(np.float64)
+    if src.shape != (4, 2) or dst.shape != (4, 2):
+        raise ValueError("homography_4pt: 4 x 2 points each way expected")
+    if not (np.isfinite(src).all() and np.isfinite(dst).all()):
+        raise ValueError("homography_4pt: non-finite point")
+
+    def normalise(p, what):
+        c = p.mean(axis=0)
+        s = np.abs(p - c).mean(axis=0)
+        if not (s > 0).all():
+            raise ValueError(f"homography_4pt: the {what} points are collinear")
+        s = 1.0 / s
+        q = (p - c) * s
+        for i, j, k in ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3)):
+            a, b = q[j] - q[i], q[k] - q[i]
+            if abs(a[0] * b[1] - a[1] * b[0]) <= 1e-9:      # twice the triangle's area, in units of the points' own spread
+                raise ValueError(f"homography_4pt: three of the {what} points are collinear")
+        return q, np.array([[s[0], 0, -c[0] * s[0]], [0, s[1], -c[1] * s[1]], [0, 0, 1.0]])
+
+    p, Tp = normalise(src, "source")
+    q, Tq = normalise(dst, "target")
+    A = np.zeros((8, 9))
+    for i in range(4):
+        x, y, u, v = p[i, 0], p[i, 1], q[i, 0], q[i, 1]
+        A[2 * i] = [x, y, 1, 0, 0, 0, -u * x, -u * y, -u]
+        A[2 * i + 1] = [0, 0, 0, x, y, 1, -v * x, -v * y, -v]
+    h = np.linalg.svd(A)[2][-1].reshape(3, 3)
+    H = np.linalg.inv(Tq) @ h @ Tp
+    if H[2, 2] == 0 or not np.isfinite(H).all():
+        raise ValueError("homography_4pt: degenerate correspondences")
+    return H / H[2, 2]
+
+
+def sea_plane_RT(plane):
+    """Rpl (3 x 3) and Tpl (3 x 1) of a plane a x + b y + c z + d = 0: the rotation that turns its normal onto the z axis and the
+    shift by d along it, what the reference's compute_sea_plane_RT returns.  The library's wass_RT_from_plane holds the arithmetic."""
+    from .stereo import RT_from_plane
+    rot, shift, _, _ = RT_from_plane([float(v) for v in np.ravel(plane)])
+    return rot, shift.reshape(3, 1)
+
+
+def _four_by_four(m34) -> np.ndarray:
+    return np.vstack((np.asarray(m34, np.float64).reshape(3, 4), [0.0, 0.0, 0.0, 1.0]))
+
+
+def setup_algebra(K0, K1, R, T, P0cam, P1cam, meanplane, baseline, area_center, area_size_x, area_size_y, Nx, Ny, Iw, Ih, z_q02, z_q98,
+                  fps=0, timestring="") -> dict:
+    """Everything the set-up derives once the files are read and the 2 % / 98 % quantiles of the aligned heights are known: the
+    values of the reference's config.mat (CONFIG_MAT_KEYS), from its expressions with its association of the matrix products
+    (wassgridsurface.py:82-174), so that the numbers are the reference's.  Raises ValueError where the reference asserts that the
+    grid spacings along x and y agree to 1e-2."""
+    Nx, Ny = int(Nx), int(Ny)
+    intrinsics = (np.asarray(K0), np.asarray(K1))
+    projections = (_four_by_four(P0cam), _four_by_four(P1cam))
+    Rpl, Tpl = sea_plane_RT(meanplane)
+    # plane frame -> camera frame (the inverse of the alignment), pixels -> the square [-1, 1]^2, metres with z up -> plane frame
+    cam_from_plane = np.vstack((np.hstack((Rpl.T, -Rpl.T @ Tpl)), [0, 0, 0, 1]))
+    unit_from_pixel = np.array([[2.0 / Iw, 0, -1, 0], [0, 2.0 / Ih, -1, 0], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=float)
+    per_metre = 1.0 / baseline
+    plane_from_grid = np.diag((per_metre, per_metre, -per_metre, 1))
+    plane_projection, cam_to_grid = [], []
+    for K, P in zip(intrinsics, projections):
+        plane_projection.append(unit_from_pixel @ P @ cam_from_plane @ plane_from_grid)
+        K44 = np.eye(4)
+        K44[:3, :3] = K
+        cam_to_grid.append(np.linalg.inv(plane_from_grid) @ np.linalg.inv(cam_from_plane) @ np.linalg.inv(np.linalg.inv(K44) @ P))
+    # the extent, and a height range symmetric about 0 that keeps the larger magnitude
+    half = (area_size_x / 2, area_size_y / 2)
+    lo = [area_center[k] - half[k] for k in (0, 1)]
+    hi = [area_center[k] + half[k] for k in (0, 1)]
+    zmax, zmin = z_q98 * 1.5, z_q02 * 1.5
+    if abs(zmax) > abs(zmin):
+        zmin = -zmax
+    else:
+        zmax = -zmin
+    # the four corners of the extent at height 0, where each camera sees them, and the homographies between the two
+    corners = np.array([[lo[0], lo[1]], [hi[0], lo[1]], [hi[0], hi[1]], [lo[0], hi[1]]], dtype=float)
+    corners_h = np.vstack((corners.T, np.zeros(4), np.ones(4)))
+    pixel_from_unit = np.linalg.inv(unit_from_pixel)
+    to_grid = []
+    for Pp in plane_projection:
+        seen = pixel_from_unit @ Pp @ corners_h
+        seen /= seen[2, :]
+        to_grid.append((seen[:2, :].T, homography_4pt(seen[:2, :].T, corners)))
+    to_texture = homography_4pt(to_grid[0][0], np.array([[0, 0], [Nx, 0], [Nx, Ny], [0, Ny]], dtype=np.float32))
+    # cell centres and the wavenumber axes of the grid's FFT
+    XX, YY = np.meshgrid(np.linspace(lo[0], hi[0], Nx), np.linspace(lo[1], hi[1], Ny))
+    dx, dy = XX[0, 1] - XX[0, 0], YY[1, 0] - YY[0, 0]
+    if not abs(dx - dy) < 1e-2:
+        raise ValueError(f"grid spacing {dx} along x and {dy} along y: they must agree to 1e-2")
+    kx = np.arange(-(Nx // 2), Nx // 2, dtype=np.float64) / Nx * (2.0 * np.pi / dx)
+    ky = np.arange(-(Ny // 2), Ny // 2, dtype=np.float64) / Ny * (2 * np.pi / dy)
+    KX, KY = np.meshgrid(kx, ky)
+    out = {"xmin": lo[0], "xmax": hi[0], "ymin": lo[1], "ymax": hi[1], "zmin": zmin, "zmax": zmax,
+           "Nx": Nx, "Ny": Ny, "N": max(Nx, Ny), "XX": XX, "YY": YY, "x_spacing": dx, "y_spacing": dy,
+           "KX_ab": KX, "KY_ab": KY, "spec_scale": 1.0 / (Nx * Ny),
+           "R": np.asarray(R), "T": np.asarray(T), "Rpl": Rpl, "Tpl": Tpl, "RTplane": cam_from_plane,
+           "CAM_BASELINE": baseline, "scale": baseline, "fps": fps, "timestring": timestring,
+           "Hcam0toTexture": to_texture}
+    for cam in (0, 1):
+        out.update({f"K{cam}": intrinsics[cam], f"P{cam}cam": projections[cam][0:3, :], f"P{cam}plane": plane_projection[cam],
+                    f"Cam{cam}toGrid": cam_to_grid[cam], f"Hcam{cam}toGrid": to_grid[cam][1]})
+    return out
+
+
+class ImageSizeUnknown(ValueError):
+    """setup_grid has neither Iw / Ih nor undistorted/00000000.png to read them from"""
+
+
+def setup_grid(wdir, meanplane, baseline, area_center, area_size_x, area_size_y, Nx, Ny, Iw=None, Ih=None, fps=0, timestring="",
+               ctx: Context | None = None, outdir=None) -> dict:
+    """wassgridsurface --action setup (:57-231) on the first frame's directory wdir: reads its calibration (intrinsics_0000000X.xml,
+    Cam0_poseR/T.txt, P0cam.txt, P1cam.txt) and mesh_cam.xyzC, takes the 2 % and 98 % quantiles of the heights aligned on
+    meanplane on the GPU (Mesh.aligned_z_quantiles) and returns the dict of the reference's config.mat (CONFIG_MAT_KEYS), which
+    grid_sequence and the wass_amd.postproc functions take.  Two keys more: cam0_rectified, the Ny x Nx uint8 picture of camera 0
+    warped onto the grid (None without undistorted/00000000.png), and coverage, the fraction of grid cells that hold a point of
+    this frame.  Iw / Ih default to the size of that picture.  outdir: also writes config.mat (the reference's keys only) and
+    cam0_rectified.png there."""
+    import torch
+    wdir = os.fspath(wdir)
+    K0 = read_opencv_matrix(os.path.join(wdir, "intrinsics_00000000.xml"), "intr")
+    K1 = read_opencv_matrix(os.path.join(wdir, "intrinsics_00000001.xml"), "intr")
+    R = np.loadtxt(os.path.join(wdir, "Cam0_poseR.txt"))
+    T = np.loadtxt(os.path.join(wdir, "Cam0_poseT.txt"))
+    P0cam = np.loadtxt(os.path.join(wdir, "P0cam.txt"))
+    P1cam = np.loadtxt(os.path.join(wdir, "P1cam.txt"))
+    picture = None
+    picfile = os.path.join(wdir, "undistorted", "00000000.png")
+    if os.path.exists(picfile):
+        from PIL import Image
+        with Image.open(picfile) as im:
+            picture = np.asarray(im.convert("L"), np.uint8)
+        if Iw is None or Ih is None:
+            Iw, Ih = picture.shape[1], picture.shape[0]
+    if Iw is None or Ih is None:
+        raise ImageSizeUnknown(f"{wdir}: no undistorted/00000000.png to take the picture size from; give Iw and Ih")
+    if meanplane is None:
+        raise ValueError("no mean plane (planes.txt)")
+    Nx, Ny = int(Nx), int(Ny)
+    Rpl, Tpl = sea_plane_RT(meanplane)
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = Context(0)
+    mesh = None
+    try:
+        mesh = upload_camera_mesh(ctx, load_camera_mesh(os.path.join(wdir, "mesh_cam.xyzC")))
+        (z98, z02), npts = mesh.aligned_z_quantiles(Rpl, Tpl, baseline, [0.98, 0.02])
+        if npts == 0:
+            raise ValueError(f"{wdir}/mesh_cam.xyzC holds no point")
+        res = setup_algebra(K0, K1, R, T, P0cam, P1cam, meanplane, baseline, area_center, area_size_x, area_size_y, Nx, Ny, Iw, Ih,
+                            z02, z98, fps, timestring)
+        gs = grid_setup(Rpl, Tpl, baseline, res["xmin"], res["xmax"], res["ymin"], res["ymax"], Nx, Ny)
+        d_cells = torch.empty((Ny, Nx), dtype=torch.float32, device=torch.device("cuda", ctx.device_id))
+        torch.cuda.synchronize(d_cells.device)
+        mesh.grid_cells_dev(gs, d_cells, "median")
+        ctx.synchronize()
+        res["coverage"] = float(torch.isfinite(d_cells).sum().item()) / float(Nx * Ny)
+        res["cam0_rectified"] = None if picture is None else ctx.warp_perspective(picture, res["Hcam0toTexture"], Nx, Ny)
+    finally:
+        if mesh is not None:
+            mesh.close()
+        if own_ctx:
+            ctx.close()
+    if outdir is not None:
+        import scipy.io
+        scipy.io.savemat(os.path.join(os.fspath(outdir), "config.mat"), {k: res[k] for k in CONFIG_MAT_KEYS})
+        if res["cam0_rectified"] is not None:
+            from PIL import Image
+            Image.fromarray(res["cam0_rectified"]).save(os.path.join(os.fspath(outdir), "cam0_rectified.png"))
+    return res
+
+
+def main(argv=None) -> int:
+    """python -m wass_amd.gridding WORKDIR OUTDIR --action generateconfig|setup: the option names and exit codes of the reference's
+    command line (-1: no output directory, no --gridconfig or file not found, nothing to set up from; -2: no such action here;
+    -3: picture size unknown)."""
+    import argparse
+    import glob
+    ap = argparse.ArgumentParser(prog="python -m wass_amd.gridding", description="Grid set-up of a WASS sequence; the quantiles of the "
+                                 "first frame's cloud are taken on the GPU.")
+    ap.add_argument("workdir", help="sequence directory: the NNNNNN_wd frame directories and planes.txt")
+    ap.add_argument("outdir", help="existing directory that receives gridconfig.txt, config.mat and cam0_rectified.png")
+    ap.add_argument("--action", choices=("setup", "grid", "generateconfig"), help="generateconfig writes a default gridconfig.txt, "
+                    "setup writes config.mat; grid is wass_amd.gridding.grid_sequence, a function")
+    ap.add_argument("--gridconfig", help="the [Area] file that setup reads")
+    ap.add_argument("-b", "--baseline", type=float, default=1.0, help="distance between the cameras in metres (default 1)")
+    ap.add_argument("-f", "--fps", type=float, default=0, help="frame rate stored in config.mat")
+    ap.add_argument("-t", "--timestring", default="", help="date and time of the sequence, stored as given")
+    ap.add_argument("-Iw", "--image_width", type=float, help="picture width when undistorted/00000000.png is absent")
+    ap.add_argument("-Ih", "--image_height", type=float, help="picture height, likewise")
+    ap.add_argument("-n", "--num_frames", type=int, default=-1, help="look at the first n frame directories only")
+    args = ap.parse_args(argv)
+
+    if args.action == "generateconfig":
+        print("wrote", generate_gridconfig(args.outdir))
+        return 0
+    frames = sorted(glob.glob(os.path.join(args.workdir, "*_wd")))
+    if args.num_frames > -1:
+        frames = frames[:args.num_frames]
+    if not os.path.isdir(args.outdir):
+        print(f"{args.outdir}: no such output directory")
+        return -1
+    if args.action == "grid":
+        print("the grid action is a function here: wass_amd.gridding.grid_sequence(frames, 'config.mat') returns the cube; no NetCDF file is written")
+        return -2
+    if args.action != "setup":
+        print("give --action generateconfig or --action setup")
+        return -2
+    if args.gridconfig is None:
+        print("setup needs --gridconfig FILE (generateconfig writes one)")
+        return -1
+    if not os.path.exists(args.gridconfig):
+        print(f"{args.gridconfig}: no such grid configuration file")
+        return -1
+    planes = os.path.join(args.workdir, "planes.txt")
+    if not frames or not os.path.exists(planes):
+        print(f"{args.workdir}: setup needs at least one NNNNNN_wd directory and planes.txt")
+        return -1
+    try:
+        res = setup_grid(frames[0], mean_plane(planes), baseline=args.baseline, Iw=args.image_width, Ih=args.image_height, fps=args.fps,
+                         timestring=args.timestring, outdir=args.outdir, **read_gridconfig(args.gridconfig))
+    except ImageSizeUnknown as e:
+        print(e)
+        return -3
+    except ValueError as e:
+        print(e)
+        return -1
+    print(f"{frames[0]}: heights within {res['zmin']:.2f} .. {res['zmax']:.2f} m, {100.0 * res['coverage']:.1f} % of the "
+          f"{res['Nx']} x {res['Ny']} cells hold a point")
+    print("wrote", os.path.join(args.outdir, "config.mat"))
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

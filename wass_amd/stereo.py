@@ -443,6 +443,19 @@ class Context:
                                                  C.byref(dl), C.byref(rl)))
         return g, dl.value, rl.value
 
+    def quantiles_dev(self, d_values, q) -> np.ndarray:
+        """np.quantile(values, q) (method "linear") over a contiguous float64 device tensor, as exact order statistics found on
+        the device (wass_quantiles_f64_dev; at most 8 values of q per call).  The tensor's producer must have finished."""
+        import torch
+        if d_values.dtype != torch.float64 or not d_values.is_contiguous():
+            raise ValueError("d_values: a contiguous float64 device tensor expected")
+        qa = np.ascontiguousarray(np.atleast_1d(q), np.float64)
+        out = np.empty(qa.size, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.wass_quantiles_f64_dev(self._h, d_values.data_ptr() if d_values.numel() else None, d_values.numel(),
+                                                     qa.ctypes.data_as(dp), qa.size, out.ctypes.data_as(dp)))
+        return out
+
     def mesh_upload(self, valid, p3d, gray=None):
         valid = np.ascontiguousarray(valid, np.uint8)
         p3d = np.ascontiguousarray(p3d, np.float64)
@@ -551,6 +564,13 @@ def grid_setup(R, T, baseline: float, xmin: float, xmax: float, ymin: float, yma
     gs.baseline, gs.xmin, gs.xmax, gs.ymin, gs.ymax, gs.width, gs.height = (float(baseline), float(xmin), float(xmax), float(ymin),
                                                                            float(ymax), int(width), int(height))
     return gs
+
+
+def quantiles_launch_shape():
+    """(elements one workgroup takes per sweep, elements one launch takes per sweep) of the quantile selection (grid_setup.hip)."""
+    a, b = C.c_int(), C.c_int()
+    _lib.load().wass_quantiles_launch_shape(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 class GridSequence:
@@ -670,6 +690,19 @@ class Mesh:
             raise ValueError("d_cells: a contiguous float32 height x width tensor expected")
         self.ctx._check(self.ctx._lib.wass_mesh_grid_cells_dev(self.ctx._h, self._h, C.byref(gs), {"mean": 0, "median": 1}[cell],
                                                                d_cells.data_ptr()))
+
+    def aligned_z_quantiles(self, R, T, baseline: float, q):
+        """np.quantile of the heights of the valid points after the alignment on the sea plane, z = -(R[2] . p + T[2]) * baseline
+        (wassgridsurface.py:87, 122-123): (the quantiles, the number of valid points).  wass_mesh_aligned_z_quantiles."""
+        qa = np.ascontiguousarray(np.atleast_1d(q), np.float64)
+        out = np.empty(qa.size, np.float64)
+        n = C.c_uint64()
+        dp = C.POINTER(C.c_double)
+        Rc = (C.c_double * 9)(*np.asarray(R, float).ravel())
+        Tc = (C.c_double * 3)(*np.asarray(T, float).ravel())
+        self.ctx._check(self.ctx._lib.wass_mesh_aligned_z_quantiles(self.ctx._h, self._h, Rc, Tc, float(baseline), qa.ctypes.data_as(dp),
+                                                                    qa.size, out.ctypes.data_as(dp), C.byref(n)))
+        return out, int(n.value)
 
     def zgap_percentile(self, pct: float):
         out = C.c_double(); n = C.c_uint64()
