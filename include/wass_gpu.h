@@ -897,6 +897,61 @@ int wass_zeromean(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride
 int wass_zeromean_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, float* d_out,
                       size_t out_stride_t, size_t out_stride_y);
 
+/* ---- Feature matcher: the game-theoretic inlier selection of wass_match (src/wass_match/GTMatcher.cpp, iidyn.cpp) as array
+ * functions.  A feature is four float32, x y scale angle (the head of a record of FeatureSet::save); a candidate is a pair of
+ * int32, (feature of A, feature of B).
+ *
+ * wass_match_knn: for every descriptor of A (na x d float32) the kk = min(k, nb) descriptors of B (nb x d) at the smallest squared
+ * L2 distance, the float32 differences squared and summed in index order without contraction; by increasing distance, equal
+ * distances by increasing index.  idx and dist are na x kk.  An exact search: the reference asks a randomised kd-forest
+ * (FeatureSet.cpp:452-468), whose limit this is.  1 <= k <= WASS_MATCH_MAX_K, 1 <= d <= WASS_MATCH_MAX_DESC.  A distance that is NaN
+ * is never a neighbour; a feature with fewer than kk neighbours left gets idx -1 and an infinite distance for the rest.
+ *
+ * wass_match_payoff: the n x n fp64 matrix of compute_payoff_matrix (:219-250).  Per candidate compute_affine (:69-97) in fp64 with
+ * the float32 positions, scales and angles widened where the reference widens them (ang_diff's two loops included); entry (i, j) =
+ * exp(-lambda * max(e_ij, e_ji)), e_ij the squared distance from candidate j's target to candidate i's transform of candidate j's
+ * source; 0 where the two share a source or a target, the diagonal included.  The matrix is symmetric bit for bit.  A candidate
+ * outside its feature set, or two angles more than 1e4 apart (the reference's loops would not end) or not numbers:
+ * WASS_ERR_INVALID_ARG after the launch, which reads nothing out of bounds.
+ *
+ * wass_match_iidyn: gt_iidyn (iidyn.cpp:520-596) from the start x (or, with uniform_start, from gt_create_population's, which is
+ * uniform: its rand() / RAND_MAX is an integer division), one workgroup of 1024 threads per problem with x and Ax in registers.
+ * A step keeps the reference's order: selectStrategy (the first largest Ax; the first smallest Ax among x > 0), the Nash error, the
+ * mu / do_remove cases, scale, x[idx], simplexify, linear_comb as alfa * (x - y) + y.  Sums and extrema are reduced in one fixed
+ * tree that depends on n alone (a thread's elements in index order, a butterfly over the wave, the waves in order), so a problem
+ * gives the same bits alone and in any batch; the reference sums sequentially, which moves the population by rounding only.
+ * toll is squared as the reference squares it.  *steps = the steps taken, *err = the last Nash error (DBL_MAX when max_iters is
+ * 0).  Where the reference would read A[-size - 1] (no strategy qualifies: a population that is all zero or NaN) the loop ends.
+ * group[i] = x[i] > max(x) * pop_threshold (match_group :273-293), *group_size their number.  n <= WASS_MATCH_MAX_N.
+ *
+ * The _dev forms take `batch` problems in device memory: problem p has n[p] candidates (n, na, nb: host arrays) and lives at
+ * base + p * stride, strides in elements (float32 for features, int32 for candidates, fp64 for A and x, bytes for group); its
+ * matrix is n[p] x n[p], tightly packed.  With batch == 1 the strides are not read.  wass_match_round_dev is one round of the
+ * matcher for the batch: payoff, uniform start, dynamics, group.  wass_match_scratch_bytes: the device memory such a round takes
+ * for `batch` problems of at most n_max candidates, the caller's arrays (A, x, group, candidates) and the context's own together;
+ * no GPU needed.  Every call returns after a synchronisation. */
+#define WASS_MATCH_MAX_N 8192
+#define WASS_MATCH_MAX_K 8
+#define WASS_MATCH_MAX_DESC 256
+int wass_match_scratch_bytes(int batch, int n_max, size_t* bytes);
+int wass_match_knn(wass_ctx* ctx, const float* desc_a, int na, const float* desc_b, int nb, int d, int k, int32_t* idx, float* dist);
+int wass_match_knn_dev(wass_ctx* ctx, const float* d_desc_a, int na, const float* d_desc_b, int nb, int d, int k, int32_t* d_idx,
+                       float* d_dist);
+int wass_match_payoff(wass_ctx* ctx, const float* fa, int na, const float* fb, int nb, const int32_t* cand, int n, double lambda,
+                      double* A);
+int wass_match_payoff_dev(wass_ctx* ctx, const float* d_fa, size_t fa_stride, const float* d_fb, size_t fb_stride, const int32_t* d_cand,
+                          size_t cand_stride, const int* n, const int* na, const int* nb, int batch, double lambda, double* d_A,
+                          size_t A_stride);
+int wass_match_iidyn(wass_ctx* ctx, const double* A, int n, double* x, int uniform_start, double toll, int max_iters,
+                     double pop_threshold, int* steps, double* err, uint8_t* group, int* group_size);
+int wass_match_iidyn_dev(wass_ctx* ctx, const double* d_A, size_t A_stride, double* d_x, size_t x_stride, int uniform_start, const int* n,
+                         int batch, double toll, int max_iters, double pop_threshold, int* steps, double* err, uint8_t* d_group,
+                         size_t group_stride, int* group_size);
+int wass_match_round_dev(wass_ctx* ctx, const float* d_fa, size_t fa_stride, const float* d_fb, size_t fb_stride, const int32_t* d_cand,
+                         size_t cand_stride, const int* n, const int* na, const int* nb, int batch, double lambda, double toll,
+                         int max_iters, double pop_threshold, double* d_A, size_t A_stride, double* d_x, size_t x_stride, int* steps,
+                         double* err, uint8_t* d_group, size_t group_stride, int* group_size);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

@@ -280,6 +280,16 @@ SYMBOLS = {
                                 C.POINTER(C.c_float)]),
     "wass_zeromean": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _sz, _sz]),
     "wass_zeromean_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_match_scratch_bytes": (_i, [_i, _i, C.POINTER(_sz)]),
+    "wass_match_knn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "wass_match_knn_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "wass_match_payoff": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp]),
+    "wass_match_payoff_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, C.c_double, _vp, _sz]),
+    "wass_match_iidyn": (_i, [_vp, _vp, _i, _vp, _i, C.c_double, _i, C.c_double, C.POINTER(_i), C.POINTER(C.c_double), _vp, C.POINTER(_i)]),
+    "wass_match_iidyn_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _i, C.POINTER(_i), _i, C.c_double, _i, C.c_double, C.POINTER(_i),
+                                  C.POINTER(C.c_double), _vp, _sz, C.POINTER(_i)]),
+    "wass_match_round_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, C.c_double, C.c_double, _i,
+                                  C.c_double, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _vp, _sz, C.POINTER(_i)]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

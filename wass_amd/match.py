@@ -1,0 +1,448 @@
+"""The game-theoretic feature matcher of wass_match on the GPU (src/wass_match/GTMatcher.cpp, iidyn.cpp, wass_match.cpp:211-246).
+
+The kernels (csrc/match.hip) find the candidates, fill the payoff matrix, run the infection-immunization dynamics and pick the
+group; the host keeps what the reference does between them: match_group's removal loop and wass_match's round loop, restated
+faithfully, quirks included.  Features come from a file in the layout of FeatureSet::save or from any detector (the reference's is
+OpenCV's KAZE, which is not part of this project); the matches go out in the text format of matches_unfiltered.txt.
+
+Host arrays are numpy, device arrays torch tensors passed by raw pointer.  There is no CPU path: without the library or a GPU
+every function that computes raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib
+
+MAX_N = 8192          # candidates per problem: WASS_MATCH_MAX_N
+MAX_K = 8             # candidates per feature: WASS_MATCH_MAX_K
+MAX_DESC = 256        # descriptor length: WASS_MATCH_MAX_DESC
+BATCH_BYTES = 16 << 30   # payoff matrices held at once by gt_match_batch; more problems go in several launches
+
+
+@dataclass
+class Features:
+    """One picture's features: xy float32 n x 2, scale and angle float32 n, desc float32 n x d"""
+    xy: np.ndarray
+    scale: np.ndarray
+    angle: np.ndarray
+    desc: np.ndarray
+
+    def __post_init__(self):
+        self.xy = np.ascontiguousarray(self.xy, np.float32).reshape(-1, 2)
+        self.scale = np.ascontiguousarray(self.scale, np.float32).reshape(-1)
+        self.angle = np.ascontiguousarray(self.angle, np.float32).reshape(-1)
+        self.desc = np.ascontiguousarray(self.desc, np.float32)
+        n = self.xy.shape[0]
+        if self.desc.ndim != 2 or not (self.scale.shape[0] == self.angle.shape[0] == self.desc.shape[0] == n):
+            raise ValueError("Features: xy, scale, angle and desc must describe the same number of features")
+
+    def __len__(self):
+        return self.xy.shape[0]
+
+    def table(self) -> np.ndarray:
+        """n x 4 float32: x y scale angle, what the payoff kernel reads"""
+        return np.ascontiguousarray(np.column_stack([self.xy, self.scale, self.angle]).astype(np.float32))
+
+
+@dataclass
+class Dynamics:
+    """What iidyn returns: the population, the steps taken, the last Nash error, the indices above max(x) * pop_threshold"""
+    x: np.ndarray
+    steps: int
+    err: float
+    group: np.ndarray
+
+
+@dataclass
+class MatchResult:
+    """matches: M x 2 int32 (feature of A, feature of B) in the reference's order; loc_a / loc_b: their float32 positions;
+    rounds: per round (candidates, steps, group size)"""
+    matches: np.ndarray
+    loc_a: np.ndarray
+    loc_b: np.ndarray
+    rounds: list = field(default_factory=list)
+
+
+# ----------------------------------------------------------------------------------------------------------------------- files
+def write_features(path, f: Features) -> None:
+    """FeatureSet::save: u32 count, u32 descriptor length, then 4 + d float32 per feature: x y scale angle descriptor"""
+    n, d = f.desc.shape
+    rec = np.empty((n, 4 + d), "<f4")
+    rec[:, 0:2], rec[:, 2], rec[:, 3], rec[:, 4:] = f.xy, f.scale, f.angle, f.desc
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<II", n, d))
+        fh.write(rec.tobytes())
+
+
+def read_features(path) -> Features:
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    if len(raw) < 8:
+        raise ValueError(f"{path}: not a feature file")
+    n, d = struct.unpack_from("<II", raw, 0)
+    if len(raw) < 8 + n * (4 + d) * 4:
+        raise ValueError(f"{path}: {n} features of {d} values need {8 + n * (4 + d) * 4} bytes, the file has {len(raw)}")
+    rec = np.frombuffer(raw, "<f4", n * (4 + d), 8).reshape(n, 4 + d)
+    return Features(rec[:, 0:2].copy(), rec[:, 2].copy(), rec[:, 3].copy(), rec[:, 4:].copy())
+
+
+def _g15(v) -> str:
+    return format(float(v), ".15g")      # operator<<(float) at setprecision(15)
+
+
+def write_matches(path, loc_a, loc_b=None) -> None:
+    """save_matches (wass_match.cpp:48-67): the count, then x0 y0 x1 y1 per match with 15 significant digits.  Takes a MatchResult
+    or the two M x 2 float32 position arrays."""
+    if isinstance(loc_a, MatchResult):
+        loc_a, loc_b = loc_a.loc_a, loc_a.loc_b
+    a, b = np.asarray(loc_a, np.float32).reshape(-1, 2), np.asarray(loc_b, np.float32).reshape(-1, 2)
+    if a.shape != b.shape:
+        raise ValueError("write_matches: the two position arrays differ in shape")
+    with open(path, "w") as fh:
+        fh.write(f"{a.shape[0]}\n")
+        for p, q in zip(a, b):
+            fh.write(f"{_g15(p[0])} {_g15(p[1])} {_g15(q[0])} {_g15(q[1])}\n")
+
+
+def read_matches(path):
+    """(loc_a, loc_b), each M x 2 float32"""
+    with open(path) as fh:
+        tok = fh.read().split()
+    m = int(tok[0])
+    v = np.array(tok[1:1 + 4 * m], np.float64).astype(np.float32).reshape(m, 4)
+    return v[:, 0:2].copy(), v[:, 2:4].copy()
+
+
+# --------------------------------------------------------------------------------------------------------------------- context
+_default_ctx = None
+
+
+def _context(ctx):
+    global _default_ctx
+    if ctx is not None:
+        return ctx
+    if _default_ctx is None:
+        from .stereo import Context
+        _default_ctx = Context(0)
+    return _default_ctx
+
+
+def _is_tensor(a) -> bool:
+    return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
+
+
+def _ints(v):
+    return (C.c_int * len(v))(*[int(t) for t in v])
+
+
+def scratch_bytes(batch: int, n_max: int) -> int:
+    """device memory one round over `batch` problems of at most n_max candidates takes (no GPU needed)"""
+    b = C.c_size_t()
+    if _lib.load().wass_match_scratch_bytes(int(batch), int(n_max), C.byref(b)) != 0:
+        raise ValueError(f"batch = {batch}, n_max = {n_max}: 1 .. 65535 problems of 1 .. {MAX_N} candidates")
+    return b.value
+
+
+# ------------------------------------------------------------------------------------------------------------------ candidates
+def _check_knn(na, da, nb, db, k):
+    if da != db:
+        raise ValueError(f"descriptors of {da} and of {db} values cannot be compared")
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k = {k}: 1 .. {MAX_K} candidates per feature")
+    if not 1 <= da <= MAX_DESC:
+        raise ValueError(f"descriptors of {da} values: 1 .. {MAX_DESC}")
+    if na < 1 or nb < 1:
+        raise ValueError("both feature sets need at least one feature")
+
+
+def knn_candidates(desc_a, desc_b, k: int = 3, ctx=None):
+    """For every descriptor of A the min(k, nb) nearest of B, exactly: (idx int32 na x kk, squared L2 distances float32 na x kk), by
+    increasing distance, ties to the lower index.  Candidate i * kk + j of the matcher is (i, idx[i, j]).  numpy arrays or 2-D
+    float32 device tensors (then device tensors come back)."""
+    if _is_tensor(desc_a) or _is_tensor(desc_b):
+        import torch
+        for t in (desc_a, desc_b):
+            if not _is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+                raise ValueError("knn_candidates: both descriptor sets must be contiguous 2-D float32 device tensors (or both numpy)")
+        (na, da), (nb, db) = desc_a.shape, desc_b.shape
+        _check_knn(na, da, nb, db, k)
+        ctx = _context(ctx)
+        kk = min(k, nb)
+        idx = torch.empty((na, kk), dtype=torch.int32, device=desc_a.device)
+        dist = torch.empty((na, kk), dtype=torch.float32, device=desc_a.device)
+        torch.cuda.synchronize()
+        ctx._check(ctx._lib.wass_match_knn_dev(ctx._h, desc_a.data_ptr(), na, desc_b.data_ptr(), nb, da, k, idx.data_ptr(), dist.data_ptr()))
+        return idx, dist
+    a, b = np.asarray(desc_a), np.asarray(desc_b)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("knn_candidates: descriptors are n x d arrays")
+    _check_knn(a.shape[0], a.shape[1], b.shape[0], b.shape[1], k)
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    ctx = _context(ctx)
+    kk = min(k, b.shape[0])
+    idx, dist = np.empty((a.shape[0], kk), np.int32), np.empty((a.shape[0], kk), np.float32)
+    ctx._check(ctx._lib.wass_match_knn(ctx._h, a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], a.shape[1], k, idx.ctypes.data,
+                                       dist.ctypes.data))
+    return idx, dist
+
+
+def candidate_list(idx: np.ndarray) -> np.ndarray:
+    """generate_candidates' list: candidate i * kk + j is (i, idx[i, j])"""
+    na, kk = idx.shape
+    return np.ascontiguousarray(np.stack([np.repeat(np.arange(na, dtype=np.int32), kk), idx.reshape(-1).astype(np.int32)], axis=1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------- payoff
+def _table(f) -> np.ndarray:
+    t = f.table() if isinstance(f, Features) else np.ascontiguousarray(f, np.float32)
+    if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1:
+        raise ValueError("a feature table is n x 4 float32 (x y scale angle) with n >= 1")
+    return t
+
+
+def _check_cand(cand, na, nb) -> np.ndarray:
+    c = np.ascontiguousarray(cand, np.int32)
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise ValueError("candidates are an N x 2 array of (feature of A, feature of B)")
+    if c.shape[0] < 1:
+        raise ValueError("no candidates")
+    if c.shape[0] > MAX_N:
+        raise ValueError(f"{c.shape[0]} candidates: at most {MAX_N} per problem")
+    if c[:, 0].min() < 0 or c[:, 0].max() >= na or c[:, 1].min() < 0 or c[:, 1].max() >= nb:
+        raise ValueError("a candidate names a feature outside its set")
+    return c
+
+
+def payoff_matrix(fa, fb, cand, lam: float = 1e-5, ctx=None, device: bool = False):
+    """The N x N fp64 payoff matrix of the candidates (compute_payoff_matrix).  fa, fb: Features or n x 4 float32 tables; cand: N x 2.
+    Returns a numpy array, or with device=True a device tensor filled in place."""
+    ta, tb = _table(fa), _table(fb)
+    c = _check_cand(cand, ta.shape[0], tb.shape[0])
+    n = c.shape[0]
+    ctx = _context(ctx)
+    if not device:
+        A = np.empty((n, n), np.float64)
+        ctx._check(ctx._lib.wass_match_payoff(ctx._h, ta.ctypes.data, ta.shape[0], tb.ctypes.data, tb.shape[0], c.ctypes.data, n, C.c_double(lam),
+                                              A.ctypes.data))
+        return A
+    import torch
+    dev = torch.device("cuda", ctx.device_id)
+    d_a, d_b, d_c = torch.from_numpy(ta).to(dev), torch.from_numpy(tb).to(dev), torch.from_numpy(c).to(dev)
+    A = torch.empty((n, n), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    ctx._check(ctx._lib.wass_match_payoff_dev(ctx._h, d_a.data_ptr(), 0, d_b.data_ptr(), 0, d_c.data_ptr(), 0, _ints([n]), _ints([ta.shape[0]]),
+                                              _ints([tb.shape[0]]), 1, C.c_double(lam), A.data_ptr(), 0))
+    return A
+
+
+# -------------------------------------------------------------------------------------------------------------------- dynamics
+def _check_matrix(A):
+    """(n, is a device tensor) of one payoff matrix; refuses what the kernel cannot read in place"""
+    if _is_tensor(A):
+        import torch
+        if A.dim() != 2 or A.shape[0] != A.shape[1] or A.dtype != torch.float64 or not A.is_cuda:
+            raise ValueError("iidyn: a device matrix is a square float64 tensor")
+        if not A.is_contiguous():
+            raise ValueError("iidyn: a non-contiguous matrix is refused (the kernel reads rows in place)")
+        n, dev = int(A.shape[0]), True
+    else:
+        if not isinstance(A, np.ndarray):
+            A = np.asarray(A, np.float64)
+        if A.ndim != 2 or A.shape[0] != A.shape[1] or A.dtype != np.float64:
+            raise ValueError("iidyn: a matrix is a square float64 array")
+        if not A.flags.c_contiguous:
+            raise ValueError("iidyn: a non-contiguous matrix is refused (the kernel reads rows in place)")
+        n, dev = int(A.shape[0]), False
+    if n < 1:
+        raise ValueError("iidyn: an empty matrix")
+    if n > MAX_N:
+        raise ValueError(f"iidyn: N = {n} is above the cap of {MAX_N} strategies")
+    return A, n, dev
+
+
+def iidyn(A, x0=None, toll: float = 1e-20, max_iters: int = 50000, pop_threshold: float = 0.7, ctx=None):
+    """gt_iidyn on the GPU.  A: an N x N float64 host array or device tensor, or a list of them (a batch: one workgroup each, side
+    by side; problem i of a batch is bit for bit the single run of problem i).  x0: the start (a list for a batch); None is
+    gt_create_population's, which is uniform.  Returns a Dynamics, or a list of them."""
+    single = not isinstance(A, (list, tuple))
+    mats = [A] if single else list(A)
+    if not mats:
+        return []
+    starts = [x0] if single else (list(x0) if x0 is not None else [None] * len(mats))
+    if len(starts) != len(mats):
+        raise ValueError("iidyn: one start per matrix")
+    if max_iters < 0:
+        raise ValueError("iidyn: max_iters < 0")
+    checked = [_check_matrix(M) for M in mats]
+    uniform = all(s is None for s in starts)
+    xs = []
+    for (M, n, _), s in zip(checked, starts):
+        if s is None:
+            xs.append(np.full(n, 1.0 / np.float64(n)))
+        else:
+            v = (s.detach().cpu().numpy() if _is_tensor(s) else np.asarray(s)).astype(np.float64).reshape(-1)
+            if v.shape[0] != n:
+                raise ValueError(f"iidyn: a start of {v.shape[0]} values for a matrix of {n}")
+            xs.append(v)
+    import torch
+    ctx = _context(ctx)
+    dev = torch.device("cuda", ctx.device_id)
+    batch = len(checked)
+    ns = [n for _, n, _ in checked]
+    nmax = max(ns)
+    if batch == 1 and checked[0][2]:
+        d_A, a_stride = checked[0][0], 0                     # read in place
+    else:
+        a_stride = nmax * nmax
+        d_A = torch.empty(batch * a_stride, dtype=torch.float64, device=dev)
+        for p, (M, n, on_dev) in enumerate(checked):
+            src = M if on_dev else torch.from_numpy(M)
+            d_A[p * a_stride:p * a_stride + n * n].copy_(src.reshape(-1))
+    hx = np.zeros((batch, nmax))
+    for p, v in enumerate(xs):
+        hx[p, :ns[p]] = v
+    d_x = torch.from_numpy(hx).to(dev)
+    d_g = torch.zeros((batch, nmax), dtype=torch.uint8, device=dev)
+    steps, gsz, err = (C.c_int * batch)(), (C.c_int * batch)(), (C.c_double * batch)()
+    torch.cuda.synchronize()
+    ctx._check(ctx._lib.wass_match_iidyn_dev(ctx._h, d_A.data_ptr(), a_stride, d_x.data_ptr(), nmax, int(uniform), _ints(ns), batch, C.c_double(toll),
+                                             int(max_iters), C.c_double(pop_threshold), steps, err, d_g.data_ptr(), nmax, gsz))
+    hx, hg = d_x.cpu().numpy(), d_g.cpu().numpy()
+    out = [Dynamics(hx[p, :ns[p]].copy(), int(steps[p]), float(err[p]), np.flatnonzero(hg[p, :ns[p]])) for p in range(batch)]
+    for p, r in enumerate(out):
+        assert r.group.size == gsz[p]
+    return out[0] if single else out
+
+
+# ------------------------------------------------------------------------------------------------------------------ host logic
+def remove_candidates(cand: np.ndarray, winners: np.ndarray) -> np.ndarray:
+    """match_group's removal loop (GTMatcher.cpp:300-315), as it is: a candidate that uses a winning source or target is overwritten
+    with the LAST candidate, the list shrinks, and slot i is not looked at again.  The candidate swapped in therefore stays even if
+    it uses a winning feature itself, and a feature can end up in two matches; the reference's match lists are what this project
+    reproduces, so the loop is kept and not corrected."""
+    cm = [(int(s), int(t)) for s, t in np.asarray(cand).reshape(-1, 2)]
+    winners = np.asarray(winners).reshape(-1, 2)
+    srcs, tgts = set(winners[:, 0].tolist()), set(winners[:, 1].tolist())       # the inner loop over the winners, as two look-ups
+    i = 0
+    while i < len(cm):
+        if cm[i][0] in srcs or cm[i][1] in tgts:
+            cm[i] = cm[-1]
+            cm.pop()
+        i += 1
+    return np.array(cm, np.int32).reshape(-1, 2)
+
+
+def nndr_matches(idx: np.ndarray, dist: np.ndarray, k: int, nndr: float) -> np.ndarray:
+    """generate_candidates' own match list (GTMatcher.cpp:197-205), which MATCHER_SKIP_GT keeps: d0 < NNDR * d1 in float32, and only
+    when k > 1"""
+    if k <= 1:
+        return np.zeros((0, 2), np.int32)
+    if idx.shape[1] < 2:
+        raise ValueError("skip_gt with k > 1 needs two features in B: the reference reads the second distance")
+    rows = np.flatnonzero(dist[:, 0] < np.float32(nndr) * dist[:, 1])
+    return np.stack([rows.astype(np.int32), idx[rows, 0].astype(np.int32)], axis=1).reshape(-1, 2)
+
+
+def round_loop(cands, run, min_group_size: int = 5, max_rounds: int = 20):
+    """wass_match.cpp:220-234 for several problems in lockstep.  cands: one N x 2 candidate list per problem; run(live, cands) plays
+    one round for the problems `live` and returns, per problem, (steps, the indices of the winning candidates).  Returns the match
+    lists and, per problem and round, (candidates, steps, group size).  The loop is do ... while (max_rounds-- && continue_matching):
+    at most max_rounds + 1 rounds, and a group below min_group_size is appended before it ends the loop.  With no candidate left the
+    reference goes on into undefined behaviour; this stops."""
+    cands = [np.asarray(c, np.int32).reshape(-1, 2) for c in cands]
+    matches = [[] for _ in cands]
+    rounds = [[] for _ in cands]
+    left = [max_rounds] * len(cands)
+    live = [p for p in range(len(cands)) if cands[p].shape[0] > 0]
+    while live:
+        nxt = []
+        for p, (steps, g) in zip(live, run(live, cands)):
+            win = cands[p][g]
+            matches[p].extend(win.tolist())
+            rounds[p].append((int(cands[p].shape[0]), int(steps), int(len(g))))
+            cands[p] = remove_candidates(cands[p], win)
+            more = left[p] != 0
+            left[p] -= 1
+            if more and len(g) >= min_group_size and cands[p].shape[0] > 0:
+                nxt.append(p)
+        live = nxt
+    return matches, rounds
+
+
+def _result(fa: Features, fb: Features, matches, rounds) -> MatchResult:
+    m = np.array(matches, np.int32).reshape(-1, 2)
+    return MatchResult(m, fa.xy[m[:, 0]].copy(), fb.xy[m[:, 1]].copy(), rounds)
+
+
+def gt_match_batch(pairs, lam: float = 1e-5, pop_threshold: float = 0.7, min_group_size: int = 5, max_rounds: int = 20, k: int = 3,
+                   skip_gt: bool = False, nndr: float = 0.25, toll: float = 1e-20, max_iters: int = 50000, ctx=None):
+    """wass_match's matching (wass_match.cpp:211-235) for several pairs of pictures at once: pairs is a list of (Features of A,
+    Features of B).  The rounds run in lockstep, one launch per round for all the pairs still matching; a pair that has finished
+    drops out.  Pair i of a batch gives bit for bit what it gives alone.  The defaults are those of matcher_config.txt.
+
+    A round: payoff matrix, dynamics from the uniform start, the group above max(x) * pop_threshold appended to the matches, the
+    removal loop.  The loop is the reference's do ... while (max_rounds-- && continue_matching): up to max_rounds + 1 rounds, and a
+    group below min_group_size is still appended before it ends the loop.  Where no candidate is left the reference is undefined;
+    this stops."""
+    pairs = list(pairs)
+    for fa, fb in pairs:
+        if not isinstance(fa, Features) or not isinstance(fb, Features):
+            raise ValueError("gt_match: pairs of Features")
+        _check_knn(len(fa), fa.desc.shape[1], len(fb), fb.desc.shape[1], k)
+        if not skip_gt and len(fa) * min(k, len(fb)) > MAX_N:
+            raise ValueError(f"{len(fa)} features with {min(k, len(fb))} candidates each are above the cap of {MAX_N} candidates")
+    if not pairs:
+        return []
+    import torch
+    ctx = _context(ctx)
+    dev = torch.device("cuda", ctx.device_id)
+    knn = [knn_candidates(fa.desc, fb.desc, k, ctx) for fa, fb in pairs]
+    if skip_gt:
+        return [_result(fa, fb, nndr_matches(idx, dist, k, nndr), []) for (fa, fb), (idx, dist) in zip(pairs, knn)]
+    for idx, _ in knn:
+        if idx.min() < 0:
+            raise ValueError("a feature has fewer comparable neighbours than candidates (descriptors that are not numbers?)")
+    cands = [candidate_list(idx) for idx, _ in knn]
+    tables = [(fa.table(), fb.table()) for fa, fb in pairs]
+
+    def run(live, cands):
+        nmax = max(cands[p].shape[0] for p in live)
+        per = max(1, int(BATCH_BYTES // (nmax * nmax * 8)))
+        out = []
+        for c0 in range(0, len(live), per):
+            chunk = live[c0:c0 + per]
+            nb_, cn = len(chunk), max(cands[p].shape[0] for p in chunk)
+            am, bm = max(tables[p][0].shape[0] for p in chunk), max(tables[p][1].shape[0] for p in chunk)
+            h_fa, h_fb, h_c = np.zeros((nb_, am, 4), np.float32), np.zeros((nb_, bm, 4), np.float32), np.zeros((nb_, cn, 2), np.int32)
+            for q, p in enumerate(chunk):
+                h_fa[q, :tables[p][0].shape[0]], h_fb[q, :tables[p][1].shape[0]] = tables[p]
+                h_c[q, :cands[p].shape[0]] = cands[p]
+            d_fa, d_fb, d_c = torch.from_numpy(h_fa).to(dev), torch.from_numpy(h_fb).to(dev), torch.from_numpy(h_c).to(dev)
+            d_A = torch.empty(nb_ * cn * cn, dtype=torch.float64, device=dev)
+            d_x = torch.zeros((nb_, cn), dtype=torch.float64, device=dev)
+            d_g = torch.zeros((nb_, cn), dtype=torch.uint8, device=dev)
+            steps, gsz, err = (C.c_int * nb_)(), (C.c_int * nb_)(), (C.c_double * nb_)()
+            torch.cuda.synchronize()
+            ctx._check(ctx._lib.wass_match_round_dev(
+                ctx._h, d_fa.data_ptr(), am * 4, d_fb.data_ptr(), bm * 4, d_c.data_ptr(), cn * 2, _ints([cands[p].shape[0] for p in chunk]),
+                _ints([tables[p][0].shape[0] for p in chunk]), _ints([tables[p][1].shape[0] for p in chunk]), nb_, C.c_double(lam),
+                C.c_double(toll), int(max_iters), C.c_double(pop_threshold), d_A.data_ptr(), cn * cn, d_x.data_ptr(), cn, steps, err,
+                d_g.data_ptr(), cn, gsz))
+            hg = d_g.cpu().numpy()
+            del d_A
+            out.extend((int(steps[q]), np.flatnonzero(hg[q, :cands[p].shape[0]])) for q, p in enumerate(chunk))
+        return out
+
+    matches, rounds = round_loop(cands, run, min_group_size, max_rounds)
+    return [_result(fa, fb, matches[p], rounds[p]) for p, (fa, fb) in enumerate(pairs)]
+
+
+def gt_match(fa: Features, fb: Features, lam: float = 1e-5, pop_threshold: float = 0.7, min_group_size: int = 5, max_rounds: int = 20,
+             k: int = 3, skip_gt: bool = False, nndr: float = 0.25, toll: float = 1e-20, max_iters: int = 50000, ctx=None) -> MatchResult:
+    """One pair of pictures: gt_match_batch of one."""
+    return gt_match_batch([(fa, fb)], lam, pop_threshold, min_group_size, max_rounds, k, skip_gt, nndr, toll, max_iters, ctx)[0]
