@@ -952,6 +952,56 @@ int wass_match_round_dev(wass_ctx* ctx, const float* d_fa, size_t fa_stride, con
                          int max_iters, double pop_threshold, double* d_A, size_t A_stride, double* d_x, size_t x_stride, int* steps,
                          double* err, uint8_t* d_group, size_t group_stride, int* group_size);
 
+/* ---- Essential-matrix filter: what wass_match does after matches_unfiltered.txt (wass_match.cpp:250-358), cv::findEssentialMat's
+ * RANSAC as array functions.  A match is two points in normalised coordinates, x0 = K0^-1 (u0, v0, 1) and x1 = K1^-1 (u1, v1, 1),
+ * two fp64 each; E (row-major 3 x 3 fp64) satisfies x1' E x0 = 0.  Everything is fp64 without contraction.
+ *
+ * wass_epi_solve5: a sample is five int32 indices into a pair's matches; it gives up to WASS_EPI_MAX_SOL essential matrices (the
+ * five-point problem, Nister 2004): the null space of the 5 x 9 constraint matrix (Gauss-Jordan with complete pivoting, then
+ * Gram-Schmidt), the ten cubic constraints det E = 0 and 2 E E' E - tr(E E') E = 0 on E = x X + y Y + z Z + W, Gauss-Jordan with
+ * partial pivoting, the degree-10 polynomial in z, its real roots (those in [-1, 1], and 1 / z in [-1, 1] from the reversed
+ * polynomial; each isolated between the roots of the derivative before it and bisected), x and y from the null vector of the 3 x 3
+ * polynomial matrix at the root, three Gauss-Newton steps on the ten constraints.  Per sample: nsol, and ten slots of which the
+ * first nsol hold the solutions scaled to Frobenius norm 1, by ascending z, the others zero.  A solution with an entry that is not
+ * finite is dropped; a rank-deficient sample gives the finite solutions it has, possibly none, never a NaN.  The output depends on
+ * the sample alone: not on the launch, the batch or the other samples.  One hypothesis per thread, workgroups of 64.
+ *
+ * wass_epi_score: the inlier count of every model over every match of its pair.  With a = x0, b = x1 and E row-major:
+ *     l0 = (E0 ax + E1 ay) + E2    l1 = (E3 ax + E4 ay) + E5    l2 = (E6 ax + E7 ay) + E8            (E x0)
+ *     r0 = (E0 bx + E3 by) + E6    r1 = (E1 bx + E4 by) + E7                                         (E' x1)
+ *     num = (bx l0 + by l1) + l2   den = ((l0 l0 + l1 l1) + r0 r0) + r1 r1
+ *     err = (float)((num num) / den)                                            the squared Sampson distance
+ * every product and sum rounded on its own in fp64; a match is an inlier when err <= (float)(t * t).  A comparison with NaN is
+ * false: a NaN match, and every match of a model of zeros, is no inlier.  counts are int32 and exact.  d_nsol (may be null): the
+ * models are rounds x 10 slots of wass_epi_solve5 and a slot at or above its sample's nsol gets the count -1.
+ *
+ * wass_epi_mask: mask (uint8) and err (float32) of one model per pair, the same arithmetic.
+ *
+ * wass_epi_find: the chain solve5 -> score -> best -> mask with no host synchronisation in between.  The best model has the
+ * largest count; of equal counts the lowest model index sample * 10 + solution wins (the reference's strict >).  E (host, 9 per
+ * pair), best_index and best_count (host, one per pair; index -1 and a zero E when no sample gave a solution), and the best
+ * model's mask and err in device memory.
+ *
+ * All forms take `batch` pairs in device memory: pair p has m[p] matches and the threshold t[p] (m, t: host arrays) and lives at base + p * stride; strides
+ * in elements (fp64 for points, int32 for samples, bytes / float32 for mask / err); every pair has `rounds` samples or `nmodels`
+ * models, tightly packed.  With batch == 1 the strides are not read.  A pair of a batch gives bit for bit what it gives alone.  A
+ * sample index outside [0, m[p]) is WASS_ERR_INVALID_ARG after the launch, which reads nothing out of bounds.
+ * 5 <= m[p] <= WASS_EPI_MAX_M, 1 <= rounds <= WASS_EPI_MAX_ROUNDS.  wass_epi_scratch_bytes: the context's own device memory for
+ * wass_epi_find; no GPU needed.  Every call returns after a synchronisation. */
+#define WASS_EPI_MAX_SOL 10
+#define WASS_EPI_MAX_ROUNDS 65536
+#define WASS_EPI_MAX_M (1 << 22)
+int wass_epi_scratch_bytes(int batch, int rounds, size_t* bytes);
+int wass_epi_solve5_dev(wass_ctx* ctx, const double* d_x0, const double* d_x1, size_t pt_stride, const int32_t* d_samples,
+                        size_t sample_stride, const int* m, int rounds, int batch, double* d_E, int32_t* d_nsol);
+int wass_epi_score_dev(wass_ctx* ctx, const double* d_E, int nmodels, const int32_t* d_nsol, const double* d_x0, const double* d_x1,
+                       size_t pt_stride, const int* m, const double* t, int batch, int32_t* d_counts);
+int wass_epi_mask_dev(wass_ctx* ctx, const double* d_E, const double* d_x0, const double* d_x1, size_t pt_stride, const int* m, const double* t,
+                      int batch, uint8_t* d_mask, float* d_err, size_t out_stride);
+int wass_epi_find_dev(wass_ctx* ctx, const double* d_x0, const double* d_x1, size_t pt_stride, const int32_t* d_samples,
+                      size_t sample_stride, const int* m, const double* t, int rounds, int batch, double* E, int* best_index, int* best_count,
+                      uint8_t* d_mask, float* d_err, size_t out_stride);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

@@ -290,6 +290,12 @@ SYMBOLS = {
                                   C.POINTER(C.c_double), _vp, _sz, C.POINTER(_i)]),
     "wass_match_round_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, C.c_double, C.c_double, _i,
                                   C.c_double, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _vp, _sz, C.POINTER(_i)]),
+    "wass_epi_scratch_bytes": (_i, [_i, _i, C.POINTER(_sz)]),
+    "wass_epi_solve5_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, C.POINTER(_i), _i, _i, _vp, _vp]),
+    "wass_epi_score_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _i, _vp]),
+    "wass_epi_mask_dev": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _i, _vp, _vp, _sz]),
+    "wass_epi_find_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _i, _i, _vp, C.POINTER(_i), C.POINTER(_i),
+                               _vp, _vp, _sz]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),
