@@ -548,3 +548,47 @@ def sea(w, h, seed=0, noise=0.05, flat_x=None):
         x = np.full((h, w), float(flat_x))
     z = (-d - n[0] * x - n[1] * y) / n[2] + rng.normal(0, noise, (h, w))
     return np.ascontiguousarray(np.stack([x, y, z], -1)), np.array([*n, d])
+
+
+# ---- the plane stages on a shared device record ----
+RECORD_SHAPES = [(1, 1), (65, 9), (257, 5)]
+EXACT_REFINE = dict(max_distance=1e4, weight_by_distance=False)       # every valid point of exact_sea is a refinement inlier, weight 1
+
+
+def exact_sea(w, h, seed=0):
+    """A rough tilted plane whose refinement gives the same bits in ANY summation order: x = column, y = row,
+    z = 20 + (u + 2 v + k) / 8 with k in -4 .. 4, and the number of valid points the largest power of two <= w h.  With
+    EXACT_REFINE the sums of pass 0 are integers / 8, the centroid is such a sum over a power of two, and the scatter sums are
+    integers over (8 n)^2 that stay below 2^53 (tests/test_mesh_edges.py computes them in integers): no partial sum is ever
+    rounded, so a tree of block sums and the reference's raster loop agree exactly.  Returns (valid, p3d)."""
+    rng = np.random.default_rng(31 * w + h + seed)
+    n = 1 << int(np.floor(np.log2(w * h)))
+    valid = np.zeros(w * h, np.uint8)
+    valid[rng.permutation(w * h)[:n]] = 1
+    vv, uu = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    z = 20.0 + (uu + 2 * vv + rng.integers(-4, 5, (h, w))) / 8.0
+    valid = valid.reshape(h, w)
+    p3d = np.stack([uu.astype(np.float64), vv.astype(np.float64), z], -1)
+    p3d[valid == 0] = 0
+    return valid, np.ascontiguousarray(p3d)
+
+
+def sparse_sea(w, h):
+    """exact_sea(seed=1) with every 20th of its points valid, at most w h // 20: no plane can reach the w h / 10 inliers that ransac_find_plane asks
+    for (PovMesh.cpp:773), so RANSAC reports "not found" -- except at 1 x 1, where the limit is 0 and nothing is valid."""
+    valid, p3d = exact_sea(w, h, seed=1)
+    keep = np.flatnonzero(valid.ravel())[::20][:(w * h) // 20]
+    valid = np.zeros(w * h, np.uint8)
+    valid[keep] = 1
+    valid = valid.reshape(h, w)
+    p3d[valid == 0] = 0
+    return valid, p3d
+
+
+def record_samples(w, h, rounds=64):
+    """sample triples of three different pixels, uv (rounds, 6); the one pixel three times at 1 x 1"""
+    if w * h < 3:
+        return np.zeros((1, 6), np.int32)
+    rng = np.random.default_rng(w + 1000 * h)
+    px = np.array([rng.choice(w * h, 3, replace=False) for _ in range(rounds)])
+    return np.ascontiguousarray(np.stack([px % w, px // w], -1).reshape(rounds, 6).astype(np.int32))

@@ -328,3 +328,56 @@ def test_refinement_inlier_reference_is_the_formula_of_the_existing_test():
         got, n = M.refinement_inliers(valid, p3d, 10, central, **kw)
         np.testing.assert_array_equal(got, p3d[ok][::10])
         assert n == ok.sum() > 100
+
+
+# ----------------------------------------------------------------------------------------- the plane stages on a shared device record
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_exact_sea_refines_to_the_same_bits_in_any_summation_order(oracle, shape):
+    """What lets the GPU tests compare refine_plane with the C oracle by equality: with EXACT_REFINE every sum of the refinement is an
+    integer multiple of a power of two and the sums of the magnitudes stay below 2^53, so no order of additions rounds anything.  The
+    moments of the C oracle's raster loop equal the integer computation exactly."""
+    w, h = shape
+    valid, p3d = M.exact_sea(w, h)
+    n = int(valid.sum())
+    assert n & (n - 1) == 0 and w * h // 2 < n <= w * h                       # a power of two
+    P = np.rint(p3d[valid != 0] * 8).astype(np.int64)
+    assert (P / 8.0 == p3d[valid != 0]).all()
+    plane, cnt, mom = oracle.refine_plane(valid, p3d, **M.EXACT_REFINE)
+    assert cnt == n
+    if n < 3:
+        return                                                              # 1 x 1: the refusal with one inlier
+    S = P.sum(0)
+    Q = P * n - S                                                           # 8 n (p - centroid), integers
+    A = Q.T @ Q
+    bound = (np.abs(Q).T @ np.abs(Q)).max()
+    print(f"{w}x{h}: {n} inliers, largest sum of |terms| 2^{np.log2(float(bound)):.1f} in units of 1 / (8 n)^2, plane {plane}")
+    assert bound < 2 ** 53 and np.abs(S).max() < 2 ** 53
+    assert mom[0] == n
+    np.testing.assert_array_equal(mom[1:4], S / (8.0 * n))
+    np.testing.assert_array_equal(mom[4:13], (A / (8.0 * n) ** 2).ravel())
+    assert abs(plane[0]) > 0.05 and abs(plane[1]) > 0.05                    # tilted in both directions: no axis drops out of the solve
+    # a crop by the refined plane that keeps some points and drops some; the numpy reference equals the C oracle
+    m, k = M.crop(valid, p3d, plane, 0.25)
+    om, ok_ = oracle.crop_plane(valid, p3d, plane, 0.25)
+    assert k == ok_ and n // 4 < k < 3 * n // 4
+    np.testing.assert_array_equal(m, om)
+    # the default RANSAC band holds every point for the candidate that wins: the refinement behind the fused call's crop sees the same n
+    uv = M.record_samples(w, h)
+    found, rpl, best, per = oracle.ransac_plane(valid, p3d, uv, 1.0)
+    assert found and best == n == M.crop(valid, p3d, rpl, 1.0)[1]
+    # ... and a narrow band separates the candidates: the choice among them is a real one
+    found, rpl, best, per = oracle.ransac_plane(valid, p3d, uv, 0.3)
+    assert found and n // 10 <= best < n and len(set(int(c) for c in per if c > 0)) > 5
+
+
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_sparse_sea_has_no_plane(oracle, shape):
+    """the mesh whose fit leaves "no plane found" and "not refined" behind in the record: best < w h / 10 in the oracle.  At 1 x 1 the
+    limit is 0: found with nothing valid, and the refinement is what fails."""
+    w, h = shape
+    valid, p3d = M.sparse_sea(w, h)
+    found, plane, best, per = oracle.ransac_plane(valid, p3d, M.record_samples(w, h), 1.0)
+    print(f"{w}x{h}: {int(valid.sum())} valid, best {best}, limit {w * h // 10}, found {found}")
+    assert (3 <= int(valid.sum()) <= w * h // 20 or w * h == 1 and not valid.any()) and (plane == 0).all()
+    assert (best < w * h // 10 and not found) if w * h > 1 else (best == 0 and found)
+    assert oracle.refine_plane(valid, p3d, **M.EXACT_REFINE)[1] == int(valid.sum())

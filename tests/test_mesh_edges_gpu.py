@@ -2,11 +2,12 @@
 Context.mesh_upload and the Mesh methods, against the numpy / fp64 references of tests/mesh_oracle.py and the C oracle.
 
 Every comparison is an equality.  The only tolerances are the two tests/test_post_mesh_gpu.py states: refine_plane (fp64 sums in a
-tree order, atol 1e-9) does not occur here because the fused calls are compared with the stage-by-stage calls, which sum in the
-same order; the triangulation allows two validity flips from acos and rtol = atol = 1e-12 on the points.
+tree order, atol 1e-9) does not occur here: the fused calls are compared with the stage-by-stage calls, which run the same
+kernels, and both with the C oracle on mesh_oracle.exact_sea, whose sums no order of additions rounds; the triangulation allows
+two validity flips from acos and rtol = atol = 1e-12 on the points.
 
 Shapes: wass_mesh_upload accepts every width, height >= 1, so every shape of mesh_oracle.SMALL runs every stage; the kernels'
-guards for them (k_zgaps, k_gap_hist: 1 <= j < w - 1 and i >= 1; hlink / vlink) were read before the first run.
+guards for them (k_gap_hist: 1 <= j < w - 1 and i >= 1; hlink / vlink) were read before the first run.
 NaN heights are left out of the percentile: the reference sorts them with a comparison that is not a strict weak order then, and the
 result of that is not defined.  What tests/test_mesh_edges.py proves on the CPU -- every probe scene is changed by the wrong variant
 named there -- gives these comparisons their power."""
@@ -19,7 +20,7 @@ import wass_amd
 pytestmark = pytest.mark.gpu
 
 ids = lambda c: "x".join(str(v) for v in c) if isinstance(c, tuple) else str(c)
-WASS_ERR_INVALID_ARG, WASS_ERR_UNSUPPORTED = -1, -2
+WASS_ERR_INVALID_ARG, WASS_ERR_UNSUPPORTED, WASS_ERR_TOO_FEW_POINTS = -1, -2, -6
 
 
 def _same(a, b):
@@ -33,7 +34,7 @@ def _up(ctx, valid, z):
 
 # ---------------------------------------------------------------------------------------------------------------- z-gap percentile
 def _both_percentiles(ctx, valid, z, pct, tag):
-    """gap array + k_radix_hist (zgap_percentile) and k_gap_hist + k_radix_pick (remove_outliers) against the reference"""
+    """the percentile alone (zgap_percentile) and as the first stage of the chain (remove_outliers) against the reference"""
     m, valid, p3d = _up(ctx, valid, z)
     ref = M.zgap_percentile(valid, p3d[..., 2], pct)
     a = m.zgap_percentile(pct)
@@ -366,6 +367,190 @@ def test_fused_calls_equal_the_stages_at_edge_shapes(gpu_ctx, oracle, shape):
     np.testing.assert_array_equal(np.array(fr.plane[:]), pl2)
     assert (fr.kept_after_ransac_crop, fr.refine_inliers, fr.kept_final) == (k1, ninl, k2)
     assert fr.xyzc_bytes == len(ref_bytes) and pin[:fr.xyzc_bytes].numpy().tobytes() == ref_bytes
+
+
+# ------------------------------------------------------------------------------------ the stage-by-stage calls on the chain's record
+# zgap_percentile, ransac_plane, crop_plane and refine_plane run the chain's kernels on the context's device record, with the
+# parameters the chain would find there written by the call itself.  What two separate implementations could not get wrong: a
+# record nobody initialised, a record an earlier fit left "no plane" in, a record a frame in flight is still being read from.
+# Scenes: mesh_oracle.exact_sea (the refined plane equals the C oracle's bit for bit, tests/test_mesh_edges.py shows why) and
+# sparse_sea (no plane to find).
+RP = M.EXACT_REFINE
+FUSED_RP = dict(refine_max_distance=RP["max_distance"], weight_by_distance=RP["weight_by_distance"])
+
+
+def _raw_refine(ctx, m):
+    """wass_mesh_refine_plane through the C ABI -- Mesh.refine_plane drops n_inliers when it raises: (code, message, plane, n_inliers)"""
+    import ctypes as C
+    rp = wass_amd.RefineParams(-9999.0, 9999.0, -9999.0, 9999.0, RP["max_distance"], int(RP["weight_by_distance"]), 0)
+    plane = (C.c_double * 4)(); n = C.c_uint64(12345)
+    rc = ctx._lib.wass_mesh_refine_plane(ctx._h, m._h, C.byref(rp), plane, C.byref(n))
+    return rc, ctx._lib.wass_last_error(ctx._h).decode() if rc else "", np.array(plane[:]), int(n.value)
+
+
+def _check_refine(ctx, oracle, valid, p3d):
+    m = ctx.mesh_upload(valid, p3d)
+    rc, msg, plane, n = _raw_refine(ctx, m)
+    opl, on, _ = oracle.refine_plane(valid, p3d, **RP)
+    print(f"refine_plane {valid.shape[1]}x{valid.shape[0]}: code {rc} {msg!r}, {n} inliers (oracle {on}), plane {plane} (oracle {opl})")
+    assert n == on
+    if on < 3:
+        assert (rc, msg) == (WASS_ERR_TOO_FEW_POINTS, f"plane refinement has {on} inliers")
+    else:
+        assert rc == 0
+        np.testing.assert_array_equal(plane, opl)
+    np.testing.assert_array_equal(m.download()[0], valid)             # its crop stayed off
+    return opl if on >= 3 else np.array([0.0, 0.0, 1.0, -20.0])
+
+
+def _check_crop(ctx, oracle, valid, p3d, plane, thr=0.25):
+    m = ctx.mesh_upload(valid, p3d)
+    kept = m.crop_plane(plane, thr)
+    o_mask, o_kept = oracle.crop_plane(valid, p3d, plane, thr)
+    print(f"crop_plane {valid.shape[1]}x{valid.shape[0]}: kept {kept} of {int(valid.sum())} (oracle {o_kept})")
+    assert kept == o_kept == M.crop(valid, p3d, plane, thr)[1]
+    np.testing.assert_array_equal(m.download()[0], o_mask)
+
+
+def _check_fit(ctx, oracle, valid, p3d, uv, thr=1.0, maxd=0.25):
+    """fit_plane against ransac_plane -> crop -> refine_plane -> crop of the references"""
+    m = ctx.mesh_upload(valid, p3d)
+    found, rpl, best, _ = oracle.ransac_plane(valid, p3d, uv, thr)
+    m1, k1 = M.crop(valid, p3d, rpl, thr) if found else (valid, 0)
+    pl2, ninl, _ = oracle.refine_plane(m1, p3d, **RP)
+    if found and ninl < 3:
+        with pytest.raises(wass_amd.WassError) as e:
+            m.fit_plane(uv, thr, maxd, **FUSED_RP)
+        assert e.value.code == WASS_ERR_TOO_FEW_POINTS
+        return
+    res = m.fit_plane(uv, thr, maxd, **FUSED_RP)
+    print(f"fit_plane {valid.shape[1]}x{valid.shape[0]}: found {res.found} best {res.ransac_inliers} (oracle {found}, {best}), kept {res.kept_after_ransac_crop}"
+          f" -> refine {res.refine_inliers} -> kept {res.kept_final}")
+    assert (bool(res.found), res.ransac_inliers) == (found, best)
+    np.testing.assert_array_equal(np.array(res.ransac_plane[:]), rpl)
+    if not found:
+        assert np.isnan(np.array(res.plane[:])).all() and (res.kept_after_ransac_crop, res.refine_inliers, res.kept_final) == (0, 0, 0)
+        np.testing.assert_array_equal(m.download()[0], valid)
+        return
+    m2, k2 = M.crop(m1, p3d, pl2, maxd)
+    assert (res.kept_after_ransac_crop, res.refine_inliers, res.kept_final) == (k1, ninl, k2)
+    np.testing.assert_array_equal(np.array(res.plane[:]), pl2)
+    np.testing.assert_array_equal(m.download()[0], m2)
+
+
+@pytest.mark.parametrize("first", ["crop_plane", "refine_plane"])
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_the_first_call_on_a_fresh_context(oracle, shape, first):
+    """no percentile, RANSAC or fused call has initialised the record before"""
+    valid, p3d = M.exact_sea(*shape)
+    plane = oracle.refine_plane(valid, p3d, **RP)[0] if valid.sum() >= 3 else np.array([0.0, 0.0, 1.0, -20.0])
+    with wass_amd.Context(0) as ctx:
+        if first == "crop_plane":
+            _check_crop(ctx, oracle, valid, p3d, plane)
+        else:
+            _check_refine(ctx, oracle, valid, p3d)
+
+
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_a_record_left_without_a_plane_and_the_other_order(gpu_ctx, oracle, shape):
+    """fit_plane on sparse_sea leaves ransac_found = refine_ok = 0 in the record (1 x 1: found, not refined); refine_plane and
+    crop_plane on another mesh must read switch words of their own.  Then the other order: the fused call after them."""
+    w, h = shape
+    uv = M.record_samples(w, h)
+    _check_fit(gpu_ctx, oracle, *M.sparse_sea(w, h), uv)
+    valid, p3d = M.exact_sea(w, h)
+    plane = _check_refine(gpu_ctx, oracle, valid, p3d)
+    _check_fit(gpu_ctx, oracle, *M.sparse_sea(w, h), uv)
+    _check_crop(gpu_ctx, oracle, valid, p3d, plane)
+    _check_fit(gpu_ctx, oracle, valid, p3d, uv)
+
+
+FRAME_FIELDS = ("n_gaps", "component_size", "found", "refine_ok", "ransac_inliers", "refine_inliers", "kept_after_ransac_crop", "kept_final",
+                "n_points", "xyzc_bytes")
+
+
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_stage_by_stage_calls_while_a_frame_is_in_flight(gpu_ctx, oracle, shape):
+    """finish_frame_async for mesh A, the four calls on mesh B before A's record is read: A's result and bytes are those of A run
+    alone, B's results the references'.  Once: an ordering check."""
+    import torch
+    w, h = shape
+    uv = M.record_samples(w, h)
+    va, pa = M.exact_sea(w, h, seed=2)
+    vb, pb = M.exact_sea(w, h)
+    z_ref = M.zgap_percentile(vb, pb[..., 2], 99.0)
+    r_found, r_plane, r_best, _ = oracle.ransac_plane(vb, pb, uv, 0.3)
+    p_ref, n_ref, _ = oracle.refine_plane(vb, pb, **RP)
+    crop_by = p_ref if n_ref >= 3 else np.array([0.0, 0.0, 1.0, -20.0])
+    c_mask, c_kept = oracle.crop_plane(vb, pb, crop_by, 0.25)
+
+    def frame(between):
+        pin = torch.zeros(148 + 6 * w * h, dtype=torch.uint8).pin_memory()
+        a = gpu_ctx.mesh_upload(va, pa)
+        a.finish_frame_async(uv, pin.data_ptr(), pin.numel(), **FUSED_RP)
+        got = between()
+        fr = gpu_ctx.frame_result()
+        return fr, pin[:fr.xyzc_bytes].numpy().tobytes(), got
+
+    def four_calls():
+        b = gpu_ctx.mesh_upload(vb, pb)
+        zg = b.zgap_percentile(99.0)
+        rs = b.ransac_plane(uv, 0.3)
+        rf = _raw_refine(gpu_ctx, b)
+        kept = b.crop_plane(crop_by, 0.25)
+        return zg, rs, rf, kept, b.download()[0]
+
+    alone, alone_bytes, _ = frame(lambda: None)
+    fr, fr_bytes, (zg, rs, rf, kept, mask) = frame(four_calls)
+    print(f"{w}x{h}: frame {[getattr(fr, k) for k in FRAME_FIELDS]} zgap {fr.zgap}; between: zgap {zg}, RANSAC {rs[0], rs[2]}, refine {rf[0], rf[3]}, kept {kept}")
+    assert [getattr(fr, k) for k in FRAME_FIELDS] == [getattr(alone, k) for k in FRAME_FIELDS] and _same(fr.zgap, alone.zgap)
+    np.testing.assert_array_equal(np.array(fr.ransac_plane[:]), np.array(alone.ransac_plane[:]))
+    np.testing.assert_array_equal(np.array(fr.plane[:]), np.array(alone.plane[:]))
+    assert fr_bytes == alone_bytes and len(fr_bytes) == 148 + 6 * fr.n_points
+    assert _same(zg[0], z_ref[0]) and zg[1] == z_ref[1]
+    assert (rs[0], rs[2]) == (r_found, r_best)
+    np.testing.assert_array_equal(rs[1], r_plane)
+    assert rf[3] == n_ref and rf[0] == (0 if n_ref >= 3 else WASS_ERR_TOO_FEW_POINTS)
+    if n_ref >= 3:
+        np.testing.assert_array_equal(rf[2], p_ref)
+    assert kept == c_kept
+    np.testing.assert_array_equal(mask, c_mask)
+
+
+def test_the_refusals_answer_as_before(gpu_ctx, oracle):
+    """What test_ransac_1800_rounds_and_the_refusals, test_ransac_degenerate_triple_and_one_pixel_mesh and the small shapes of the
+    percentile test do not already hold: refine_plane's refusal with its inlier count, samples on invalid pixels only, the
+    percentile at 1 x 5 and 5 x 1, a bad sample through fit_plane, and the mesh untouched by every refused call."""
+    w, h = 65, 9
+    full, p3d = M.exact_sea(w, h)
+    for n in (0, 1, 2):
+        valid = np.zeros((h, w), np.uint8)
+        valid.ravel()[np.flatnonzero(full.ravel())[:n]] = 1
+        assert int(valid.sum()) == n
+        _check_refine(gpu_ctx, oracle, valid, p3d * valid[..., None])
+    # every sample on an invalid pixel: no candidate at all
+    valid = full.copy()
+    valid[0, 0] = valid[0, 1] = valid[1, 0] = 0
+    uv = np.array([[0, 0, 1, 0, 0, 1]] * 3, np.int32)
+    m = gpu_ctx.mesh_upload(valid, p3d)
+    found, plane, best = m.ransac_plane(uv, 1.0)
+    ok, opl, obest, _ = oracle.ransac_plane(valid, p3d, uv, 1.0)
+    assert (found, best) == (ok, obest) == (False, 0) and (plane == 0).all() and (opl == 0).all()
+    for ww, hh in ((1, 5), (5, 1)):
+        v1, z1 = M.holes(ww, hh, frac=0.0)
+        got = gpu_ctx.mesh_upload(*M.as_mesh(v1, z1)).zgap_percentile(50.0)
+        assert got[0] != got[0] and got[1] == 0 and M.zgap_percentile(v1, z1, 50.0)[1] == 0
+    # refused before anything is enqueued, by both tiers: the valid plane is as uploaded
+    many = np.tile(M.record_samples(w, h), (29, 1))[:1801]
+    for bad in (many, np.array([[0, 0, w, 1, 2, 2]], np.int32)):
+        code = WASS_ERR_UNSUPPORTED if len(bad) == 1801 else WASS_ERR_INVALID_ARG
+        for call in (lambda: m.ransac_plane(bad, 1.0), lambda: m.fit_plane(bad, 1.0, 0.25, **FUSED_RP)):
+            with pytest.raises(wass_amd.WassError) as e:
+                call()
+            assert e.value.code == code
+    np.testing.assert_array_equal(m.download()[0], valid)
+    res = m.fit_plane(many[:1800], 1.0, 0.25, **FUSED_RP)             # ... and the mesh still fits
+    assert res.found and res.kept_final < res.kept_after_ransac_crop
 
 
 # ----------------------------------------------------------------------------------------------------------------- triangulation

@@ -190,51 +190,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, WAS
     if ((threadIdx.x & 63) == 0 && found) atomicAdd(count + slot_of_block(), (unsigned long long)found);
 }
 
-// ------------------------------------------------------------------ z-gap percentile (PovMesh.cpp:888-926)
-// gaps[3*idx + k] = |z - z(neighbour k in the row above)| as the fp64 bit pattern, ~0 when absent.
-__global__ void __launch_bounds__(256) k_zgaps(const uint8_t* __restrict__ valid, const double* __restrict__ Z, int w, int h,
-                                               unsigned long long* __restrict__ gaps, unsigned long long* __restrict__ count)
-{
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    const int i = blockIdx.y;
-    if (j >= w) return;
-    const size_t c = (size_t)i * w + j;
-    unsigned long long g[3] = { ~0ull, ~0ull, ~0ull };
-    int n = 0;
-    if (i >= 1 && j >= 1 && j < w - 1 && valid[c]) {
-        const double z = Z[c];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const size_t nb = c - w - 1 + k;
-            if (valid[nb]) { g[k] = (unsigned long long)__double_as_longlong(fabs(z - Z[nb])); ++n; }
-        }
-    }
-    gaps[3 * c] = g[0]; gaps[3 * c + 1] = g[1]; gaps[3 * c + 2] = g[2];
-    // wave-level count
-    int s = n;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(count + slot_of_block(), (unsigned long long)s);
-}
-
-// one MSD radix-select pass: histogram of an 11-bit digit among keys whose higher bits equal `prefix`
-__global__ void __launch_bounds__(256) k_radix_hist(const unsigned long long* __restrict__ keys, size_t n, int shift,
-                                                    unsigned int mask, int hi_shift, unsigned long long prefix,
-                                                    unsigned int* __restrict__ hist)
-{
-    __shared__ unsigned int lh[2048];
-    for (int i = threadIdx.x; i < 2048; i += 256) lh[i] = 0;
-    __syncthreads();
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const unsigned long long k = keys[i];
-        if (k == ~0ull) continue;
-        if (hi_shift < 64 && (k >> hi_shift) != prefix) continue;
-        atomicAdd(&lh[(unsigned)(k >> shift) & mask], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2048; i += 256)
-        if (lh[i]) atomicAdd(&hist[i], lh[i]);
-}
-
 // ------------------------------------------------------------------ connected components (PovMesh.cpp:929-987)
 // Union-find over RASTER indices (coalesced, neighbours are near in memory).  Horizontal runs are
 // labelled up front by a segmented scan, so the merge pass only stitches runs that touch vertically.
@@ -389,7 +344,7 @@ struct DevState {
     int sel_hi_shift, sel_fail;
     double zgap;
     unsigned long long ccl_best;                          // (size << 32) | ~mincm of the winning component
-    int ransac_found, pad0;
+    int ransac_found, zero;                               // zero: the crop switch of a refinement without a crop (wass_mesh_refine_plane)
     unsigned long long ransac_best;
     double ransac_plane[4];
     double wsum, centroid[3], ninl;
@@ -405,7 +360,8 @@ struct DevState {
     unsigned long long inl_text_bytes;                    // ... bytes of that file's text when the device formatted it, numbers it could not format
 };
 
-// z gaps computed on the fly (no gap array): histogram of one 11-bit digit of the fp64 bit patterns that match the
+// ------------------------------------------------------------------ z-gap percentile (PovMesh.cpp:888-926)
+// |z - z(neighbour k in the row above)|, k = -1, 0, +1, computed on the fly (no gap array): histogram of one 11-bit digit of the fp64 bit patterns that match the
 // prefix found so far.  Blocks own a 256-column strip and walk rows (no index divisions); their totals go to one of
 // GAP_HIST_COPIES copies of the global histogram (same-address atomics serialise), which k_radix_pick adds up.
 constexpr int GAP_HIST_COPIES = 4;
@@ -654,22 +610,6 @@ __global__ void __launch_bounds__(256) k_ransac_score(const uint8_t* __restrict_
         if (lc[r]) atomicAdd(&counts[r], (unsigned long long)lc[r]);
 }
 
-// ------------------------------------------------------------------ crop_plane (PovMesh.cpp:780-815)
-__global__ void __launch_bounds__(256) k_crop_plane(uint8_t* __restrict__ valid, const double* __restrict__ X,
-                                                    const double* __restrict__ Y, const double* __restrict__ Z, size_t n,
-                                                    double a, double b, double c, double d, double thr,
-                                                    unsigned long long* __restrict__ kept)
-{
-    unsigned int cnt = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        if (valid[i]) {
-            if (fabs((a * X[i] + b * Y[i] + c * Z[i]) + d) < thr) ++cnt; else valid[i] = 0;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept + slot_of_block(), (unsigned long long)cnt);
-}
-
 // first strictly better candidate wins (PovMesh.cpp:750-755); failure if best < W*H/10 (:773)
 __global__ void __launch_bounds__(64) k_ransac_pick(const PlaneCand* __restrict__ cand, const unsigned long long* __restrict__ counts,
                                                     int rounds, size_t n, DevState* __restrict__ ds)
@@ -697,7 +637,9 @@ __global__ void __launch_bounds__(64) k_ransac_pick(const PlaneCand* __restrict_
         ds->ransac_found = best < n / 10 ? 0 : 1;
     }
 }
-// crop_plane with the plane (and the "RANSAC succeeded" switch) read from device memory
+
+// ------------------------------------------------------------------ crop_plane (PovMesh.cpp:780-815)
+// the plane and the switch (a plane was found / refined, or the 1 that wass_mesh_crop_plane writes) are read from device memory
 __global__ void __launch_bounds__(256) k_crop_plane_dev(uint8_t* __restrict__ valid, const double* __restrict__ X,
                                                         const double* __restrict__ Y, const double* __restrict__ Z, size_t n,
                                                         const double* __restrict__ plane, const int* __restrict__ enable,
@@ -718,8 +660,8 @@ __global__ void __launch_bounds__(256) k_crop_plane_dev(uint8_t* __restrict__ va
 // ------------------------------------------------------------------ refine_plane (PovMesh.cpp:581-660)
 struct RefineDev { double xmin, xmax, ymin, ymax, maxd; int weighted, umin, umax, vmin, vmax; };
 
-// block-level sum of NV doubles; partial sums go to out[block][NV] and are added on the host in block
-// order, so the result does not depend on scheduling
+// block-level sum of NV doubles; partial sums go to out[block][NV] and are added in a fixed order
+// (sum_partials_wave), so the result does not depend on scheduling
 template <int NV>
 __device__ __forceinline__ void block_sum_store(double (&v)[NV], double* __restrict__ out)
 {
@@ -750,23 +692,9 @@ __device__ __forceinline__ bool refine_inlier(const RefineDev& rp, const uint8_t
     return true;
 }
 
-// pass 0: {count, wsum, sum w*x, sum w*y, sum w*z}
-__global__ void __launch_bounds__(256) k_refine_moments(const uint8_t* __restrict__ valid, const double* __restrict__ X,
-                                                        const double* __restrict__ Y, const double* __restrict__ Z, int w,
-                                                        size_t n, RefineDev rp, double* __restrict__ partial)
-{
-    double acc[5] = { 0, 0, 0, 0, 0 };
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        double px, py, pz, wt;
-        if (refine_inlier(rp, valid, X, Y, Z, w, i, px, py, pz, wt)) {
-            acc[0] += 1.0; acc[1] += wt; acc[2] += px * wt; acc[3] += py * wt; acc[4] += pz * wt;
-        }
-    }
-    block_sum_store<5>(acc, partial);
-}
-// crop_plane by the RANSAC plane (k_crop_plane_dev) and pass 0 of the refinement in ONE pass over the points: the same
-// walk as k_refine_moments (grid, stride and therefore summation order), with the crop decision taken -- and written to
-// valid -- just before the point is offered to the moments.
+// crop_plane by the RANSAC plane (k_crop_plane_dev) and pass 0 of the refinement, {count, wsum, sum w*x, sum w*y, sum w*z},
+// in ONE pass over the points: the crop decision is taken -- and written to valid -- just before the point is offered to
+// the moments.  With *enable == 0 it is pass 0 alone (wass_mesh_refine_plane).
 __global__ void __launch_bounds__(256) k_crop_moments_dev(uint8_t* __restrict__ valid, const double* __restrict__ X,
                                                           const double* __restrict__ Y, const double* __restrict__ Z, int w, size_t n,
                                                           const double* __restrict__ plane, const int* __restrict__ enable, double thr,
@@ -795,23 +723,6 @@ __global__ void __launch_bounds__(256) k_crop_moments_dev(uint8_t* __restrict__ 
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept + slot_of_block(), (unsigned long long)cnt);
     block_sum_store<5>(acc, partial);
-}
-// pass 1: weighted scatter matrix around the centroid (6 unique entries)
-__global__ void __launch_bounds__(256) k_refine_cov(const uint8_t* __restrict__ valid, const double* __restrict__ X,
-                                                    const double* __restrict__ Y, const double* __restrict__ Z, int w, size_t n,
-                                                    RefineDev rp, double cx, double cy, double cz,
-                                                    double* __restrict__ partial)
-{
-    double acc[6] = { 0, 0, 0, 0, 0, 0 };
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        double px, py, pz, wt;
-        if (refine_inlier(rp, valid, X, Y, Z, w, i, px, py, pz, wt)) {
-            const double qx = px - cx, qy = py - cy, qz = pz - cz;
-            acc[0] += wt * qx * qx; acc[1] += wt * qx * qy; acc[2] += wt * qx * qz;
-            acc[3] += wt * qy * qy; acc[4] += wt * qy * qz; acc[5] += wt * qz * qz;
-        }
-    }
-    block_sum_store<6>(acc, partial);
 }
 
 // plane_refinement_inliers.xyz (wass_stereo.cpp:2077-2085 writes every 10th refinement inlier, in raster order): the
@@ -933,7 +844,7 @@ __global__ void k_inl_text_totals(DevState* __restrict__ ds, const unsigned int*
 }
 
 // smallest-eigenvalue eigenvector of a symmetric 3x3 (cyclic Jacobi); stands in for row 2 of cv::SVD's vt
-__host__ __device__ static void smallest_eigvec3(const double Ain[9], double vout[3])
+__device__ static void smallest_eigvec3(const double Ain[9], double vout[3])
 {
     double A[3][3], V[3][3] = { { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 } };
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) A[i][j] = Ain[i * 3 + j];
@@ -959,10 +870,9 @@ __host__ __device__ static void smallest_eigvec3(const double Ain[9], double vou
 }
 
 
-// Sum of per-block partials in a fixed two-level order (64 strided sub-sums, then those in index order): the same
-// function runs on the host (step-by-step API) and on the device (fused API), so both give identical bits.
+// Sum of per-block partials in a fixed two-level order (64 strided sub-sums, then those in lane order)
 template <int NV>
-__host__ __device__ static void sum_partials_lane(const double* partial, int nb, int lane, double (&out)[NV])
+__device__ static void sum_partials_lane(const double* partial, int nb, int lane, double (&out)[NV])
 {
     for (int k = 0; k < NV; ++k) out[k] = 0;
     for (int b = lane; b < nb; b += 64)
@@ -979,15 +889,7 @@ __device__ static void sum_partials_wave(const double* __restrict__ partial, int
         out[k] = tot;
     }
 }
-template <int NV>
-static void sum_partials_host(const double* partial, int nb, double (&out)[NV])
-{
-    double lanes[64][NV];
-    for (int l = 0; l < 64; ++l) sum_partials_lane<NV>(partial, nb, l, lanes[l]);
-    for (int k = 0; k < NV; ++k) { double tot = 0; for (int l = 0; l < 64; ++l) tot += lanes[l][k]; out[k] = tot; }
-}
-
-// partial sums of k_refine_moments -> centroid
+// partial sums of k_crop_moments_dev -> centroid
 __global__ void k_refine_centroid(const double* __restrict__ partial, int nb, const int* __restrict__ enable, DevState* __restrict__ ds)
 {
     if (blockIdx.x) return;
@@ -999,6 +901,7 @@ __global__ void k_refine_centroid(const double* __restrict__ partial, int nb, co
     ds->refine_ok = (mom[0] >= 3 && mom[1] > 0) ? 1 : 0;
     ds->centroid[0] = mom[2] / mom[1]; ds->centroid[1] = mom[3] / mom[1]; ds->centroid[2] = mom[4] / mom[1];
 }
+// pass 1: weighted scatter matrix around the centroid (6 unique entries)
 __global__ void __launch_bounds__(256) k_refine_cov_dev(const uint8_t* __restrict__ valid, const double* __restrict__ X,
                                                         const double* __restrict__ Y, const double* __restrict__ Z, int w, size_t n,
                                                         RefineDev rp, const DevState* __restrict__ ds, double* __restrict__ partial)
@@ -1234,6 +1137,19 @@ static int mesh_alloc(wass_ctx* c, int w, int h, wass_mesh** out)
 
 static inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
 
+// refine_plane's window and limits (PovMesh.cpp:585-588)
+static RefineDev refine_dev(const wass_refine_params* rp, const wass_mesh* m)
+{
+    RefineDev rd;
+    rd.xmin = rp->xmin; rd.xmax = rp->xmax; rd.ymin = rp->ymin; rd.ymax = rp->ymax; rd.maxd = rp->max_distance;
+    rd.weighted = rp->weight_by_distance;
+    rd.umin = rp->central_third_only ? m->w / 4 : 0;
+    rd.umax = rp->central_third_only ? m->w * 3 / 4 : m->w - 1;
+    rd.vmin = rp->central_third_only ? m->h / 4 : 0;
+    rd.vmax = rp->central_third_only ? m->h * 2 / 3 : m->h - 1;
+    return rd;
+}
+
 // striped device counters (NSLOT u64) -> host sum
 static int counters_reset(wass_ctx* c, unsigned long long** cnt)
 {
@@ -1394,48 +1310,6 @@ int wass_mesh_upload(wass_ctx* c, int width, int height, const uint8_t* valid, c
     }
     if (e != hipSuccess) { wass_mesh_destroy(m); return set_err(c, WASS_ERR_DEVICE, "mesh upload: %s", hipGetErrorString(e)); }
     *out = m;
-    return WASS_OK;
-}
-
-int wass_mesh_zgap_percentile(wass_ctx* c, wass_mesh* m, double percentile, double* out, uint64_t* n_gaps)
-{
-    if (!c || !m || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
-    WASS_HIP(c, hipSetDevice(c->device));
-    const size_t n = m->n(), ng = n * 3;
-    int rc = ensure(c, c->scratch, ng * 8 + 2048 * 4 + 64);
-    if (rc) return rc;
-    unsigned long long* gaps = (unsigned long long*)c->scratch.p;
-    unsigned int* hist = (unsigned int*)(gaps + ng);
-    unsigned long long* cnt = nullptr;
-    if ((rc = counters_reset(c, &cnt))) return rc;
-    hipLaunchKernelGGL(k_zgaps, dim3((m->w + 255) / 256, m->h), dim3(256), 0, c->ts(), m->valid, m->z, m->w, m->h, gaps, cnt);
-    unsigned long long total = 0;
-    if ((rc = counters_sum(c, cnt, &total))) return rc;
-    if (n_gaps) *n_gaps = total;
-    if (total == 0) { *out = NAN; return WASS_OK; }
-    // zgaps[floor(p/100 * n)] of the sorted list (:924), index clamped to n-1
-    unsigned long long k = (unsigned long long)floor(percentile / 100.0 * (double)total);
-    if (k >= total) k = total - 1;
-    unsigned long long prefix = 0;
-    std::vector<unsigned int> hh(2048);
-    int hi_shift = 64;
-    for (int pass = 0; pass < 6; ++pass) {
-        const int shift = pass < 5 ? 64 - 11 * (pass + 1) : 0;      // 53,42,31,20,9,0 (last digit: 9 bits)
-        WASS_HIP(c, hipMemsetAsync(hist, 0, 2048 * 4, c->ts()));
-        hipLaunchKernelGGL(k_radix_hist, dim3(1024), dim3(256), 0, c->ts(), (const unsigned long long*)gaps, ng, shift,
-                           pass < 5 ? 2047u : 511u, hi_shift, prefix, hist);
-        WASS_HIP(c, hipMemcpyAsync(hh.data(), hist, 2048 * 4, hipMemcpyDeviceToHost, c->ts()));
-        WASS_HIP(c, hipStreamSynchronize(c->ts()));
-        const int nb = pass < 5 ? 2048 : 512;
-        int b = 0;
-        for (; b < nb; ++b) { if (k < hh[b]) break; k -= hh[b]; }
-        if (b >= nb) return set_err(c, WASS_ERR_DEVICE, "radix select lost its rank (internal error)");
-        prefix = (pass < 5 ? (prefix << 11) : (prefix << 9)) | (unsigned long long)b;
-        hi_shift = shift;
-    }
-    double r;
-    memcpy(&r, &prefix, 8);
-    *out = r;
     return WASS_OK;
 }
 
@@ -1643,18 +1517,19 @@ int wass_mesh_keep_biggest_component(wass_ctx* c, wass_mesh* m, double zgap, uin
     return WASS_OK;
 }
 
-// wass_stereo.cpp:2046-2050 as one call: compute_zgap_percentile + cluster_biggest_connected_component with every
-// intermediate decision taken on the device (6 radix-select passes, component choice) and one read-back at the end.
 // Pinned, context-owned source images of the small host-to-device copies of the sync-free frame tail.  An asynchronous
 // copy from pageable or stack memory is only safe if the runtime happens to stage it before returning; these copies
-// are enqueued and never waited for, so their sources must outlive the call: [DevState init | limits init | uv samples].
+// are enqueued and never waited for, so their sources must outlive the call:
+// [DevState init | parameters of a stage-by-stage call | limits init | uv samples].
+constexpr size_t STAGE_PARAM_OFF = 2048;
 constexpr size_t STAGE_UV_OFF = 4096 + NSLOT * 6 * 8;
 constexpr int RANSAC_MAX_ROUNDS = 1800;                       // PLANE_RANSAC_ROUNDS: k_ransac_score keeps 36 bytes of LDS per round (64 KB)
+static_assert((size_t)RANSAC_MAX_ROUNDS * (32 + 4) <= 64 * 1024, "k_ransac_score: a plane and a counter per round in LDS");
 constexpr size_t STAGE_UV_BYTES = (size_t)RANSAC_MAX_ROUNDS * 24;
 constexpr size_t STAGE_BYTES = STAGE_UV_OFF + 2 * STAGE_UV_BYTES;   // two areas, alternated: the host never waits for the previous frame's copy
 static int host_stage(wass_ctx* c, unsigned char** out)
 {
-    static_assert(sizeof(DevState) <= 4096, "DevState init image");
+    static_assert(sizeof(DevState) <= STAGE_PARAM_OFF, "DevState init image");
     if (!c->h_stage) {
         if (hipHostMalloc((void**)&c->h_stage, STAGE_BYTES, hipHostMallocDefault) != hipSuccess)
             return set_err(c, WASS_ERR_NO_MEMORY, "hipHostMalloc failed");
@@ -1672,15 +1547,41 @@ static int host_stage(wass_ctx* c, unsigned char** out)
     return WASS_OK;
 }
 
-static int enqueue_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile, DevState** dsp)
+// Before anything overwrites the current record: the download that read THIS record (two frames ago in a sequence; the
+// frame still in flight when a stage-by-stage call comes in between) must have finished.
+static int record_wait(wass_ctx* c)
 {
-    DevState* ds = nullptr;
-    int rc = dstate(c, &ds);
-    if (rc) return rc;
+    WASS_HIP(c, hipStreamWaitEvent(c->ts(), c->fslot[c->ds_slot & 1].ev_copy, 0));
+    return WASS_OK;
+}
+// the record as the stages enqueued so far leave it, on the host; returns when they have run
+static int record_read(wass_ctx* c, const DevState* ds, DevState* h)
+{
+    WASS_HIP(c, hipGetLastError());
+    WASS_HIP(c, hipMemcpyAsync(h, ds, sizeof *h, hipMemcpyDeviceToHost, c->ts()));
+    WASS_HIP(c, hipStreamSynchronize(c->ts()));
+    return WASS_OK;
+}
+// What a stage-by-stage call is given on the host and the chain's kernels read from the record (a plane, a switch word) goes
+// there through the pinned stage: the caller's memory need not outlive the copy, and the area is free again when the call
+// returns, because every such call ends in a synchronise.
+static int record_put(wass_ctx* c, void* field, const void* src, size_t bytes)
+{
+    unsigned char* stage = nullptr;
+    int rc = host_stage(c, &stage);
+    if (rc || (rc = record_wait(c))) return rc;
+    memcpy(stage + STAGE_PARAM_OFF, src, bytes);
+    WASS_HIP(c, hipMemcpyAsync(field, stage + STAGE_PARAM_OFF, bytes, hipMemcpyHostToDevice, c->ts()));
+    return WASS_OK;
+}
+
+// compute_zgap_percentile: the record reset to its initial image, then the radix select; leaves zgap, sel_total and sel_fail in it
+static int enqueue_percentile(wass_ctx* c, wass_mesh* m, double percentile, DevState* ds)
+{
     unsigned int* hist = (unsigned int*)((char*)ds + DSTATE_HIST_OFF);      // 256-byte aligned: one fill kernel, not three
     unsigned char* stage = nullptr;
-    if ((rc = host_stage(c, &stage))) return rc;
-    WASS_HIP(c, hipStreamWaitEvent(c->ts(), c->fslot[c->ds_slot & 1].ev_copy, 0));   // the download that read THIS record: two frames ago
+    int rc = host_stage(c, &stage);
+    if (rc || (rc = record_wait(c))) return rc;
     WASS_HIP(c, hipMemcpyAsync(ds, stage, sizeof(DevState), hipMemcpyHostToDevice, c->ts()));
     WASS_HIP(c, hipMemsetAsync(hist, 0, (size_t)GAP_HIST_COPIES * GAP_BINS * 4, c->ts()));
     for (int pass = 0; pass < GAP_PASSES; ++pass) {
@@ -1690,6 +1591,28 @@ static int enqueue_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile,
                            (const DevState*)ds, hist);
         hipLaunchKernelGGL(k_radix_pick, dim3(1), dim3(256), 0, c->ts(), hist, pass, shift, nbits, percentile, ds);
     }
+    return WASS_OK;
+}
+
+int wass_mesh_zgap_percentile(wass_ctx* c, wass_mesh* m, double percentile, double* out, uint64_t* n_gaps)
+{
+    if (!c || !m || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    WASS_HIP(c, hipSetDevice(c->device));
+    DevState* ds = nullptr;
+    DevState h;
+    int rc = dstate(c, &ds);
+    if (rc || (rc = enqueue_percentile(c, m, percentile, ds)) || (rc = record_read(c, ds, &h))) return rc;
+    if (h.sel_fail == 2) return set_err(c, WASS_ERR_DEVICE, "radix select lost its rank (internal error)");
+    *out = h.zgap;                                     // no gaps: k_radix_pick's quiet NaN, with 0 gaps
+    if (n_gaps) *n_gaps = h.sel_total;
+    return WASS_OK;
+}
+
+static int enqueue_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile, DevState** dsp)
+{
+    DevState* ds = nullptr;
+    int rc = dstate(c, &ds);
+    if (rc || (rc = enqueue_percentile(c, m, percentile, ds))) return rc;
     if (c->ev_tail[2]) (void)hipEventRecord(c->ev_tail[2], c->ts());
     if ((rc = enqueue_ccl(c, m, ds))) return rc;
     if (c->ev_tail[3]) (void)hipEventRecord(c->ev_tail[3], c->ts());
@@ -1697,16 +1620,16 @@ static int enqueue_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile,
     return WASS_OK;
 }
 
+// wass_stereo.cpp:2046-2050 as one call: compute_zgap_percentile + cluster_biggest_connected_component with every
+// intermediate decision taken on the device (6 radix-select passes, component choice) and one read-back at the end.
 int wass_mesh_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile, double* zgap_out, uint64_t* n_gaps, uint64_t* size_out)
 {
     if (!c || !m) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
     DevState* ds = nullptr;
-    int rc = enqueue_remove_outliers(c, m, percentile, &ds);
-    if (rc) return rc;
     DevState h;
-    WASS_HIP(c, hipMemcpyAsync(&h, ds, sizeof h, hipMemcpyDeviceToHost, c->ts()));
-    WASS_HIP(c, hipStreamSynchronize(c->ts()));
+    int rc = enqueue_remove_outliers(c, m, percentile, &ds);
+    if (rc || (rc = record_read(c, ds, &h))) return rc;
     if (h.sel_fail == 2) return set_err(c, WASS_ERR_DEVICE, "radix select lost its rank (internal error)");
     if (zgap_out) *zgap_out = h.zgap;
     if (n_gaps) *n_gaps = h.sel_total;
@@ -1794,42 +1717,100 @@ int wass_ransac_sample_seeded(uint32_t seed, int width, int height, int rounds, 
     return ransac_sample_with(g, width, height, rounds, uv);
 }
 
+// ---- the plane stages.  Each is enqueued by ONE helper, which the stage-by-stage entry points call with parameters they have
+// written into the record themselves and the chain (enqueue_fit_plane) calls with what the stage before left there.
+
+// [candidates | inlier counts | samples] [per-block partial sums of the refinement] in the scratch buffer
+constexpr int REFINE_BLOCKS = 1024;
+static int plane_scratch(wass_ctx* c, int rounds, PlaneCand** cand, double** part)
+{
+    const size_t cand_bytes = (((size_t)rounds * (24 + sizeof(PlaneCand) + 8) + 256) + 255) & ~(size_t)255;
+    int rc = ensure(c, c->scratch, cand_bytes + (size_t)REFINE_BLOCKS * 6 * 8);
+    if (rc) return rc;
+    *cand = (PlaneCand*)c->scratch.p;
+    *part = (double*)((char*)c->scratch.p + cand_bytes);
+    return WASS_OK;
+}
+
+// what ransac_find_plane accepts; checked before anything is enqueued
+static int check_ransac_args(wass_ctx* c, const wass_mesh* m, const int32_t* uv, int rounds)
+{
+    for (int r = 0; r < rounds * 3; ++r)
+        if (uv[2 * r] < 0 || uv[2 * r] >= m->w || uv[2 * r + 1] < 0 || uv[2 * r + 1] >= m->h)
+            return set_err(c, WASS_ERR_INVALID_ARG, "sample %d outside the mesh grid", r / 3);
+    // (the limit the message states, not the 1820 rounds that would still fit into LDS: the pinned sample stage holds 1800)
+    if (rounds > RANSAC_MAX_ROUNDS) return set_err(c, WASS_ERR_UNSUPPORTED, "PLANE_RANSAC_ROUNDS %d too large (max 1800)", rounds);
+    return WASS_OK;
+}
+
+// ransac_find_plane: a candidate per sample triple, every candidate scored in one pass over the points, the choice ->
+// ds->ransac_plane, ransac_best, ransac_found.  k_ransac_planes also clears the nzero counters at `zero`.
+static int enqueue_ransac(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds, double thr, PlaneCand* cand,
+                          unsigned long long* zero, int nzero, DevState* ds)
+{
+    unsigned long long* counts = (unsigned long long*)(cand + rounds);
+    int32_t* duv = (int32_t*)(counts + rounds);
+    hipStream_t s = c->ts();
+    // the caller's sample array may be pageable and short-lived: go through the pinned stage (the previous frame's
+    // copy out of it was enqueued a whole frame ago; wait for it before overwriting)
+    unsigned char* stage = nullptr;
+    int rc = host_stage(c, &stage);
+    if (rc) return rc;
+    // (two areas, alternated with the frame slot: the copy out of THIS one was enqueued two frames ago)
+    const int ua = c->ds_slot & 1;
+    hipEvent_t evs = ua ? c->ev_stage2 : c->ev_stage;
+    unsigned char* area = stage + STAGE_UV_OFF + (size_t)ua * STAGE_UV_BYTES;
+    if (c->stage_uv_busy) WASS_HIP(c, hipEventSynchronize(evs));
+    memcpy(area, uv, (size_t)rounds * 24);
+    WASS_HIP(c, hipMemcpyAsync(duv, area, (size_t)rounds * 24, hipMemcpyHostToDevice, s));
+    WASS_HIP(c, hipEventRecord(evs, s));
+    c->stage_uv_busy = true;
+    constexpr int PTS = 8;
+    hipLaunchKernelGGL(k_ransac_planes, dim3((rounds + 63) / 64), dim3(64), 0, s, m->valid, m->x, m->y, m->z, m->w, (const int32_t*)duv,
+                       rounds, cand, counts, zero, nzero);
+    hipLaunchKernelGGL(k_ransac_score<PTS>, dim3((m->w + 255) / 256, (m->h + PTS - 1) / PTS), dim3(256), (size_t)rounds * (32 + 4), s,
+                       m->valid, m->x, m->y, m->z, m->w, m->h, (const PlaneCand*)cand, rounds, thr, counts);
+    hipLaunchKernelGGL(k_ransac_pick, dim3(1), dim3(64), 0, s, (const PlaneCand*)cand, (const unsigned long long*)counts, rounds, m->n(), ds);
+    return WASS_OK;
+}
+
+// crop_plane by *plane where *on; the survivors are counted into kept[NSLOT]
+static void enqueue_crop(wass_ctx* c, wass_mesh* m, const double* plane, const int* on, double thr, unsigned long long* kept)
+{
+    hipLaunchKernelGGL(k_crop_plane_dev, dim3(2048), dim3(256), 0, c->ts(), m->valid, m->x, m->y, m->z, m->n(), plane, on, thr, kept);
+}
+
+// crop_plane by *crop_plane where *crop_on, then refine_plane on what is left where *refine_on: centroid, scatter matrix and
+// its eigenvector on the device -> ds->ninl, refine_ok, plane
+static void enqueue_refine(wass_ctx* c, wass_mesh* m, const RefineDev& rd, const double* crop_plane, const int* crop_on, double crop_thr,
+                           unsigned long long* kept, const int* refine_on, double* part, DevState* ds)
+{
+    const int NB = REFINE_BLOCKS;
+    const size_t n = m->n();
+    hipStream_t s = c->ts();
+    hipLaunchKernelGGL(k_crop_moments_dev, dim3(NB), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, crop_plane, crop_on, crop_thr, kept, rd, part);
+    hipLaunchKernelGGL(k_refine_centroid, dim3(1), dim3(64), 0, s, (const double*)part, NB, refine_on, ds);
+    hipLaunchKernelGGL(k_refine_cov_dev, dim3(NB), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, rd, (const DevState*)ds, part);
+    hipLaunchKernelGGL(k_refine_finish, dim3(1), dim3(64), 0, s, (const double*)part, NB, ds);
+}
+
 int wass_mesh_ransac_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds, double thr, double plane_out[4],
                            uint64_t* best_inliers, int* found)
 {
     if (!c || !m || !uv || !plane_out || rounds <= 0) return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
-    for (int r = 0; r < rounds * 3; ++r)
-        if (uv[2 * r] < 0 || uv[2 * r] >= m->w || uv[2 * r + 1] < 0 || uv[2 * r + 1] >= m->h)
-            return set_err(c, WASS_ERR_INVALID_ARG, "sample %d outside the mesh grid", r / 3);
-    WASS_HIP(c, hipSetDevice(c->device));
-    const size_t n = m->n();
-    const size_t bytes = (size_t)rounds * (24 + sizeof(PlaneCand) + 8) + 256;
-    int rc = ensure(c, c->scratch, bytes);
+    int rc = check_ransac_args(c, m, uv, rounds);
     if (rc) return rc;
-    PlaneCand* cand = (PlaneCand*)c->scratch.p;
-    unsigned long long* counts = (unsigned long long*)(cand + rounds);
-    int32_t* duv = (int32_t*)(counts + rounds);
-    WASS_HIP(c, hipMemcpyAsync(duv, uv, (size_t)rounds * 24, hipMemcpyHostToDevice, c->ts()));
-    hipLaunchKernelGGL(k_ransac_planes, dim3((rounds + 63) / 64), dim3(64), 0, c->ts(), m->valid, m->x, m->y, m->z, m->w,
-                       (const int32_t*)duv, rounds, cand, counts, (unsigned long long*)nullptr, 0);
-    constexpr int PTS = 8;
-    const size_t lds = (size_t)rounds * (32 + 4);
-    // (the limit the message states, not the 1820 rounds that would still fit into LDS: the pinned sample stage holds 1800)
-    if (rounds > RANSAC_MAX_ROUNDS || lds > 64 * 1024) return set_err(c, WASS_ERR_UNSUPPORTED, "PLANE_RANSAC_ROUNDS %d too large (max 1800)", rounds);
-    hipLaunchKernelGGL(k_ransac_score<PTS>, dim3((m->w + 255) / 256, (m->h + PTS - 1) / PTS), dim3(256), lds, c->ts(),
-                       m->valid, m->x, m->y, m->z, m->w, m->h, (const PlaneCand*)cand, rounds, thr, counts);
-    std::vector<PlaneCand> hc(rounds);
-    std::vector<unsigned long long> hn(rounds);
-    WASS_HIP(c, hipMemcpyAsync(hc.data(), cand, (size_t)rounds * sizeof(PlaneCand), hipMemcpyDeviceToHost, c->ts()));
-    WASS_HIP(c, hipMemcpyAsync(hn.data(), counts, (size_t)rounds * 8, hipMemcpyDeviceToHost, c->ts()));
-    WASS_HIP(c, hipStreamSynchronize(c->ts()));
-    unsigned long long best = 0;
-    double bn[3] = { 0, 0, 0 }, bd = 0;
-    for (int r = 0; r < rounds; ++r)          // first strictly better candidate wins (:750-755)
-        if (hc[r].ok && hn[r] > best) { best = hn[r]; bn[0] = hc[r].n[0]; bn[1] = hc[r].n[1]; bn[2] = hc[r].n[2]; bd = hc[r].d; }
-    plane_out[0] = bn[0]; plane_out[1] = bn[1]; plane_out[2] = bn[2]; plane_out[3] = bd;
-    if (best_inliers) *best_inliers = best;
-    if (found) *found = best < n / 10 ? 0 : 1;  // :773
+    WASS_HIP(c, hipSetDevice(c->device));
+    DevState* ds = nullptr;
+    DevState h;
+    PlaneCand* cand = nullptr;
+    double* part = nullptr;
+    if ((rc = dstate(c, &ds)) || (rc = plane_scratch(c, rounds, &cand, &part)) || (rc = record_wait(c)) ||
+        (rc = enqueue_ransac(c, m, uv, rounds, thr, cand, nullptr, 0, ds)) || (rc = record_read(c, ds, &h)))
+        return rc;
+    for (int k = 0; k < 4; ++k) plane_out[k] = h.ransac_plane[k];
+    if (best_inliers) *best_inliers = h.ransac_best;
+    if (found) *found = h.ransac_found;
     return WASS_OK;
 }
 
@@ -1837,11 +1818,14 @@ int wass_mesh_crop_plane(wass_ctx* c, wass_mesh* m, const double plane[4], doubl
 {
     if (!c || !m || !plane) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
+    DevState* ds = nullptr;
     unsigned long long* cnt = nullptr;
-    int rc = counters_reset(c, &cnt);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_crop_plane, dim3(2048), dim3(256), 0, c->ts(), m->valid, m->x, m->y, m->z, m->n(), plane[0],
-                       plane[1], plane[2], plane[3], thr, cnt);
+    int rc = dstate(c, &ds);
+    // the plane and the switch behind it, on: what the chain's final crop finds in the record
+    const struct { double plane[4]; int on, pad; } given = { { plane[0], plane[1], plane[2], plane[3] }, 1, 0 };
+    static_assert(offsetof(DevState, refine_ok) == offsetof(DevState, plane) + 32 && offsetof(DevState, pad1) == offsetof(DevState, plane) + 36, "one copy");
+    if (rc || (rc = counters_reset(c, &cnt)) || (rc = record_put(c, ds->plane, &given, sizeof given))) return rc;
+    enqueue_crop(c, m, ds->plane, &ds->refine_ok, thr, cnt);
     unsigned long long hk = 0;
     if ((rc = counters_sum(c, cnt, &hk))) return rc;
     if (kept) *kept = hk;
@@ -1852,40 +1836,22 @@ int wass_mesh_refine_plane(wass_ctx* c, wass_mesh* m, const wass_refine_params* 
 {
     if (!c || !m || !rp || !plane_out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
-    RefineDev rd;
-    rd.xmin = rp->xmin; rd.xmax = rp->xmax; rd.ymin = rp->ymin; rd.ymax = rp->ymax; rd.maxd = rp->max_distance;
-    rd.weighted = rp->weight_by_distance;
-    rd.umin = rp->central_third_only ? m->w / 4 : 0;            // :585-588
-    rd.umax = rp->central_third_only ? m->w * 3 / 4 : m->w - 1;
-    rd.vmin = rp->central_third_only ? m->h / 4 : 0;
-    rd.vmax = rp->central_third_only ? m->h * 2 / 3 : m->h - 1;
-    const int NB = 1024;
-    int rc = ensure(c, c->scratch, (size_t)NB * 6 * 8);
-    if (rc) return rc;
-    double* part = (double*)c->scratch.p;
-    std::vector<double> hp((size_t)NB * 6);
-    hipLaunchKernelGGL(k_refine_moments, dim3(NB), dim3(256), 0, c->ts(), m->valid, m->x, m->y, m->z, m->w, m->n(), rd, part);
-    WASS_HIP(c, hipMemcpyAsync(hp.data(), part, (size_t)NB * 5 * 8, hipMemcpyDeviceToHost, c->ts()));
-    WASS_HIP(c, hipStreamSynchronize(c->ts()));
-    double mom[5];
-    sum_partials_host<5>(hp.data(), NB, mom);
-    if (n_inliers) *n_inliers = (uint64_t)(mom[0] + 0.5);
-    if (mom[0] < 3 || !(mom[1] > 0)) return set_err(c, WASS_ERR_TOO_FEW_POINTS, "plane refinement has %g inliers", mom[0]);
-    const double cx = mom[2] / mom[1], cy = mom[3] / mom[1], cz = mom[4] / mom[1];
-    hipLaunchKernelGGL(k_refine_cov, dim3(NB), dim3(256), 0, c->ts(), m->valid, m->x, m->y, m->z, m->w, m->n(), rd, cx, cy, cz,
-                       part);
-    WASS_HIP(c, hipMemcpyAsync(hp.data(), part, (size_t)NB * 6 * 8, hipMemcpyDeviceToHost, c->ts()));
-    WASS_HIP(c, hipStreamSynchronize(c->ts()));
-    double s[6];
-    sum_partials_host<6>(hp.data(), NB, s);
-    const double A[9] = { s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5] };
-    double nrm[3];
-    smallest_eigvec3(A, nrm);
-    const double nn = sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
-    nrm[0] /= nn; nrm[1] /= nn; nrm[2] /= nn;
-    if (nrm[2] < 0) { nrm[0] *= -1.0; nrm[1] *= -1.0; nrm[2] *= -1.0; }   // :646-649
-    plane_out[0] = nrm[0]; plane_out[1] = nrm[1]; plane_out[2] = nrm[2];
-    plane_out[3] = -(nrm[0] * cx + nrm[1] * cy + nrm[2] * cz);
+    DevState* ds = nullptr;
+    DevState h;
+    PlaneCand* cand = nullptr;
+    double* part = nullptr;
+    int rc = dstate(c, &ds);
+    // the refinement on, its crop off: both words written here, whatever an earlier fit_plane left in the record
+    const int given[2] = { 1, 0 };
+    static_assert(offsetof(DevState, zero) == offsetof(DevState, ransac_found) + 4, "one copy");
+    if (rc || (rc = plane_scratch(c, 0, &cand, &part)) || (rc = ensure(c, c->counters, (size_t)NSLOT * 6 * 8)) ||
+        (rc = record_put(c, &ds->ransac_found, given, sizeof given)))
+        return rc;
+    enqueue_refine(c, m, refine_dev(rp, m), ds->ransac_plane, &ds->zero, 0.0, (unsigned long long*)c->counters.p, &ds->ransac_found, part, ds);
+    if ((rc = record_read(c, ds, &h))) return rc;
+    if (n_inliers) *n_inliers = (uint64_t)(h.ninl + 0.5);
+    if (!h.refine_ok) return set_err(c, WASS_ERR_TOO_FEW_POINTS, "plane refinement has %g inliers", h.ninl);
+    for (int k = 0; k < 4; ++k) plane_out[k] = h.plane[k];
     return WASS_OK;
 }
 
@@ -1894,13 +1860,7 @@ int wass_mesh_refinement_inliers(wass_ctx* c, wass_mesh* m, const wass_refine_pa
     if (!c || !m || !rp || !xyz_out || !n_out || every <= 0) return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
     WASS_HIP(c, hipSetDevice(c->device));
     *xyz_out = nullptr; *n_out = 0;
-    RefineDev rd;
-    rd.xmin = rp->xmin; rd.xmax = rp->xmax; rd.ymin = rp->ymin; rd.ymax = rp->ymax; rd.maxd = rp->max_distance;
-    rd.weighted = rp->weight_by_distance;
-    rd.umin = rp->central_third_only ? m->w / 4 : 0;
-    rd.umax = rp->central_third_only ? m->w * 3 / 4 : m->w - 1;
-    rd.vmin = rp->central_third_only ? m->h / 4 : 0;
-    rd.vmax = rp->central_third_only ? m->h * 2 / 3 : m->h - 1;
+    const RefineDev rd = refine_dev(rp, m);
     const size_t n = m->n();
     const unsigned nb = nblk(n);
     const size_t cap = (n + (size_t)every - 1) / (size_t)every;                 // at most every point is an inlier
@@ -1935,64 +1895,20 @@ static int enqueue_fit_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int r
                              double max_distance, DevState** dsp, unsigned long long** keptp, bool final_crop = true)
 {
     if (!c || !m || !uv || !rp || rounds <= 0) return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
-    for (int r = 0; r < rounds * 3; ++r)
-        if (uv[2 * r] < 0 || uv[2 * r] >= m->w || uv[2 * r + 1] < 0 || uv[2 * r + 1] >= m->h)
-            return set_err(c, WASS_ERR_INVALID_ARG, "sample %d outside the mesh grid", r / 3);
-    WASS_HIP(c, hipSetDevice(c->device));
-    const size_t n = m->n();
-    DevState* ds = nullptr;
-    int rc = dstate(c, &ds);
+    int rc = check_ransac_args(c, m, uv, rounds);
     if (rc) return rc;
-    const int NB = 1024;
-    const size_t cand_bytes = (((size_t)rounds * (24 + sizeof(PlaneCand) + 8) + 256) + 255) & ~(size_t)255;
-    if ((rc = ensure(c, c->scratch, cand_bytes + (size_t)NB * 6 * 8))) return rc;
-    if ((rc = ensure(c, c->counters, (size_t)NSLOT * 6 * 8))) return rc;
-    PlaneCand* cand = (PlaneCand*)c->scratch.p;
-    unsigned long long* counts = (unsigned long long*)(cand + rounds);
-    int32_t* duv = (int32_t*)(counts + rounds);
-    double* part = (double*)((char*)c->scratch.p + cand_bytes);
+    WASS_HIP(c, hipSetDevice(c->device));
+    DevState* ds = nullptr;
+    PlaneCand* cand = nullptr;
+    double* part = nullptr;
+    if ((rc = dstate(c, &ds)) || (rc = plane_scratch(c, rounds, &cand, &part)) || (rc = ensure(c, c->counters, (size_t)NSLOT * 6 * 8))) return rc;
     unsigned long long* kept1 = (unsigned long long*)c->counters.p;            // [NSLOT]
     unsigned long long* kept2 = kept1 + NSLOT;
-    constexpr int PTS = 8;
-    const size_t lds = (size_t)rounds * (32 + 4);
-    // (the limit the message states, not the 1820 rounds that would still fit into LDS: the pinned sample stage holds 1800)
-    if (rounds > RANSAC_MAX_ROUNDS || lds > 64 * 1024) return set_err(c, WASS_ERR_UNSUPPORTED, "PLANE_RANSAC_ROUNDS %d too large (max 1800)", rounds);
-    hipStream_t s = c->ts();
-    {   // the caller's sample array may be pageable and short-lived: go through the pinned stage (the previous frame's
-        // copy out of it was enqueued a whole frame ago; wait for it before overwriting)
-        unsigned char* stage = nullptr;
-        if ((rc = host_stage(c, &stage))) return rc;
-        // (two areas, alternated with the frame slot: the copy out of THIS one was enqueued two frames ago)
-        const int ua = c->ds_slot & 1;
-        hipEvent_t evs = ua ? c->ev_stage2 : c->ev_stage;
-        unsigned char* area = stage + STAGE_UV_OFF + (size_t)ua * STAGE_UV_BYTES;
-        if (c->stage_uv_busy) WASS_HIP(c, hipEventSynchronize(evs));
-        memcpy(area, uv, (size_t)rounds * 24);
-        WASS_HIP(c, hipMemcpyAsync(duv, area, (size_t)rounds * 24, hipMemcpyHostToDevice, s));
-        WASS_HIP(c, hipEventRecord(evs, s));
-        c->stage_uv_busy = true;
-    }
-    hipLaunchKernelGGL(k_ransac_planes, dim3((rounds + 63) / 64), dim3(64), 0, s, m->valid, m->x, m->y, m->z, m->w, (const int32_t*)duv,
-                       rounds, cand, counts, kept1, 2 * NSLOT);
-    hipLaunchKernelGGL(k_ransac_score<PTS>, dim3((m->w + 255) / 256, (m->h + PTS - 1) / PTS), dim3(256), lds, s, m->valid, m->x,
-                       m->y, m->z, m->w, m->h, (const PlaneCand*)cand, rounds, ransac_thr, counts);
-    hipLaunchKernelGGL(k_ransac_pick, dim3(1), dim3(64), 0, s, (const PlaneCand*)cand, (const unsigned long long*)counts, rounds, n, ds);
-    if (c->ev_tail[4]) (void)hipEventRecord(c->ev_tail[4], s);
-    RefineDev rd;
-    rd.xmin = rp->xmin; rd.xmax = rp->xmax; rd.ymin = rp->ymin; rd.ymax = rp->ymax; rd.maxd = rp->max_distance;
-    rd.weighted = rp->weight_by_distance;
-    rd.umin = rp->central_third_only ? m->w / 4 : 0;
-    rd.umax = rp->central_third_only ? m->w * 3 / 4 : m->w - 1;
-    rd.vmin = rp->central_third_only ? m->h / 4 : 0;
-    rd.vmax = rp->central_third_only ? m->h * 2 / 3 : m->h - 1;
-    hipLaunchKernelGGL(k_crop_moments_dev, dim3(NB), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, (const double*)ds->ransac_plane,
-                       (const int*)&ds->ransac_found, ransac_thr, kept1, rd, part);
-    hipLaunchKernelGGL(k_refine_centroid, dim3(1), dim3(64), 0, s, (const double*)part, NB, (const int*)&ds->ransac_found, ds);
-    hipLaunchKernelGGL(k_refine_cov_dev, dim3(NB), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, rd, (const DevState*)ds, part);
-    hipLaunchKernelGGL(k_refine_finish, dim3(1), dim3(64), 0, s, (const double*)part, NB, ds);
+    if ((rc = enqueue_ransac(c, m, uv, rounds, ransac_thr, cand, kept1, 2 * NSLOT, ds))) return rc;
+    if (c->ev_tail[4]) (void)hipEventRecord(c->ev_tail[4], c->ts());
+    enqueue_refine(c, m, refine_dev(rp, m), ds->ransac_plane, &ds->ransac_found, ransac_thr, kept1, &ds->ransac_found, part, ds);
     if (final_crop)                                              // the frame tail folds this pass into its limits / counts pass
-        hipLaunchKernelGGL(k_crop_plane_dev, dim3(2048), dim3(256), 0, s, m->valid, m->x, m->y, m->z, n, (const double*)ds->plane,
-                           (const int*)&ds->refine_ok, max_distance, kept2);
+        enqueue_crop(c, m, ds->plane, &ds->refine_ok, max_distance, kept2);
     WASS_HIP(c, hipGetLastError());
     *dsp = ds;
     *keptp = kept1;
@@ -2088,13 +2004,7 @@ int wass_mesh_finish_frame_async_ex2(wass_ctx* c, wass_mesh* m, double percentil
     const unsigned int* text_totals = nullptr;             // [0] bytes of text, [1] numbers not formatted: written on the copy stream
     unsigned int* inl_total = nullptr;
     if (inliers_dst || inliers_text_dst) {
-        RefineDev rd;
-        rd.xmin = rp->xmin; rd.xmax = rp->xmax; rd.ymin = rp->ymin; rd.ymax = rp->ymax; rd.maxd = rp->max_distance;
-        rd.weighted = rp->weight_by_distance;
-        rd.umin = rp->central_third_only ? m->w / 4 : 0;
-        rd.umax = rp->central_third_only ? m->w * 3 / 4 : m->w - 1;
-        rd.vmin = rp->central_third_only ? m->h / 4 : 0;
-        rd.vmax = rp->central_third_only ? m->h * 2 / 3 : m->h - 1;
+        const RefineDev rd = refine_dev(rp, m);
         const size_t cap = (n + (size_t)inliers_every - 1) / (size_t)inliers_every;
         if (inliers_dst && inliers_capacity < cap) return set_err(c, WASS_ERR_INVALID_ARG, "inliers_dst must hold %zu points", cap);
         const unsigned nb2 = nblk(cap);
