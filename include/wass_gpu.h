@@ -1117,6 +1117,68 @@ int wass_warp_perspective(wass_ctx* ctx, const uint8_t* src, int sw, int sh, siz
 int wass_warp_perspective_dev(wass_ctx* ctx, const uint8_t* d_src, int sw, int sh, size_t src_stride,
                               const double H[9], int dw, int dh, const int roi[4], uint8_t* d_dst);
 
+/* ---- KAZE feature detector (kaze.hip; wass_amd/features.py chains the stages) --------------------------------------------------
+ * What FeatureSet::detect asks of cv::KAZE::create(false, false, threshold, n_octaves, n_sublevels): soffset 1.6, sderivatives 1,
+ * PM-G2 diffusivity, M-SURF 64 descriptor.  Restated from the published algorithm, not pinned against OpenCV.
+ * All planes are h x w float32, contiguous; a stack of levels is `plane_stride` floats apart.  Everything is float32 in the
+ * order written here, without contraction, division and square root correctly rounded; every call returns after a
+ * synchronisation.  3 <= h, w <= 32768.
+ *
+ * convert:  dst = (float)src * scale.
+ * gauss:    separable, rows then columns, border replicated, acc = acc + tap[j] * v from the first tap to the last (taps: host
+ *           pointer, an odd number <= 15).  d_tmp holds the row pass.
+ * scharr:   reach s = sigma_size, reflect-101 (s < h, w), norm and wnorm = w * norm given by the caller:
+ *             Lx = (norm * d(y-s) + wnorm * d(y)) + norm * d(y+s),  d(r) = src[r][x+s] - src[r][x-s]
+ *             Ly = m(y+s) - m(y-s),  m(r) = (norm * src[r][x-s] + wnorm * src[r][x]) + norm * src[r][x+s]
+ * hessian:  from the UNSCALED Lx, Ly of scharr: Lxx = scharr_x(Lx) * s^2, Lxy = scharr_y(Lx) * s^2, Lyy = scharr_y(Ly) * s^2,
+ *           Ldet = Lxx * Lyy - Lxy * Lxy; then Lx and Ly are multiplied by s in place.  d_lxx, d_lxy, d_lyy may be null.
+ * contrast: over the interior pixels m = sqrt(Lx * Lx + Ly * Ly); hmax = the largest; npoints = the moduli that are not 0; hist[300]:
+ *           bin floor(300 * (m / hmax)) clamped to 299, of the non-zero ones.  Integer atomics: the same in any launch order.
+ *           d_rec: 302 uint32 of device scratch.
+ * flow:     1 / (1 + (Lx * Lx + Ly * Ly) / (k * k)).
+ * diffuse:  for every tau (host pointer) L <- L + (0.5 * tau) * (((xpos - xneg) + ypos) - yneg) with xpos = (c[E] + c) * (L[E] - L),
+ *           xneg = (c + c[W]) * (L - L[W]), ypos = (c[S] + c) * (L[S] - L), yneg = (c + c[N]) * (L - L[N]), a term being 0 where its
+ *           neighbour is outside; d_tmp is the other side of the ping-pong, the result ends in d_lt.
+ * extrema:  levels 1 .. n_levels-2, interior pixels, v = Ldet > threshold and >= 1e-5, strictly above its 26 neighbours, and
+ *           rint(x -+ 3 * esigma[level]) in [0, w), the same for y.  Appends the key (level * h + y) * w + x in any order; *count is
+ *           the number found.  More than `cap` returns WASS_KAZE_CAP_REACHED with the first `cap` arrivals in d_keys, valid but
+ *           not a defined subset.  d_count: one uint32 of device scratch.
+ * refine:   per key Dx = 0.5 (C[x+1] - C[x-1]), Dy, Ds alike (Ds = 0.5 (up - down)); Dxx = (C[x+1] + C[x-1]) - 2 C, Dyy, Dss alike;
+ *           Dxy = 0.25 ((C[y+1][x+1] + C[y-1][x-1]) - (C[y-1][x+1] + C[y+1][x-1])), Dxs = 0.25 ((U[x+1] + D[x-1]) - (U[x-1] + D[x+1])),
+ *           Dys alike.  [Dxx Dxy Dxs; Dxy Dyy Dys; Dxs Dys Dss] d = -[Dx Dy Ds] by elimination on the 3 x 4 tableau: per column k the
+ *           row >= k with the largest |a[r][k]| (the first of equals) is swapped in, f = a[r][k] / a[k][k], a[r][c] = a[r][c] - f * a[k][c]
+ *           for c = k+1 .. 3; then d2 = a23 / a22, d1 = (a13 - a12 d2) / a11, d0 = ((a03 - a01 d1) - a02 d2) / a00.
+ *           out: n x 5 float32 = x + d0, y + d1, d2, |v|, kept; kept = 0 (x, y unrefined) where a pivot is 0 or some |d| > 1.
+ * orientation, descriptors: kp is n x 5 float32 (x, y, size, level, angle), Lx / Ly the scaled stacks.  s = (int)(size / 2 + 0.5).
+ *           Orientation: the 109 lattice samples (i outer, j inner, i^2 + j^2 < 36) at ((int)(x + i s + 0.5), (int)(y + j s + 0.5)) inside
+ *           the picture, weighted by SURF's gauss25[|i|][|j|]; 42 windows of pi / 3 starting at 0, 0.15, ... (accumulated in float32),
+ *           each summed in sample order; the first window with the largest sumX^2 + sumY^2 gives atan2f(sumY, sumX) in [0, 2 pi).
+ *           Descriptor: 4 x 4 subregions of 9 x 9 samples, step s, rotated by the angle, bilinear samples (pixels floor and floor + 1, the fraction taken
+ *           first, then the indices clamped into the picture),
+ *           Gaussian 2.5 s about the subregion, 1.5 about the grid; (sum dx, sum dy, sum |dx|, sum |dy|) per subregion, each summed
+ *           in sample order, the 64 values divided by their length.  atan2f, sinf, cosf, expf: bounded, not exact. */
+#define WASS_KAZE_MAX_LEVELS 32
+#define WASS_KAZE_MAX_CANDIDATES (1 << 20)
+#define WASS_KAZE_CAP_REACHED 1
+int wass_kaze_scratch_bytes(int h, int w, int n_levels, size_t* bytes);
+int wass_kaze_convert_dev(wass_ctx* ctx, const uint8_t* d_src, size_t pitch, int h, int w, float scale, float* d_dst);
+int wass_kaze_gauss_dev(wass_ctx* ctx, const float* d_src, int h, int w, const float* taps, int ntaps, float* d_tmp, float* d_dst);
+int wass_kaze_scharr_dev(wass_ctx* ctx, const float* d_src, int h, int w, int sigma_size, float norm, float wnorm, float* d_lx, float* d_ly);
+int wass_kaze_hessian_dev(wass_ctx* ctx, float* d_lx, float* d_ly, int h, int w, int sigma_size, float norm, float wnorm, float* d_ldet,
+                          float* d_lxx, float* d_lxy, float* d_lyy);
+int wass_kaze_contrast_dev(wass_ctx* ctx, const float* d_lx, const float* d_ly, int h, int w, uint32_t* d_rec, float* hmax, uint32_t* npoints,
+                           uint32_t* hist);
+int wass_kaze_flow_dev(wass_ctx* ctx, const float* d_lx, const float* d_ly, int h, int w, float k, float* d_flow);
+int wass_kaze_diffuse_dev(wass_ctx* ctx, float* d_lt, float* d_tmp, const float* d_flow, int h, int w, const float* taus, int ntaus);
+int wass_kaze_extrema_dev(wass_ctx* ctx, const float* d_ldet, size_t plane_stride, int n_levels, int h, int w, float threshold,
+                          const float* esigma, int64_t* d_keys, int cap, uint32_t* d_count, uint32_t* count);
+int wass_kaze_refine_dev(wass_ctx* ctx, const float* d_ldet, size_t plane_stride, int n_levels, int h, int w, const int64_t* d_keys, int n,
+                         float* d_out);
+int wass_kaze_orientation_dev(wass_ctx* ctx, const float* d_kp, int n, const float* d_lx, const float* d_ly, size_t plane_stride, int n_levels,
+                              int h, int w, float* d_angle);
+int wass_kaze_descriptors_dev(wass_ctx* ctx, const float* d_kp, int n, const float* d_lx, const float* d_ly, size_t plane_stride, int n_levels,
+                              int h, int w, float* d_desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Pin the oracle to the real OpenCV -- for a machine that HAS OpenCV (the build image does not).
 
-    python scripts/pin_with_opencv.py            # writes tests/golden/sgbm_opencv.npz, opencv_other.npz and pyrup_pin.npz
+    python scripts/pin_with_opencv.py            # writes tests/golden/sgbm_opencv.npz, opencv_other.npz, pyrup_pin.npz and kaze_pin.npz
     python -m pytest tests/test_oracle_pin.py    # compares oracle/*.c with them (skipped while the files are absent)
     python -m pytest tests/test_pyramid.py       # test_opencv_pin compares tests/pyramid_oracle.py with pyrup_pin.npz
+    python -m pytest tests/test_kaze.py          # test_oracle_against_opencv_pin compares tests/kaze_oracle.py with kaze_pin.npz
 
 One run pins every restatement of an OpenCV routine the hot path and its neighbours rest on: cv::StereoSGBM (rows a2-a6,
 below), and -- other_cases() / run_other() -- stereoRectify + initUndistortRectifyMap + remap, warpPerspective (f1),
@@ -189,12 +190,24 @@ def run_pyrup(cv2):
     return store
 
 
+def run_kaze(cv2):
+    """cv2.KAZE on the picture tests/test_kaze.py compares the numpy oracle with (kaze_pictures 'interior'): image, keypoints
+    (x, y, size, angle in degrees, response, octave, class_id) and descriptors"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import kaze_pictures
+    img = kaze_pictures.picture("interior")
+    kps, desc = cv2.KAZE_create(False, False, 1e-4, 4, 4).detectAndCompute(img, None)       # FeatureSet.cpp:199
+    table = np.array([[k.pt[0], k.pt[1], k.size, k.angle, k.response, k.octave, k.class_id] for k in kps], np.float64).reshape(-1, 7)
+    return {"image": img, "keypoints": table, "descriptors": np.asarray(desc, np.float32).reshape(len(kps), -1)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "sgbm_opencv.npz"))
     ap.add_argument("--out-other", default=os.path.join(ROOT, "tests", "golden", "opencv_other.npz"),
                     help="rectification / undistort / CLAHE / resize / filterSpeckles / component vectors")
     ap.add_argument("--out-pyrup", default=os.path.join(ROOT, "tests", "golden", "pyrup_pin.npz"), help="cv.pyrUp vectors")
+    ap.add_argument("--out-kaze", default=os.path.join(ROOT, "tests", "golden", "kaze_pin.npz"), help="cv.KAZE keypoints and descriptors")
     args = ap.parse_args()
     try:
         import cv2
@@ -237,6 +250,10 @@ def main():
     pyr["opencv_version"] = np.array(ver)
     np.savez_compressed(args.out_pyrup, **pyr)
     print(f"wrote {args.out_pyrup}: {len(pyr['names'])} pictures through cv.pyrUp")
+    kz = run_kaze(cv2)
+    kz["opencv_version"] = np.array(ver)
+    np.savez_compressed(args.out_kaze, **kz)
+    print(f"wrote {args.out_kaze}: {len(kz['keypoints'])} KAZE keypoints of the 160 x 128 blob picture")
 
 
 if __name__ == "__main__":

@@ -296,6 +296,18 @@ SYMBOLS = {
     "wass_epi_mask_dev": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _i, _vp, _vp, _sz]),
     "wass_epi_find_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _i, _i, _vp, C.POINTER(_i), C.POINTER(_i),
                                _vp, _vp, _sz]),
+    "wass_kaze_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "wass_kaze_convert_dev": (_i, [_vp, _vp, _sz, _i, _i, C.c_float, _vp]),
+    "wass_kaze_gauss_dev": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "wass_kaze_scharr_dev": (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_float, _vp, _vp]),
+    "wass_kaze_hessian_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "wass_kaze_contrast_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32), _vp]),
+    "wass_kaze_flow_dev": (_i, [_vp, _vp, _vp, _i, _i, C.c_float, _vp]),
+    "wass_kaze_diffuse_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i]),
+    "wass_kaze_extrema_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, C.c_float, _vp, _vp, _i, _vp, C.POINTER(C.c_uint32)]),
+    "wass_kaze_refine_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _i, _vp]),
+    "wass_kaze_orientation_dev": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "wass_kaze_descriptors_dev": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

@@ -3,7 +3,7 @@
 The kernels (csrc/match.hip) find the candidates, fill the payoff matrix, run the infection-immunization dynamics and pick the
 group; the host keeps what the reference does between them: match_group's removal loop and wass_match's round loop, restated
 faithfully, quirks included.  Features come from a file in the layout of FeatureSet::save or from any detector (the reference's is
-OpenCV's KAZE, which is not part of this project); the matches go out in the text format of matches_unfiltered.txt.
+OpenCV's KAZE: wass_amd.features.detect_features is that detector with the reference's subsampling); the matches go out in the text format of matches_unfiltered.txt.
 
 Host arrays are numpy, device arrays torch tensors passed by raw pointer.  There is no CPU path: without the library or a GPU
 every function that computes raises.

@@ -91,6 +91,31 @@ def make_pair(w: int, h: int, num_disp: int, frame_idx: int = 0, noise: bool = T
     return np.ascontiguousarray(right), np.ascontiguousarray(left)
 
 
+def relief_disparity(w: int, h: int) -> np.ndarray:
+    """The disparity of make_relief_pair, float64 (h, w): one swell 0.94 w x 0.75 w long, from 0.019 w to 0.056 w pixels, which
+    stretches the right picture by at most 13 %."""
+    x = np.arange(w, dtype=np.float64)[None, :]
+    y = np.arange(h, dtype=np.float64)[:, None]
+    return 0.0375 * w + 0.01875 * w * np.sin(2 * np.pi * x / (0.9375 * w)) * np.cos(2 * np.pi * y / (0.75 * w))
+
+
+def make_relief_pair(w: int, h: int, frame_idx: int = 0, noise: bool = True):
+    """(left, right) u8 (h, w) of the ideal rig of rig_geometry over a surface with relief (relief_disparity), in make_pair's texture
+    and noise: right(x, y) = left(x - d(x, y), y).  make_pair's own surface is a plane with ripples of 0.4 pixels, and the
+    essential matrix of a plane leaves the translation's direction to the noise: a pair for pose tests needs depth."""
+    params = texture_params(frame_idx)
+    x = np.arange(w, dtype=np.float64)[None, :]
+    y = np.arange(h, dtype=np.float64)[:, None]
+    left = _tex(x, y, params)
+    right = _tex(x - relief_disparity(w, h), y, params)
+    if noise:
+        seed = (SEED_BASE + frame_idx) & _M64
+        left = left + _hash_noise(seed, 0, h, w)
+        right = right + _hash_noise(seed, 1, h, w)
+    u8 = lambda a: np.ascontiguousarray(np.clip(np.rint(a), 1, 254).astype(np.uint8))
+    return u8(left), u8(right)
+
+
 def _i64(c: int) -> int:
     """64-bit constant as the int64 with the same bit pattern."""
     c &= _M64
