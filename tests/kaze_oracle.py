@@ -114,7 +114,12 @@ def scharr_y(src, s, mode="reflect"):
 def contrast(img32, mode="reflect"):
     """(k, hmax, npoints, hist)"""
     g = gauss(img32, gaussian_taps(1.0))
-    lx, ly = scharr_x(g, 1, mode), scharr_y(g, 1, mode)
+    return contrast_of(scharr_x(g, 1, mode), scharr_y(g, 1, mode))
+
+
+def contrast_of(lx, ly):
+    """(k, hmax, npoints, hist) of two planes of first derivatives: what wass_kaze_contrast_dev and the host's scan of the bins give"""
+    lx, ly = np.asarray(lx, F), np.asarray(ly, F)
     m = np.sqrt(lx * lx + ly * ly)[1:-1, 1:-1].ravel()
     hmax = m.max() if m.size else F(0)
     nz = m[m != 0]
@@ -174,8 +179,18 @@ def scale_space(img, n_octaves=4, n_sublevels=4, border="reflect", fed_reorder=T
 
 
 # -------------------------------------------------------------------------------------------------------------------- extrema
-def extrema(ldet, lv, threshold=1e-4, strict=True):
-    """n x 3 (level, y, x) sorted, and the values"""
+def _round(v, rounding):
+    if rounding == "even":
+        return np.rint(v)
+    if rounding == "away":
+        return np.sign(v) * np.floor(np.abs(v) + F(0.5))
+    assert rounding == "trunc"
+    return np.trunc(v)
+
+
+def extrema(ldet, lv, threshold=1e-4, strict=True, loose=None, rounding="even"):
+    """n x 3 (level, y, x) sorted, and the values.  Mistakes: strict=False compares >= everywhere, loose=(dl, dy, dx) at that one
+    neighbour; rounding "away" / "trunc" in the border rule instead of half to even"""
     N, h, w = ldet.shape
     found = []
     for l in range(1, N - 1):
@@ -187,12 +202,13 @@ def extrema(ldet, lv, threshold=1e-4, strict=True):
                     if dl == 0 and dy == 0 and dx == 0:
                         continue
                     nb = ldet[l + dl, 1 + dy:h - 1 + dy, 1 + dx:w - 1 + dx]
-                    ok &= (v > nb) if strict else (v >= nb)
+                    ok &= (v > nb) if strict and loose != (dl, dy, dx) else (v >= nb)
         r = F(3.0) * lv[l]["esigma"]
         ys, xs = np.nonzero(ok)
         ys, xs = ys + 1, xs + 1
         xf, yf = xs.astype(F), ys.astype(F)
-        inside = (np.rint(xf - r) >= 0) & (np.rint(xf + r) < w) & (np.rint(yf - r) >= 0) & (np.rint(yf + r) < h)
+        rnd = lambda t: _round(t, rounding)
+        inside = (rnd(xf - r) >= 0) & (rnd(xf + r) < w) & (rnd(yf - r) >= 0) & (rnd(yf + r) < h)
         found += [(l, int(y), int(x)) for y, x in zip(ys[inside], xs[inside])]
     cand = np.array(sorted(found), np.int64).reshape(-1, 3)
     return cand, ldet[cand[:, 0], cand[:, 1], cand[:, 2]].astype(F)
@@ -216,12 +232,13 @@ def duplicates(cand, values, lv):
     return np.array(acc, np.int64)
 
 
-def solve3(a):
+def solve3(a, pivot="first"):
+    """pivot: "first" of equal pivots (the rule); the mistakes "last" of equal pivots and "none" (no row exchange)"""
     a = [[F(v) for v in row] for row in a]
     for k in range(3):
         p = k
         for r in range(k + 1, 3):
-            if abs(a[r][k]) > abs(a[p][k]):
+            if pivot != "none" and (abs(a[r][k]) > abs(a[p][k]) or (pivot == "last" and abs(a[r][k]) == abs(a[p][k]))):
                 p = r
         a[k], a[p] = a[p], a[k]
         if a[k][k] == 0:
@@ -236,8 +253,8 @@ def solve3(a):
     return d0, d1, d2
 
 
-def refine(ldet, cand):
-    """n x 5 float32: x + dx, y + dy, ds, |v|, kept"""
+def refine(ldet, cand, pivot="first", bound="le"):
+    """n x 5 float32: x + dx, y + dy, ds, |v|, kept.  Mistakes: pivot (solve3), bound="lt" refuses an offset of exactly 1"""
     out = np.zeros((len(cand), 5), F)
     h2, q = F(0.5), F(0.25)
     with np.errstate(all="ignore"):
@@ -252,8 +269,9 @@ def refine(ldet, cand):
             Dxs = q * ((U[y, x + 1] + D[y, x - 1]) - (U[y, x - 1] + D[y, x + 1]))
             Dys = q * ((U[y + 1, x] + D[y - 1, x]) - (U[y - 1, x] + D[y + 1, x]))
             out[i] = (x, y, 0, abs(v), 0)
-            d = solve3([[Dxx, Dxy, Dxs, -Dx], [Dxy, Dyy, Dys, -Dy], [Dxs, Dys, Dss, -Ds]])
-            if d is not None and abs(d[0]) <= 1 and abs(d[1]) <= 1 and abs(d[2]) <= 1:
+            d = solve3([[Dxx, Dxy, Dxs, -Dx], [Dxy, Dyy, Dys, -Dy], [Dxs, Dys, Dss, -Ds]], pivot)
+            inside = (lambda t: abs(t) <= 1) if bound == "le" else (lambda t: abs(t) < 1)
+            if d is not None and inside(d[0]) and inside(d[1]) and inside(d[2]):
                 out[i] = (F(x) + d[0], F(y) + d[1], d[2], abs(v), 1)
     return out
 
@@ -272,9 +290,24 @@ def _fround(v):
     return np.trunc(v + v.dtype.type(0.5)).astype(np.int64)
 
 
-def orientation(kp, Lx, Ly, dtype=np.float32, flags=False):
+def orientation(kp, Lx, Ly, dtype=np.float32, flags=False, admissible=False, **mistakes):
     """angles of a keypoint table (x, y, size, level[, ...]); with flags also the fragile keypoints: a sample's angle within 1e-5 rad
-    of a window edge, or a window of other members whose score is within 1e-6 (relative) of the best"""
+    of a window edge, or a window of other members whose score is within 1e-6 (relative) of the best.  With admissible as well, a
+    third value: per keypoint the angles a correct float32 implementation may give (empty where the keypoint is not fragile).  They
+    are the angles of every window, with its samples within 1e-5 rad of one of its edges as computed, all counted in and all counted
+    out, whose score reaches (within 1e-6) the largest score some window has whichever way its own near samples fall; 0 as well where
+    that is 0.
+
+    Mistakes (keywords, for the probes of tests/kaze_probes.py): transpose (the planes read at [x][y]; swapping i and j alone only
+    reorders the symmetric lattice), floor (floor(v + 0.5) instead of the
+    truncation), clamp (outside samples read the border instead of 0), zero_in (a >= 0 in the wrap-around windows), last_equal (the
+    last of equal windows wins), no_wrap (ang2 = ang1 + pi / 3 always), no_high (a wrap-around window
+    without its part below 2 pi), level0 (every keypoint reads level 0), size_floor
+    ((int)(size / 2)), drop=q (sample q is not read)"""
+    mk = lambda name, default=False: mistakes.pop(name, default)
+    transpose, floor_, clamp, zero_in, last_equal = mk("transpose"), mk("floor"), mk("clamp"), mk("zero_in"), mk("last_equal")
+    no_wrap, level0, size_floor, drop, no_high = mk("no_wrap"), mk("level0"), mk("size_floor"), mk("drop", None), mk("no_high")
+    assert not mistakes, mistakes
     T = dtype
     N, h, w = Lx.shape
     two_pi, pi3, pi53 = T(6.2831853071795864769), T(1.0471975511965976), T(5.2359877559829887)
@@ -288,37 +321,55 @@ def orientation(kp, Lx, Ly, dtype=np.float32, flags=False):
         a = a + np.float32(0.15)
     ang1s = np.array(ang1s, np.float32).astype(T)              # the window starts are float32 sums on the device
     assert len(ang1s) == 42
-    ang2s = np.where(ang1s + pi3 > two_pi, ang1s - pi53, ang1s + pi3).astype(T)
-    out, frag = np.zeros(len(kp), T), np.zeros(len(kp), bool)
+    ang2s = np.where((ang1s + pi3 > two_pi) & (not no_wrap), ang1s - pi53, ang1s + pi3).astype(T)
+    out, frag, adm = np.zeros(len(kp), T), np.zeros(len(kp), bool), [np.zeros(0, T) for _ in range(len(kp))]
     kp = np.asarray(kp, np.float32)
+
+    def member(ang, a1, a2, force=None):
+        """force: (near, value): samples of `near` are counted in (True) or out (False)"""
+        if a1 < a2:
+            m = (a1 < ang) & (ang < a2)
+        else:
+            m = (((ang >= 0) if zero_in else (ang > 0)) & (ang < a2)) | ((ang > a1) & (ang < two_pi) & (not no_high))
+        if force is not None:
+            m = np.where(force[0], force[1], m)
+        return m
+
+    def window(m, rx, ry):
+        sx, sy = T(0), T(0)
+        for t in np.flatnonzero(m):
+            sx, sy = sx + rx[t], sy + ry[t]
+        ba = np.arctan2(sy, sx).astype(T)
+        return sx * sx + sy * sy, (ba + two_pi if ba < 0 else ba)
+
     for q in range(len(kp)):
         xf, yf = kp[q, 0], kp[q, 1]                                 # float32 coordinates, float32 sample positions, as on the device
-        s = int(np.float32(kp[q, 2]) / np.float32(2.0) + np.float32(0.5))
-        lev = int(kp[q, 3])
-        ix = _fround(xf + (ii * s).astype(np.float32))
-        iy = _fround(yf + (jj * s).astype(np.float32))
+        s = int(np.float32(kp[q, 2]) / np.float32(2.0) + (np.float32(0.0) if size_floor else np.float32(0.5)))
+        lev = 0 if level0 else int(kp[q, 3])
+        rnd = (lambda v: np.floor(v + v.dtype.type(0.5)).astype(np.int64)) if floor_ else _fround
+        ix = rnd(xf + (ii * s).astype(np.float32))
+        iy = rnd(yf + (jj * s).astype(np.float32))
         ok = (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h)
+        if clamp:
+            ok[:] = True
+        if drop is not None:
+            ok[drop] = False
         cx, cy = np.clip(ix, 0, w - 1), np.clip(iy, 0, h - 1)
+        if transpose:
+            cx, cy = np.clip(iy, 0, w - 1), np.clip(ix, 0, h - 1)
         rx = np.where(ok, g * Lx[lev, cy, cx].astype(T), T(0))
         ry = np.where(ok, g * Ly[lev, cy, cx].astype(T), T(0))
         ang = np.arctan2(ry, rx).astype(T)
         ang = np.where(ang < 0, ang + two_pi, ang).astype(T)
         best, besta, members, scores = T(0), T(0), [], []
         for a1, a2 in zip(ang1s, ang2s):
-            if a1 < a2:
-                m = (a1 < ang) & (ang < a2)
-            else:
-                m = ((ang > 0) & (ang < a2)) | ((ang > a1) & (ang < two_pi))
-            sx, sy = T(0), T(0)
-            for t in np.flatnonzero(m):
-                sx, sy = sx + rx[t], sy + ry[t]
-            sc = sx * sx + sy * sy
+            m = member(ang, a1, a2)
+            sc, ba = window(m, rx, ry)
             members.append(m)
             scores.append(sc)
-            if sc > best:
+            if sc > best or (last_equal and sc == best and sc > 0):
                 best = sc
-                besta = np.arctan2(sy, sx).astype(T)
-                besta = besta + two_pi if besta < 0 else besta
+                besta = ba
         out[q] = besta
         if flags:
             live = (rx != 0) | (ry != 0)
@@ -328,21 +379,48 @@ def orientation(kp, Lx, Ly, dtype=np.float32, flags=False):
             close = any(abs(float(sc) - float(best)) < 1e-6 * float(best) and not np.array_equal(m, members[b])
                         for m, sc in zip(members, scores)) if best > 0 else True
             frag[q] = bool(near or close)
+            if admissible and frag[q]:
+                a64 = ang.astype(np.float64)
+                variants = []                                       # per window: [(score, angle), ...]
+                for a1, a2, m, sc in zip(ang1s, ang2s, members, scores):
+                    own = [float(a1), float(a2)] + ([0.0, float(two_pi)] if not a1 < a2 else [])
+                    nr = live & (np.abs(a64[:, None] - np.array(own)[None, :]).min(axis=1) < 1e-5)
+                    v = [window(m, rx, ry)]
+                    if nr.any():
+                        v += [window(member(ang, a1, a2, (nr, True)), rx, ry), window(member(ang, a1, a2, (nr, False)), rx, ry)]
+                    variants.append(v)
+                floor_score = max(min(float(sc) for sc, _ in v) for v in variants)
+                ok_a = [ba for v in variants for sc, ba in v if float(sc) > 0 and float(sc) >= floor_score * (1.0 - 1e-6)]
+                if floor_score == 0.0:
+                    ok_a.append(T(0))
+                adm[q] = np.array(ok_a, T)
+    if flags and admissible:
+        return out, frag, adm
     return (out, frag) if flags else out
 
 
 # ----------------------------------------------------------------------------------------------------------------- descriptor
-def descriptors(kp, Lx, Ly, dtype=np.float32, rotate_sign=1.0):
-    """n x 64 of a keypoint table (x, y, size, level, angle).  rotate_sign = -1 rotates the pattern the wrong way (a probe)."""
+def descriptors(kp, Lx, Ly, dtype=np.float32, rotate_sign=1.0, **mistakes):
+    """n x 64 of a keypoint table (x, y, size, level, angle).  rotate_sign = -1 rotates the pattern the wrong way (a probe).
+    Further mistakes (keywords): swap_sub (sub / 4 and sub % 4 swapped), swap_kl (k and l swapped in the sample's position), swap_rr (rrx and rry written to
+    the other array), zero_outside (a sample outside the picture reads 0 instead of the border), frac_after_clamp (the bilinear
+    fraction taken from the clamped index)"""
+    mk = lambda name: mistakes.pop(name, False)
+    swap_sub, swap_kl, swap_rr, zero_outside, frac_after_clamp = mk("swap_sub"), mk("swap_kl"), mk("swap_rr"), mk("zero_outside"), mk("frac_after_clamp")
+    assert not mistakes, mistakes
     T = dtype
     N, h, w = Lx.shape
     kp = np.asarray(kp, np.float32)
     out = np.zeros((len(kp), 64), T)
     sub = np.arange(16)
     i0, j0 = -12 + 5 * (sub // 4), -12 + 5 * (sub % 4)
+    if swap_sub:
+        i0, j0 = j0, i0
     r = np.arange(81)
     k = (i0[:, None] + r[None, :] // 9).astype(T)
     l = (j0[:, None] + r[None, :] % 9).astype(T)
+    if swap_kl:
+        k, l = l, k
     ky, kx = (i0 + 5).astype(T)[:, None], (j0 + 5).astype(T)[:, None]
     half = T(0.5)
 
@@ -365,14 +443,24 @@ def descriptors(kp, Lx, Ly, dtype=np.float32, rotate_sign=1.0):
             fx, fy = sx - flx, sy - fly
             y1, x1 = np.clip(fly.astype(np.int64), 0, h - 1), np.clip(flx.astype(np.int64), 0, w - 1)
             y2, x2 = np.clip(fly.astype(np.int64) + 1, 0, h - 1), np.clip(flx.astype(np.int64) + 1, 0, w - 1)
+            if frac_after_clamp:
+                fx, fy = sx - x1.astype(T), sy - y1.astype(T)
             one = T(1.0)
             w1, w2, w3, w4 = (one - fx) * (one - fy), fx * (one - fy), (one - fx) * fy, fx * fy
             PX, PY = Lx[lev].astype(T), Ly[lev].astype(T)
-            rx = ((w1 * PX[y1, x1] + w2 * PX[y1, x2]) + w3 * PX[y2, x1]) + w4 * PX[y2, x2]
-            ry = ((w1 * PY[y1, x1] + w2 * PY[y1, x2]) + w3 * PY[y2, x1]) + w4 * PY[y2, x2]
+            if zero_outside:
+                fi, fj = fly.astype(np.int64), flx.astype(np.int64)
+                z = lambda P, yy, xx, oy, ox: np.where((fi + oy >= 0) & (fi + oy < h) & (fj + ox >= 0) & (fj + ox < w), P[yy, xx], T(0))
+                rx = ((w1 * z(PX, y1, x1, 0, 0) + w2 * z(PX, y1, x2, 0, 1)) + w3 * z(PX, y2, x1, 1, 0)) + w4 * z(PX, y2, x2, 1, 1)
+                ry = ((w1 * z(PY, y1, x1, 0, 0) + w2 * z(PY, y1, x2, 0, 1)) + w3 * z(PY, y2, x1, 1, 0)) + w4 * z(PY, y2, x2, 1, 1)
+            else:
+                rx = ((w1 * PX[y1, x1] + w2 * PX[y1, x2]) + w3 * PX[y2, x1]) + w4 * PX[y2, x2]
+                ry = ((w1 * PY[y1, x1] + w2 * PY[y1, x2]) + w3 * PY[y2, x1]) + w4 * PY[y2, x2]
             rx, ry = g1 * rx, g1 * ry
             rry = rx * co + ry * si
             rrx = -rx * si + ry * co
+            if swap_rr:
+                rrx, rry = rry, rrx
             acc = np.zeros((16, 4), T)
             for t in range(81):
                 acc[:, 0] = acc[:, 0] + rrx[:, t]

@@ -267,9 +267,13 @@ def test_border_probes_sit_one_pixel_inside_and_outside_the_rule():
 def test_orientation_fragility_of_the_compared_pictures():
     for name in P.ORIENTED:
         d = P.oracle(name)
-        _, fragile = KO.orientation(d["kp"], d["ss"]["Lx"], d["ss"]["Ly"], flags=True)
-        print(f"{name}: {fragile.sum()} of {len(fragile)} keypoints fragile ({100 * fragile.mean():.1f} %)")
+        a, fragile, admissible = KO.orientation(d["kp"], d["ss"]["Lx"], d["ss"]["Ly"], flags=True, admissible=True)
+        print(f"{name}: {fragile.sum()} of {len(fragile)} keypoints fragile ({100 * fragile.mean():.1f} %), "
+              f"{max([len(set(admissible[q].tolist())) for q in np.flatnonzero(fragile)], default=0)} admissible angles at most")
         assert fragile.mean() <= 0.05 and (~fragile).sum() >= 50
+        assert np.array_equal(a, d["kp"][:, 4])
+        for q in range(len(a)):                                # the oracle's own choice is admissible; nothing is listed for the others
+            assert (a[q] in admissible[q].tolist()) if fragile[q] else len(admissible[q]) == 0, (name, q)
 
 
 MISTAKES = {"border": dict(border="symmetric"), "extremum": dict(strict=False), "sigma_size": dict(sigma_sq=False),
@@ -452,6 +456,39 @@ def test_match_workdir_files_markers_and_exit_codes(tmp_path, monkeypatch, capsy
     (tmp_path / "undistorted" / "00000001.png").unlink()
     assert FE.match_workdir(tmp_path) == -1
     assert "00000001.png" in capsys.readouterr().err
+
+
+def test_match_workdir_of_featureless_pictures_returns_minus_one(tmp_path, monkeypatch, capsys):
+    """A picture without features gives an empty feature set, which the matcher refuses (the real gt_match, before it touches a GPU):
+    the reference catches its matcher's exception and returns -1 (wass_match.cpp:363-371), so does match_workdir, with one line on
+    stderr, both progress markers and no matches_unfiltered.txt."""
+    from PIL import Image
+    some = lambda n: match.Features(np.arange(2 * n).reshape(n, 2), np.full(n, 5.0), np.zeros(n), np.eye(n, 64))
+
+    def detect_features(image, max_features=2000, options=None, subdivisions=5, min_distance=10.0, ctx=None):
+        if (image == image[0, 0]).all():
+            return match.Features(np.zeros((0, 2)), np.zeros(0), np.zeros(0), np.zeros((0, 64)))
+        if image.shape[0] < 23:
+            raise ValueError(f"image: {image.shape[0]} x {image.shape[1]} is smaller than the largest reflect-101 reach")
+        return some(12)
+    monkeypatch.setattr(FE, "detect_features", detect_features)
+    (tmp_path / "undistorted").mkdir()
+    textured = np.arange(40 * 50, dtype=np.uint8).reshape(40, 50)
+    for flat in ((0,), (1,), (0, 1)):
+        for cam in (0, 1):
+            Image.fromarray(np.full((40, 50), 7, np.uint8) if cam in flat else textured).save(tmp_path / "undistorted" / f"{cam:08d}.png")
+        assert FE.main([str(tmp_path)]) == -1
+        io = capsys.readouterr()
+        assert io.out.split() == ["[P|10|100]", "[P|20|100]"]
+        assert len(io.err.strip().splitlines()) == 1 and "feature" in io.err and "Traceback" not in io.err
+        assert not (tmp_path / "matches_unfiltered.txt").exists()
+    # a picture the detector refuses ends the same way, after its own marker
+    Image.fromarray(textured[:20]).save(tmp_path / "undistorted" / "00000001.png")
+    Image.fromarray(textured).save(tmp_path / "undistorted" / "00000000.png")
+    assert FE.match_workdir(tmp_path) == -1
+    io = capsys.readouterr()
+    assert io.out.split() == ["[P|10|100]", "[P|20|100]"] and len(io.err.strip().splitlines()) == 1 and "00000001.png" in io.err
+    assert not (tmp_path / "matches_unfiltered.txt").exists()
 
 
 def test_oracle_against_opencv_pin():

@@ -78,16 +78,20 @@ def _angle_diff(a, b):
 def test_orientation_of_the_oracles_keypoints(gpu_ctx, name):
     ref = P.oracle(name)
     ss, kp = ref["ss"], ref["kp"]
-    a32, fragile = KO.orientation(kp, ss["Lx"], ss["Ly"], np.float32, flags=True)
+    a32, fragile, admissible = KO.orientation(kp, ss["Lx"], ss["Ly"], np.float32, flags=True, admissible=True)
     a64 = KO.orientation(kp, ss["Lx"], ss["Ly"], np.float64)
     keep = ~fragile
     assert fragile.mean() <= 0.05 and keep.sum() >= 50
     got = FE.kaze_orientation(kp[:, :4], run(gpu_ctx, name)[0])
     tol = 0.5 * float(np.spacing(np.float32(2 * np.pi))) + 4.0 * _angle_diff(a32[keep], a64[keep]).max()
     err = _angle_diff(got[keep], a32[keep]).max()
-    print(f"{name}: {keep.sum()} keypoints, largest difference {err:.3g} rad, tolerance {tol:.3g} rad")
+    # a fragile keypoint is not compared with the oracle's one choice, but with every angle a correct float32 run may give
+    ferr = max([_angle_diff(admissible[q], got[q]).min() for q in np.flatnonzero(fragile)], default=0.0)
+    print(f"{name}: {keep.sum()} keypoints, largest difference {err:.3g} rad, tolerance {tol:.3g} rad; {fragile.sum()} fragile keypoints, "
+          f"{ferr:.3g} rad off their nearest admissible angle")
     assert (got >= 0).all() and (got < np.float32(2 * np.pi) + 1e-6).all()
     assert err <= tol
+    assert ferr <= tol
 
 
 @pytest.mark.parametrize("name", P.ORIENTED)

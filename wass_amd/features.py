@@ -579,8 +579,11 @@ def _bool(v) -> bool:
 def match_workdir(workdir, config=None, ctx=None) -> int:
     """wass_match up to matches_unfiltered.txt (wass_match.cpp:170-250): reads undistorted/0000000{0,1}.png of `workdir`, detects and
     subsamples the features of both, matches them and writes matches_unfiltered.txt; prints [P|10|100] and [P|20|100].  config: a
-    KEY=value file with the FEATURE_*, NUM_FEATURES_PER_IMAGE, AREA_SUBDIVISION and MATCHER_* keys.  Returns 0, or -1 on a missing
-    file.  epipolar.filter_workdir finishes the job."""
+    KEY=value file with the FEATURE_*, NUM_FEATURES_PER_IMAGE, AREA_SUBDIVISION and MATCHER_* keys.  Returns 0, or -1 with one line on
+    stderr: on a missing file, and where the detector or the matcher refuses its input (a picture without features, one smaller than
+    the derivatives' reach, options out of range), as the reference catches its extractor's and matcher's exceptions
+    (wass_match.cpp:363-371).  matches_unfiltered.txt is written only after the matcher has returned.  epipolar.filter_workdir
+    finishes the job."""
     from . import epipolar
     from PIL import Image
     wd = os.fspath(workdir)
@@ -600,11 +603,19 @@ def match_workdir(workdir, config=None, ctx=None) -> int:
             print(f"Unable to open undistorted/{cam:08d}.png", file=sys.stderr)
             return -1
         print(mark, flush=True)
-        feats.append(detect_features(img, int(cfg.get("NUM_FEATURES_PER_IMAGE", 2000)), opts, int(cfg.get("AREA_SUBDIVISION", 5)),
-                                     float(cfg.get("FEATURE_MIN_DISTANCE", 10.0)), ctx))
-    r = _match.gt_match(feats[0], feats[1], lam=float(cfg.get("MATCHER_LAMBDA", 1e-5)),
-                        pop_threshold=float(cfg.get("MATCHER_POPULATION_THRESHOLD", 0.7)), min_group_size=int(cfg.get("MATCHER_MIN_GROUP_SIZE", 5)),
-                        max_rounds=int(cfg.get("MATCHER_MAX_ROUNDS", 20)), skip_gt=_bool(cfg.get("MATCHER_SKIP_GT", "false")), ctx=ctx)
+        try:
+            feats.append(detect_features(img, int(cfg.get("NUM_FEATURES_PER_IMAGE", 2000)), opts, int(cfg.get("AREA_SUBDIVISION", 5)),
+                                         float(cfg.get("FEATURE_MIN_DISTANCE", 10.0)), ctx))
+        except (ValueError, RuntimeError) as ex:
+            print(f"wass_amd.features: undistorted/{cam:08d}.png: {ex}", file=sys.stderr)
+            return -1
+    try:
+        r = _match.gt_match(feats[0], feats[1], lam=float(cfg.get("MATCHER_LAMBDA", 1e-5)),
+                            pop_threshold=float(cfg.get("MATCHER_POPULATION_THRESHOLD", 0.7)), min_group_size=int(cfg.get("MATCHER_MIN_GROUP_SIZE", 5)),
+                            max_rounds=int(cfg.get("MATCHER_MAX_ROUNDS", 20)), skip_gt=_bool(cfg.get("MATCHER_SKIP_GT", "false")), ctx=ctx)
+    except (ValueError, RuntimeError) as ex:
+        print(f"wass_amd.features: {len(feats[0])} and {len(feats[1])} features: {ex}", file=sys.stderr)
+        return -1
     _match.write_matches(os.path.join(wd, "matches_unfiltered.txt"), r)
     return 0
 
