@@ -5,7 +5,8 @@ sosfiltfilt restates scipy.signal.sosfiltfilt(sos, x, axis=0) with scipy's defau
 dtype (float32: 2 x[0] - x[k] is rounded before anything becomes wider), the steady state zi is in closed form, the
 recurrence is transposed direct form II in scipy's order of operations, one sample at a time, vectorised over the series.
 `dtype` is the precision of state and arithmetic: np.float64 is what scipy computes, np.longdouble measures the
-recurrence's own fp64 noise (noise()).
+recurrence's own fp64 noise (noise()).  `padlen` is scipy's argument (None: its default; 0: no extension); VARIANTS are known
+mistakes for showing what the tests can tell, never compared with the GPU.
 """
 import numpy as np
 
@@ -13,6 +14,9 @@ import numpy as np
 def padlen(sos):
     sos = np.asarray(sos)
     return 3 * (2 * sos.shape[0] + 1 - int(min((sos[:, 2] == 0).sum(), (sos[:, 5] == 0).sum())))
+
+
+default_padlen = padlen          # sosfiltfilt's own argument is called padlen, as scipy's is
 
 
 def sosfilt_zi(sos, dtype=np.float64):
@@ -29,45 +33,77 @@ def sosfilt_zi(sos, dtype=np.float64):
     return zi
 
 
-def _sosfilt(sos, x, zi):
+def _fma(a, b, c):
+    """a * b + c rounded once, approximately: the product and the sum in np.longdouble (64-bit significand on x86-64), then one rounding
+    to fp64.  An APPROXIMATION of an fma (the exact product has 106 bits, and where long double is fp64 this is no fma at all): enough
+    to show that a contracted update does not hide, not a model of the hardware instruction."""
+    L = np.longdouble
+    return (np.asarray(a, L) * np.asarray(b, L) + np.asarray(c, L)).astype(np.float64)
+
+
+# One known mistake each, for showing that the probes of tests/filter_probes.py tell it from the oracle (tests/test_filter_edges.py).
+# Never compared with the GPU.
+VARIANTS = {"reassociated": dict(update="reassociated"),            # z0 = b1 x + (z1 - a1 y)
+            "contracted": dict(first="contracted"),                 # y = fma(b0, x, z0), see _fma
+            "padding in fp64": dict(pad="fp64"),                    # 2 x[0] - x[k] formed in fp64
+            "mean summed pairwise": dict(mean="pairwise")}          # np.mean over a contiguous copy of each series
+
+
+def _sosfilt(sos, x, zi, update="scipy", first="scipy"):
     """x [n, ...] (overwritten with the output), zi [n_sections, 2, ...]"""
     for n in range(x.shape[0]):
         xc = x[n]
         for s in range(sos.shape[0]):
-            y = sos[s, 0] * xc + zi[s, 0]
-            zi[s, 0] = (sos[s, 1] * xc - sos[s, 4] * y) + zi[s, 1]
+            y = _fma(sos[s, 0], xc, zi[s, 0]) if first == "contracted" else sos[s, 0] * xc + zi[s, 0]
+            if update == "reassociated":
+                zi[s, 0] = sos[s, 1] * xc + (zi[s, 1] - sos[s, 4] * y)
+            else:
+                zi[s, 0] = (sos[s, 1] * xc - sos[s, 4] * y) + zi[s, 1]
             zi[s, 1] = sos[s, 2] * xc - sos[s, 5] * y
             xc = y
         x[n] = xc
     return x
 
 
-def sosfiltfilt(sos, x, dtype=np.float64, remove_mean=False):
-    """x: [count, ...] float32.  The filtered series in `dtype` (not cast to float32)."""
+def sosfiltfilt(sos, x, dtype=np.float64, remove_mean=False, padlen=None, update="scipy", first="scipy", pad="input", mean="frames", zi=None):
+    """x: [count, ...] float32.  The filtered series in `dtype` (not cast to float32).  padlen: None for scipy's default, else
+    0 <= padlen < count as scipy takes it (0: no extension, both passes start from zi times their first sample).  update, first,
+    pad, mean: see VARIANTS; the defaults are scipy's arithmetic.  zi: the steady state [n_sections, 2] to start from instead of
+    the closed form of sosfilt_zi (scipy's own comes out of a LAPACK solve and differs from it in the last bits)."""
     x = np.asarray(x)
     assert x.dtype == np.float32
-    edge = padlen(sos)
+    edge = default_padlen(sos) if padlen is None else int(padlen)
+    if edge < 0:
+        raise ValueError("padlen must not be negative")
     if x.shape[0] <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
-    ext = np.concatenate((2 * x[:1] - x[edge:0:-1], x, 2 * x[-1:] - x[-2:-(edge + 2):-1]), axis=0) if edge else x.copy()
-    assert ext.dtype == np.float32
-    s = np.asarray(sos, np.float64).astype(dtype)
-    zi = sosfilt_zi(np.asarray(sos, np.float64), dtype).reshape((s.shape[0], 2) + (1,) * (x.ndim - 1))
-    y = ext.astype(dtype)
-    y = _sosfilt(s, y, zi * y[:1])
-    y = y[::-1].copy()
-    y = _sosfilt(s, y, zi * y[:1])[::-1]
-    y = y[edge:y.shape[0] - edge] if edge else y
-    if remove_mean:
-        y = y - np.mean(y, axis=0, keepdims=True)
+    with np.errstate(invalid="ignore", over="ignore"):
+        xp = x.astype(np.float64) if pad == "fp64" else x
+        ext = np.concatenate((2 * xp[:1] - xp[edge:0:-1], xp, 2 * xp[-1:] - xp[-2:-(edge + 2):-1]), axis=0) if edge else x.copy()
+        assert ext.dtype == xp.dtype
+        s = np.asarray(sos, np.float64).astype(dtype)
+        zi = sosfilt_zi(np.asarray(sos, np.float64), dtype) if zi is None else np.asarray(zi, np.float64).astype(dtype)
+        zi = zi.reshape((s.shape[0], 2) + (1,) * (x.ndim - 1))
+        y = ext.astype(dtype)
+        y = _sosfilt(s, y, zi * y[:1], update, first)
+        y = y[::-1].copy()
+        y = _sosfilt(s, y, zi * y[:1], update, first)[::-1]
+        y = y[edge:y.shape[0] - edge] if edge else y
+        if remove_mean:
+            if mean == "pairwise":
+                m = np.mean(np.ascontiguousarray(np.moveaxis(y, 0, -1)), axis=-1)[None]
+            else:
+                m = np.mean(y, axis=0, keepdims=True)
+            y = y - m
     return np.ascontiguousarray(y)
 
 
-def noise(sos, x, remove_mean=False):
+def noise(sos, x, remove_mean=False, padlen=None):
     """(oracle64, n): n = the largest |oracle64 - oracle_longdouble| over the series that hold no NaN."""
-    o64 = sosfiltfilt(sos, x, np.float64, remove_mean)
-    old = sosfiltfilt(sos, x, np.longdouble, remove_mean)
-    d = np.abs(o64.astype(np.longdouble) - old)
+    o64 = sosfiltfilt(sos, x, np.float64, remove_mean, padlen)
+    old = sosfiltfilt(sos, x, np.longdouble, remove_mean, padlen)
+    with np.errstate(invalid="ignore"):
+        d = np.abs(o64.astype(np.longdouble) - old)
     return o64, float(np.nanmax(d)) if np.isfinite(d).any() else 0.0
 
 
