@@ -1002,6 +1002,74 @@ int wass_epi_find_dev(wass_ctx* ctx, const double* d_x0, const double* d_x1, siz
                       size_t sample_stride, const int* m, const double* t, int rounds, int batch, double* E, int* best_index, int* best_count,
                       uint8_t* d_mask, float* d_err, size_t out_stride);
 
+/* ---- Autocalibration: what wass_autocalibrate does between the matcher and the stereo stage (src/wass_autocalibrate/): the choice
+ * among the four poses of an essential matrix and the bundle adjustment of two cameras over N points seen by both (sba's
+ * sba_motstr_levmar_x with no constant frame).  Everything is fp64 without contraction; every product, sum, quotient and square
+ * root below is rounded on its own, in the order the parentheses give.
+ *
+ * wass_ac_triangulate: R4 (host, 4 x 9 row-major) and T4 (host, 4 x 3) are the candidates; one thread per (candidate, match).  With
+ * p = x0, q = x1 of the match, the 4 x 3 system has the rows (-1, 0, p0), (0, -1, p1), r2 and r3 and the right side (0, 0, b2, b3):
+ *     r2k = q0 R[2][k] - R[0][k]     r3k = q1 R[2][k] - R[1][k]     b2 = T0 - T2 q0     b3 = T1 - T2 q1
+ *     a = (1 + r20 r20) + r30 r30    b = r20 r21 + r30 r31          c = (r20 r22 - p0) + r30 r32
+ *     d = (1 + r21 r21) + r31 r31    e = (r21 r22 - p1) + r31 r32   f = ((p0 p0 + p1 p1) + r22 r22) + r32 r32
+ *     yk = r2k b2 + r3k b3
+ *     C00 = d f - e e   C01 = c e - b f   C02 = b e - c d   C11 = a f - c c   C12 = b c - a e   C22 = a d - b b
+ *     det = (a C00 + b C01) + c C02
+ *     X = ((C00 y0 + C01 y1) + C02 y2) / det   Y = ((C01 y0 + C11 y1) + C12 y2) / det   Z = ((C02 y0 + C12 y1) + C22 y2) / det
+ * det zero or not finite: the point is NaN.  d_pts: 4 x m x 3; counts (host, 4): per candidate the matches with mask != 0 and
+ * Z > 1 (a NaN counts nowhere), exact.
+ *
+ * A camera is 15 doubles: R0 (9, row-major, fixed), v (3) and t (3).  With s = (v0 v0 + v1 v1) + v2 v2, w = sqrt(1 - s) (NaN for
+ * |v| > 1), Rl[r][k] = I[r][k] + 2 (w [v]x[r][k] + (v_r v_k - s I[r][k])) and Rj[r][k] = (Rl[r][0] R0[0][k] + Rl[r][1] R0[1][k]) +
+ * Rl[r][2] R0[2][k] (host arithmetic), a point M projects to
+ *     X_r = ((Rj[r][0] M0 + Rj[r][1] M1) + Rj[r][2] M2) + t_r      iz = 1 / X2      px = X0 iz      py = X1 iz
+ * and the residual is (ex, ey) = (u - px, v - py) of the measured (u, v): obs holds (u0, v0, u1, v1) per point, pts (X, Y, Z).
+ * The Jacobian rows, with Y_r = (R0[r][0] M0 + R0[r][1] M1) + R0[r][2] M2, c = v x Y (c0 = v1 Y2 - v2 Y1, ...),
+ * h = (v0 Y0 + v1 Y1) + v2 Y2, g_r = w Y_r + c_r, G_r = (1 / w) c_r + Y_r:
+ *     D[r][k] = 2 ((h I[r][k] - G_r v_k) - [g]x[r][k])                                   dX / dv; off the diagonal 0 - G_r v_k
+ *     ax_k = iz (D[0][k] - px D[2][k])   ay_k = iz (D[1][k] - py D[2][k])                k = 0 .. 2
+ *     ax_3..5 = iz, 0, -(px iz)          ay_3..5 = 0, iz, -(py iz)
+ *     bx_k = iz (Rj[0][k] - px Rj[2][k]) by_k = iz (Rj[1][k] - py Rj[2][k])
+ * and per point, camera 0 first: V_kl = (bx_k bx_l + by_k by_l)_0 + (...)_1, eb_k = (bx_k ex + by_k ey)_0 + (...)_1,
+ * W_j[a][k] = ax_a bx_k + ay_a by_k, |e_i|^2 = (ex ex + ey ey)_0 + (...)_1; per camera U_j[a][b] = sum_i ax_a ax_b + ay_a ay_b and
+ * ea_j[a] = sum_i ax_a ex + ay_a ey.
+ *
+ * wass_ac_linearize: d_lin (may be null) gets WASS_AC_LIN_ROWS rows of n: ex0 ey0 ex1 ey1, V (00 01 02 11 12 22), eb (3),
+ * W_0 (18, a-major), W_1 (18).  sums (host, WASS_AC_LIN_SUMS): the lower triangles of U_0 and U_1 by rows (21 each), ea (12),
+ * |e|^2, max_i,k |eb_i,k| and max_i,k V_i,kk.
+ *
+ * wass_ac_step: one Schur step at mu from the linearisation at (cams, pts).  Per point Vi = (V_i + mu I)^-1 by the cofactor
+ * rule (as C00 .. det above with a, d, f the damped diagonal; Vi = C (1 / det)), Y_p = (W_p0 Vi_0k + W_p1 Vi_1k) + W_p2 Vi_2k
+ * for the 12 stacked rows of W_0, W_1, the sums T_pq = sum_i (Y_p0 W_q0 + Y_p1 W_q1) + Y_p2 W_q2 and r_p = sum_i (Y_p0 eb0 +
+ * Y_p1 eb1) + Y_p2 eb2; S = diag(U_0 + mu I, U_1 + mu I) - T and rhs = ea - r on the host (S: 144, rhs: 12), a Cholesky
+ * factorisation by rows and two triangular solves give da (12: v and t of camera 0, then of camera 1).  *ok = 0 when a pivot or
+ * an entry of da is not positive or not finite: a rejected step, with da and scal zero.  Otherwise per point
+ *     g_k = eb_k - (((W[0][k] da_0 + W[1][k] da_1) + ...) + W[11][k] da_11)     db_r = (Vi_r0 g0 + Vi_r1 g1) + Vi_r2 g2
+ * d_db and d_pts_new = pts + db (n x 3 each, may be null), cams_new = cams with da added to v and t (host, 30), and scal (host,
+ * 4): |e_new|^2 at the candidate, |dp|^2, |p|^2 and dL = dp' (mu dp + J'e), each the points' sum and then the cameras' terms.
+ *
+ * wass_ac_error: |e|^2 at (cams, pts); d_res (may be null) 4 rows of n.
+ *
+ * wass_ac_bundle: the Levenberg-Marquardt loop of sba on the host, restated from knowledge: mu = 1e-3 max diag(J'J),
+ * additive damping, Nielsen's update, thresholds 1e-12.  cams (host, 30) and d_pts are updated in place to the last accepted
+ * step.  info (host, 8): initial and final |e|^2, iterations, stop reason (1 gradient, 2 step, 3 iterations, 4 step too large, 5
+ * damping overflow, 6 error, 7 not finite), mu, the gradient's infinity norm, |dp|^2 of the last solve, solves.
+ *
+ * Reductions: a workgroup is one wave of 64 and sums with the tree l += l + 32, 16, 8, 4, 2, 1 (a lane past n adds 0.0); the
+ * workgroups are then added in ascending order.  The per-point results do not depend on n.  1 <= n, m <= WASS_AC_MAX_N.
+ * wass_ac_scratch_bytes: the context's device memory for n points; no GPU needed.  Every call returns after a synchronisation. */
+#define WASS_AC_LIN_ROWS 49
+#define WASS_AC_LIN_SUMS 57
+#define WASS_AC_MAX_N (1 << 22)
+int wass_ac_scratch_bytes(int n, size_t* bytes);
+int wass_ac_triangulate_dev(wass_ctx* ctx, const double* d_x0, const double* d_x1, const uint8_t* d_mask, int m, const double* R4, const double* T4,
+                            double* d_pts, int32_t* counts);
+int wass_ac_linearize_dev(wass_ctx* ctx, const double* cams, const double* d_pts, const double* d_obs, int n, double* d_lin, double* sums);
+int wass_ac_step_dev(wass_ctx* ctx, const double* cams, const double* d_pts, const double* d_obs, int n, double mu, double* S, double* rhs,
+                     double* da, double* d_db, double* d_pts_new, double* cams_new, double* scal, int* ok);
+int wass_ac_error_dev(wass_ctx* ctx, const double* cams, const double* d_pts, const double* d_obs, int n, double* d_res, double* err);
+int wass_ac_bundle_dev(wass_ctx* ctx, double* cams, double* d_pts, const double* d_obs, int n, int max_iters, double* info);
+
 /* Coll-1: NaN-aware mean of per-frame planes (np.nanmean of planes.txt,
  * gridding/wassgridsurface/wassgridsurface.py:672-678).  Reduces
  * [sum a, sum b, sum c, sum d, n_valid] into acc5 (caller all-reduces acc5

@@ -296,6 +296,12 @@ SYMBOLS = {
     "wass_epi_mask_dev": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _i, _vp, _vp, _sz]),
     "wass_epi_find_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, C.POINTER(_i), C.POINTER(C.c_double), _i, _i, _vp, C.POINTER(_i), C.POINTER(_i),
                                _vp, _vp, _sz]),
+    "wass_ac_scratch_bytes": (_i, [_i, C.POINTER(_sz)]),
+    "wass_ac_triangulate_dev": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, C.POINTER(C.c_int32)]),
+    "wass_ac_linearize_dev": (_i, [_vp, C.POINTER(C.c_double), _vp, _vp, _i, _vp, C.POINTER(C.c_double)]),
+    "wass_ac_step_dev": (_i, [_vp, C.POINTER(C.c_double), _vp, _vp, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
+    "wass_ac_error_dev": (_i, [_vp, C.POINTER(C.c_double), _vp, _vp, _i, _vp, C.POINTER(C.c_double)]),
+    "wass_ac_bundle_dev": (_i, [_vp, C.POINTER(C.c_double), _vp, _vp, _i, _i, C.POINTER(C.c_double)]),
     "wass_kaze_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
     "wass_kaze_convert_dev": (_i, [_vp, _vp, _sz, _i, _i, C.c_float, _vp]),
     "wass_kaze_gauss_dev": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),

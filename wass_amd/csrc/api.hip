@@ -160,7 +160,7 @@ void wass_ctx_destroy(wass_ctx* c)
     mesh_pool_purge(c);
     for (Buf* b : { &c->bt1, &c->bt2, &c->hsum, &c->C, &c->S, &c->ckpt, &c->sel_d16, &c->sel_key, &c->raw,
                     &c->flags, &c->tmp_in0, &c->tmp_in1, &c->tmp_out, &c->tmp_mask, &c->fA, &c->fB, &c->fC, &c->fD, &c->fE, &c->uf, &c->rs_r, &c->rs_l, &c->raw2, &c->grid, &c->dct, &c->dct_io, &c->scratch, &c->counters, &c->tri_cnt, &c->inl, &c->inl2, &c->clahe_lut, &c->prep_pol, &c->qsel, &c->ccmask, &c->und_cache[0].xy, &c->und_cache[1].xy, &c->dstate, &c->rect_tab, &c->lanczos_tab, &c->bilinear_tab, &c->rect_mx, &c->rect_my, &c->xyzc, &c->limits, &c->jpeg_scratch, &c->jpeg_huff,
-                    &c->jpeg_out, &c->jpeg_info, &c->jpeg_part, &c->match, &c->match_io, &c->epi })
+                    &c->jpeg_out, &c->jpeg_info, &c->jpeg_part, &c->match, &c->match_io, &c->epi, &c->ac })
         release(*b);
     for (auto& e : c->ev_dbg) if (e) (void)hipEventDestroy(e);
     for (auto& k : c->kev) { if (k.a) (void)hipEventDestroy(k.a); if (k.b) (void)hipEventDestroy(k.b); }

@@ -201,6 +201,7 @@ struct wass_ctx {
     wass::Buf qsel;                // wass_quantiles_f64_dev: the selection record and the per-query histogram copies (grid_setup.hip)
     wass::Buf match, match_io;     // feature matcher: candidate transforms and per-problem records / host-pointer staging (match.hip)
     wass::Buf epi;                 // essential-matrix filter: sizes, models, solution and inlier counts, the best per pair (epipolar.hip)
+    wass::Buf ac;                  // autocalibration: partial sums, the per-point records of the bundle adjustment (autocal.hip)
     // stage events of the SGM call, two sets used alternately so that the timings of call n can be read after call
     // n+1 has been enqueued (a lagging reader never stalls the pipeline)
     // (four sets, not two, since round 5: a driver that runs two frames ahead reads call n's timings after call n+2 has been enqueued)
