@@ -1247,6 +1247,48 @@ int wass_kaze_orientation_dev(wass_ctx* ctx, const float* d_kp, int n, const flo
 int wass_kaze_descriptors_dev(wass_ctx* ctx, const float* d_kp, int n, const float* d_lx, const float* d_ly, size_t plane_stride, int n_levels,
                               int h, int w, float* d_desc);
 
+/* ---- variational refinement of the gridded surface (vref.hip; wass_amd/refinement.py) ------------------------------------------
+ * gridding/wassgridsurface/TFVariationalRefinement.py: a half-resolution height field Zc [ny / 2][nx / 2] is moved by Adam so that
+ * the two pictures, sampled where the nodes of Z = resize(Zc) project, agree, with a derivative-of-Gaussian smoothness term.
+ * Everything is float32 in the order written at the head of vref.hip (projection sums left to right, the 49 taps in row-major
+ * order, tfa's bilinear sampler, tf.image.resize with half-pixel centres, Keras's Adam with beta 0.9 / 0.999), without
+ * contraction; the gradient is derived by hand and is one sequence of operations per node, so a trajectory does not depend on
+ * the launch shape.  The two loss sums are fp64.  Restated from knowledge, not pinned against TensorFlow.
+ *
+ * Every d_ pointer is device memory, contiguous; every call runs on the context's stream and returns after a synchronisation.
+ * create: the set-up is copied into the handle's own allocation (scratch_bytes says how large): d_xb = XX / baseline and
+ *   d_yb = YY / baseline [ny][nx] float32, d_mask [ny][nx] float32, the two pictures as float32 [ih][iw]; Rp2c, Tp2c, P0cam,
+ *   P1cam are host fp64 and are cast to float32; kernels: host, 2 x 49 float32, the x then the y derivative kernel, row-major.
+ *   2 <= ny, nx, ih, iw <= 32768; values that are not finite are refused.
+ * sample:   d_I0s, d_I1s [ny][nx] and d_uv [4][ny][nx] = u0, v0, u1, v1 for a full-resolution d_Z.  A node with s_k2 <= 0 or a
+ *           coordinate that is not finite in either camera samples 0 in both and adds nothing to the data term or its gradient.
+ * zgrad:    the two correlations of d_Z with the kernels, zero padding.
+ * loss:     data = mean(((I0s - I1s) / 255)^2), smoothness = mean(Zdx^2 + Zdy^2) over all ny * nx nodes.
+ * gradient: d(data + alpha * smoothness) / dZc into d_gC [ny / 2][nx / 2]; d_gZ (may be null): the same with respect to Z.
+ * adjoint:  the backward half alone, on planes given by the caller: gZ = d_gd + cS * (the correlations of d_Zdx and d_Zdy with the flipped
+ *           kernels), cS = float32(2 alpha / (ny nx)), then d_gC = the adjoint of the resize applied to gZ.  What gradient runs after
+ *           its forward half; it lets a test put a single value into one plane and read the footprint.
+ * optimize: `iters` Adam steps on d_Zc in place.  d_m, d_v and *step are the optimiser's state, in and out (zeros and 0 to start):
+ *           a run continued through them equals one longer run bit for bit.  trace (host, may be null): rows of four doubles
+ *           [steps done in this call, data, smoothness, data + alpha * smoothness]: before the first step, after step i (from 0)
+ *           where i % report_every == 0, and after the last one; report_every <= 0: the first and the last only.  At most trace_cap
+ *           rows, *n_trace written.  The rows are made on the device and read once at the end; no iteration waits for the host.
+ *           d_Zout (may be null): resize(Zc) * mask [ny][nx].
+ * A Z, Zc, m or v that holds a value that is not finite, iters < 0 and null pointers return WASS_ERR_INVALID_ARG. */
+typedef struct wass_vref wass_vref;
+int wass_vref_scratch_bytes(int ny, int nx, int ih0, int iw0, int ih1, int iw1, size_t* bytes);
+int wass_vref_create(wass_ctx* ctx, int ny, int nx, const float* d_xb, const float* d_yb, const float* d_mask, const double Rp2c[9],
+                     const double Tp2c[3], const double P0cam[12], const double P1cam[12], const float* d_I0, int ih0, int iw0,
+                     const float* d_I1, int ih1, int iw1, const float* kernels, wass_vref** out);
+void wass_vref_destroy(wass_vref* h);
+int wass_vref_sample(wass_vref* h, const float* d_Z, float* d_I0s, float* d_I1s, float* d_uv);
+int wass_vref_zgrad(wass_vref* h, const float* d_Z, float* d_Zdx, float* d_Zdy);
+int wass_vref_loss(wass_vref* h, const float* d_Z, double* data_loss, double* smoothness_loss);
+int wass_vref_gradient(wass_vref* h, const float* d_Zc, double alpha, float* d_gC, float* d_gZ);
+int wass_vref_adjoint(wass_vref* h, const float* d_Zdx, const float* d_Zdy, const float* d_gd, double alpha, float* d_gC, float* d_gZ);
+int wass_vref_optimize(wass_vref* h, float* d_Zc, float* d_m, float* d_v, int64_t* step, int iters, double alpha, double lr, double eps,
+                       int report_every, double* trace, int trace_cap, int* n_trace, float* d_Zout);
+
 #ifdef __cplusplus
 }
 #endif

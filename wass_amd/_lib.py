@@ -314,6 +314,17 @@ SYMBOLS = {
     "wass_kaze_refine_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _i, _vp]),
     "wass_kaze_orientation_dev": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "wass_kaze_descriptors_dev": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "wass_vref_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_sz)]),
+    "wass_vref_create": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_double), _vp, _i, _i, _vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "wass_vref_destroy": (None, [_vp]),
+    "wass_vref_sample": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "wass_vref_zgrad": (_i, [_vp, _vp, _vp, _vp]),
+    "wass_vref_loss": (_i, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "wass_vref_gradient": (_i, [_vp, _vp, C.c_double, _vp, _vp]),
+    "wass_vref_adjoint": (_i, [_vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "wass_vref_optimize": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int64), _i, C.c_double, C.c_double, C.c_double, _i, _vp, _i,
+                                C.POINTER(_i), _vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

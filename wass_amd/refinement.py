@@ -1,0 +1,283 @@
+"""Variational refinement of the gridded surface on the GPU: the reference's TFVariationalRefinement
+(gridding/wassgridsurface/TFVariationalRefinement.py) without TensorFlow.
+
+    from wass_amd.refinement import VariationalRefinement      # instead of: from TFVariationalRefinement import TFVariationalRefinement
+
+VariationalRefinement(I0, I1, Rp2c, Tp2c, P0cam, P1cam, XX, YY, baseline, mask) takes the reference's constructor arguments and has
+its methods: sample_images(Z), compute_Z_gradient(Z), compute_loss(Z), optimize(Zinit, max_iters, alpha).  Every grid node is
+projected into both cameras, the two pictures are sampled there, and a half-resolution height field is moved by Adam so that the
+samples agree, under a derivative-of-Gaussian smoothness term.  The gradient TensorFlow derived is written out by hand in
+csrc/vref.hip (energy_gradient returns it); the whole loop runs on the context's stream without a host round trip.
+
+Differences: the coarse field is (Ny // 2) x (Nx // 2) (the reference transposes the size of a
+non-square grid); a Zinit that is not finite is refused; a node behind a camera adds nothing to the data term; Adam,
+tf.image.resize and tfa's sampler are restated from their published definitions, not pinned against TensorFlow.
+
+refine_surface(Zi, mask, I0, I1, gridsetup) is what the commented block of the reference's grid() amounts to
+(wassgridsurface.py:382-435).  Pictures may be uint8 or float32; every array may be a host array or a device tensor, and a
+result comes back on the side its Z came from.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+
+import numpy as np
+
+from .stereo import Context
+
+ADAM_BETA_1, ADAM_BETA_2 = 0.9, 0.999       # Keras's defaults, compiled into the library
+
+
+def derivative_of_gaussian_win(N: int, sigma: float = 1.0):
+    """The reference's derivative_of_Gaussian_win: np.gradient along x and y of the outer product of
+    scipy.signal.windows.gaussian(N, sigma) with itself (exp(-n^2 / (2 sigma^2)), n = 0 .. N-1 about (N-1) / 2), fp64."""
+    N = int(N)
+    if N < 3 or N % 2 != 1:
+        raise ValueError(f"N = {N}: an odd size of at least 3")
+    if not sigma > 0:
+        raise ValueError("sigma must be positive")
+    n = np.arange(N, dtype=np.float64) - (N - 1) / 2.0
+    x = np.exp(-n ** 2 / (2 * float(sigma) * float(sigma)))[np.newaxis]
+    x = x.T @ x
+    return np.gradient(x, axis=1), np.gradient(x, axis=0)
+
+
+def downsample_linear(Z, hc: int, wc: int) -> np.ndarray:
+    """cv.resize(Z, (wc, hc), interpolation=cv.INTER_LINEAR) for a float32 picture, restated in float32 on the host: per axis
+    f = (float)((d + 0.5) * (in / out) - 0.5) from fp64, s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= in - 1: s = in - 1, f = 0;
+    a row is S[s] * (1 - f) + S[s + 1] * f, and the rows are combined by the same rule."""
+    Z = np.asarray(Z, np.float32)
+    one = np.float32(1)
+
+    def axis(n_in, n_out):
+        f = ((np.arange(n_out) + 0.5) * (n_in / n_out) - 0.5).astype(np.float32)
+        s = np.floor(f).astype(np.int64)
+        f = f - s.astype(np.float32)
+        low, high = s < 0, s >= n_in - 1
+        f[low | high] = 0
+        s[low] = 0
+        s[high] = n_in - 1
+        return s, np.minimum(s + 1, n_in - 1), f
+
+    ys, ys1, fy = axis(Z.shape[0], hc)
+    xs, xs1, fx = axis(Z.shape[1], wc)
+    rows = Z[:, xs] * (one - fx)[np.newaxis] + Z[:, xs1] * fx[np.newaxis]
+    return np.ascontiguousarray(rows[ys] * (one - fy)[:, np.newaxis] + rows[ys1] * fy[:, np.newaxis])
+
+
+def _is_device(a) -> bool:
+    return hasattr(a, "data_ptr")
+
+
+@dataclasses.dataclass
+class AdamState:
+    """The optimiser's state after `step` steps; m, v: (Ny // 2) x (Nx // 2) float32, on the side Zc came from."""
+    m: object
+    v: object
+    step: int = 0
+
+
+class VariationalRefinement:
+    def __init__(self, I0, I1, Rp2c, Tp2c, P0cam, P1cam, XX, YY, baseline, mask, ctx: Context | None = None):
+        shape = tuple(int(v) for v in XX.shape)
+        if len(shape) != 2 or tuple(YY.shape) != shape or tuple(mask.shape) != shape:
+            raise ValueError(f"XX, YY and mask must be one Ny x Nx shape, got {tuple(XX.shape)}, {tuple(YY.shape)}, {tuple(mask.shape)}")
+        if min(shape) < 2:
+            raise ValueError(f"a grid of {shape[0]} x {shape[1]}: at least 2 x 2 nodes")
+        for name, I in (("I0", I0), ("I1", I1)):
+            if len(I.shape) != 2 or min(int(v) for v in I.shape) < 2:
+                raise ValueError(f"{name} of shape {tuple(I.shape)}: a picture of at least 2 x 2 pixels")
+        baseline = float(baseline)
+        if not np.isfinite(baseline) or baseline == 0:
+            raise ValueError("baseline must be finite and not 0")
+        mats = []
+        for name, m, shp in (("Rp2c", Rp2c, (3, 3)), ("Tp2c", Tp2c, (3,)), ("P0cam", P0cam, (3, 4)), ("P1cam", P1cam, (3, 4))):
+            a = np.ascontiguousarray(np.asarray(m, np.float64))
+            if a.size != int(np.prod(shp)) or not np.isfinite(a).all():
+                raise ValueError(f"{name}: {' x '.join(map(str, shp))} finite values expected")
+            mats.append(a.reshape(-1))
+        self.shape = shape
+        self.coarse_shape = (shape[0] // 2, shape[1] // 2)
+        self.losses = np.zeros((0, 4))
+        self.state = None                                        # the AdamState the last optimize() ended with
+        self._h = None
+        self._ctx = ctx if ctx is not None else Context(0)
+        import torch
+        self._dev = torch.device("cuda", self._ctx.device_id)
+        # the reference's casts: fp64 quotients, then float32
+        xb = self._to_dev(XX, torch.float64) / baseline
+        yb = self._to_dev(YY, torch.float64) / baseline
+        planes = [xb.to(torch.float32).contiguous(), yb.to(torch.float32).contiguous(), self._to_dev(mask, torch.float32),
+                  self._to_dev(I0, torch.float32), self._to_dev(I1, torch.float32)]
+        dsx, dsy = derivative_of_gaussian_win(7, sigma=0.8)
+        kernels = np.ascontiguousarray(np.stack([dsx, dsy]).astype(np.float32))
+        torch.cuda.synchronize(self._dev)
+        h = C.c_void_p()
+        dp = C.POINTER(C.c_double)
+        (ih0, iw0), (ih1, iw1) = planes[3].shape, planes[4].shape
+        self._ctx._check(self._ctx._lib.wass_vref_create(
+            self._ctx._h, shape[0], shape[1], planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
+            mats[0].ctypes.data_as(dp), mats[1].ctypes.data_as(dp), mats[2].ctypes.data_as(dp), mats[3].ctypes.data_as(dp),
+            planes[3].data_ptr(), int(ih0), int(iw0), planes[4].data_ptr(), int(ih1), int(iw1), kernels.ctypes.data, C.byref(h)))
+        self._h = h                                              # the library has copied everything it keeps
+
+    # ---- plumbing
+    def _to_dev(self, a, dtype):
+        import torch
+        if _is_device(a):
+            if a.device != self._dev:
+                raise ValueError(f"a tensor on {a.device}, the context is on {self._dev}")
+            return a.to(dtype).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(self._dev).to(dtype).contiguous()
+
+    def _plane(self, Z, shape, name):
+        """Z as a contiguous float32 device tensor of `shape`, finite; and whether the caller's was a device tensor"""
+        import torch
+        if tuple(int(v) for v in Z.shape) != tuple(shape):
+            raise ValueError(f"{name} of shape {tuple(Z.shape)}, expected {tuple(shape)}")
+        dev = _is_device(Z)
+        if not dev and not np.isfinite(np.asarray(Z)).all():
+            raise ValueError(f"{name} holds a value that is not finite")
+        d = self._to_dev(Z, torch.float32)
+        if dev and not bool(torch.isfinite(d).all()):
+            raise ValueError(f"{name} holds a value that is not finite")
+        torch.cuda.synchronize(self._dev)
+        return d, dev
+
+    def _new(self, *shape):
+        import torch
+        t = torch.empty(shape, dtype=torch.float32, device=self._dev)
+        torch.cuda.synchronize(self._dev)
+        return t
+
+    @staticmethod
+    def _back(t, dev):
+        return t if dev else t.cpu().numpy()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._ctx._lib.wass_vref_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- the reference's methods
+    def sample_images(self, Z):
+        """(I0_samp, I1_samp, cam0_p2, cam1_p2): the masked samples, Ny x Nx, and the pixel coordinates, (Ny * Nx) x 2 as (x, y)."""
+        import torch
+        d, dev = self._plane(Z, self.shape, "Z")
+        i0, i1, uv = self._new(*self.shape), self._new(*self.shape), self._new(4, *self.shape)
+        self._ctx._check(self._ctx._lib.wass_vref_sample(self._h, d.data_ptr(), i0.data_ptr(), i1.data_ptr(), uv.data_ptr()))
+        p0 = torch.stack([uv[0].reshape(-1), uv[1].reshape(-1)], dim=1)
+        p1 = torch.stack([uv[2].reshape(-1), uv[3].reshape(-1)], dim=1)
+        return tuple(self._back(t, dev) for t in (i0, i1, p0, p1))
+
+    def compute_Z_gradient(self, Z):
+        """(Z_dx, Z_dy): Z correlated with the two 7 x 7 derivative-of-Gaussian kernels (sigma 0.8), zero padding."""
+        d, dev = self._plane(Z, self.shape, "Z")
+        zdx, zdy = self._new(*self.shape), self._new(*self.shape)
+        self._ctx._check(self._ctx._lib.wass_vref_zgrad(self._h, d.data_ptr(), zdx.data_ptr(), zdy.data_ptr()))
+        return self._back(zdx, dev), self._back(zdy, dev)
+
+    def compute_loss(self, Z):
+        """(data_loss, smoothness_loss) as Python floats."""
+        d, _ = self._plane(Z, self.shape, "Z")
+        a, b = C.c_double(), C.c_double()
+        self._ctx._check(self._ctx._lib.wass_vref_loss(self._h, d.data_ptr(), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def energy_gradient(self, Zc, alpha=10.0, full=False):
+        """The gradient of data_loss + alpha * smoothness_loss of resize(Zc) with respect to the coarse field Zc; with full=True
+        also with respect to the full-resolution surface: (gC, gZ)."""
+        d, dev = self._plane(Zc, self.coarse_shape, "Zc")
+        gc = self._new(*self.coarse_shape)
+        gz = self._new(*self.shape) if full else None
+        self._ctx._check(self._ctx._lib.wass_vref_gradient(self._h, d.data_ptr(), float(alpha), gc.data_ptr(), gz.data_ptr() if full else None))
+        return (self._back(gc, dev), self._back(gz, dev)) if full else self._back(gc, dev)
+
+    def adjoint(self, Zdx, Zdy, gd, alpha=10.0):
+        """The backward half on given planes (wass_vref_adjoint): (gC, gZ) with gZ = gd + float32(2 alpha / N) * (Zdx and Zdy correlated
+        with the flipped kernels) and gC the adjoint of the resize applied to gZ."""
+        planes = [self._plane(a, self.shape, n) for a, n in ((Zdx, "Zdx"), (Zdy, "Zdy"), (gd, "gd"))]
+        dev = planes[0][1]
+        gc, gz = self._new(*self.coarse_shape), self._new(*self.shape)
+        self._ctx._check(self._ctx._lib.wass_vref_adjoint(self._h, planes[0][0].data_ptr(), planes[1][0].data_ptr(), planes[2][0].data_ptr(),
+                                                          float(alpha), gc.data_ptr(), gz.data_ptr()))
+        return self._back(gc, dev), self._back(gz, dev)
+
+    def optimize_coarse(self, Zc, iters, alpha=10.0, lr=1e-3, eps=1e-7, report_every=10, state: AdamState | None = None):
+        """`iters` Adam steps from the coarse field Zc: (Zc, state, Z) with Z = resize(Zc) * mask.  state: an AdamState to continue
+        from (what an earlier call returned); a continued run equals one longer run bit for bit.  The loss trace of this call is
+        kept in .losses: rows [steps done, data, smoothness, energy]."""
+        import torch
+        iters = int(iters)
+        if iters < 0:
+            raise ValueError("iters must not be negative")
+        d, dev = self._plane(Zc, self.coarse_shape, "Zc")
+        d = d.clone()                                            # the caller's tensor is not modified
+        if state is None:
+            m, v, step = torch.zeros_like(d), torch.zeros_like(d), 0
+        else:
+            m, v, step = self._plane(state.m, self.coarse_shape, "state.m")[0].clone(), self._plane(state.v, self.coarse_shape, "state.v")[0].clone(), int(state.step)
+        z = self._new(*self.shape)
+        torch.cuda.synchronize(self._dev)
+        every = int(report_every)
+        cap = 2 + ((iters + every - 1) // every if every > 0 else 0)
+        trace = np.zeros((cap, 4), np.float64)
+        n, st = C.c_int(0), C.c_int64(step)
+        self._ctx._check(self._ctx._lib.wass_vref_optimize(self._h, d.data_ptr(), m.data_ptr(), v.data_ptr(), C.byref(st), iters, float(alpha),
+                                                           float(lr), float(eps), every, trace.ctypes.data, cap, C.byref(n), z.data_ptr()))
+        self.losses = trace[:n.value].copy()
+        return self._back(d, dev), AdamState(self._back(m, dev), self._back(v, dev), int(st.value)), self._back(z, dev)
+
+    def optimize(self, Zinit, max_iters=400, alpha=10, lr=1e-3, report_every=10):
+        """The reference's optimize: Zinit (Ny x Nx) is down-sampled to (Ny // 2) x (Nx // 2) by cv.resize's INTER_LINEAR rule, moved by
+        max_iters Adam steps, and the refined full-resolution Z * mask is returned; the loss trace stays in .losses."""
+        if tuple(int(v) for v in Zinit.shape) != self.shape:
+            raise ValueError(f"Zinit of shape {tuple(Zinit.shape)}, expected {self.shape}")
+        dev = _is_device(Zinit)
+        host = Zinit.detach().cpu().numpy() if dev else np.asarray(Zinit)
+        if not np.isfinite(host).all():
+            raise ValueError("Zinit holds a value that is not finite")
+        zc = downsample_linear(host, *self.coarse_shape)
+        if dev:
+            import torch
+            zc = torch.from_numpy(zc).to(self._dev)
+        _, self.state, z = self.optimize_coarse(zc, max_iters, alpha=alpha, lr=lr, report_every=report_every)
+        return z
+
+
+def _scalar(v) -> float:
+    return float(np.ravel(np.asarray(v))[0])
+
+
+def refine_surface(Zi, mask, I0, I1, gridsetup, ctx: Context | None = None, **kw):
+    """What the commented block of the reference's grid() does with a gridded surface Zi (metres, z up, Ny x Nx): the refinement
+    runs on -Zi / CAM_BASELINE in the plane's frame with Rp2c = Rpl.T and Tp2c = -Rp2c @ Tpl, and the result comes back as
+    -Z * CAM_BASELINE with NaN where mask == 0.  gridsetup: the mapping setup_grid returns (Rpl, Tpl, P0cam, P1cam, XX, YY,
+    CAM_BASELINE).  Cells with mask == 0 are set to 0 before the refinement, so a NaN outside the mask is no obstacle.
+    kw: max_iters, alpha, lr, report_every of VariationalRefinement.optimize.  Returns a float32 host array."""
+    baseline = _scalar(gridsetup["CAM_BASELINE"])
+    Rp2c = np.asarray(gridsetup["Rpl"], np.float64).reshape(3, 3).T
+    Tp2c = -Rp2c @ np.asarray(gridsetup["Tpl"], np.float64).reshape(3, 1)
+    Zi = Zi.detach().cpu().numpy() if _is_device(Zi) else np.asarray(Zi)
+    mask = mask.detach().cpu().numpy() if _is_device(mask) else np.asarray(mask)
+    inside = mask != 0
+    zin = np.where(inside, -Zi.astype(np.float64) / baseline, 0.0).astype(np.float32)
+    with VariationalRefinement(I0, I1, Rp2c, Tp2c, gridsetup["P0cam"], gridsetup["P1cam"], gridsetup["XX"], gridsetup["YY"], baseline,
+                               inside.astype(np.float32), ctx=ctx) as vr:
+        z = vr.optimize(zin, **kw)
+    out = (-z.astype(np.float64) * baseline).astype(np.float32)
+    out[~inside] = np.nan
+    return out
