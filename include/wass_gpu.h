@@ -1289,6 +1289,39 @@ int wass_vref_adjoint(wass_vref* h, const float* d_Zdx, const float* d_Zdy, cons
 int wass_vref_optimize(wass_vref* h, float* d_Zc, float* d_m, float* d_v, int64_t* step, int iters, double alpha, double lr, double eps,
                        int report_every, double* trace, int trace_cap, int* n_trace, float* d_Zout);
 
+/* ---- the refinement of a sequence: several frames per launch (vref.hip; refinement.refine_sequence, gridding.grid_sequence) --------
+ * The kernels above take their frame from blockIdx.z: mask, pictures, Zc, m, v, the slopes, the gradients, the block partials and
+ * the trace rows are per frame; XX / b, YY / b, the cameras, the kernels, the axis tables and Adam's lr_t are shared.  Every value
+ * is the same sequence of float32 operations and every frame's fp64 partials are folded on their own in the single run's order, so
+ * frame i of a batch equals the single run of frame i bit for bit; the wass_vref_ entries above are a batch of one.
+ * A batch handle keeps the shared set-up and room for nb frames (batch_scratch_bytes: what create allocates; needs no GPU; the
+ * value for nb = 1 is wass_vref_scratch_bytes') and is loaded again and again, with 1 <= n <= nb frames each time; only the frames
+ * of the last load are run, read or reported.  It is not a handle for the single entries above, nor the other way round.
+ * load:      d_Zi [n][ny][nx] float32, the gridded surfaces in metres, z up, NaN outside; d_mask [n][ny][nx] float32 or null: a
+ *            node is inside where d_mask != 0, without d_mask where d_Zi is not NaN; d_I0 [n][ih0][iw0], d_I1 [n][ih1][iw1] float32.
+ *            On the device: zin = inside ? (float)(-(double)Zi / baseline) : 0, then Zc = cv.resize's INTER_LINEAR rule applied to
+ *            zin (per axis f = (float)((d + 0.5) * (in / out) - 0.5) from fp64, s = floor(f), f -= s, clamped like OpenCV's; a row
+ *            is S[s] * (1 - f) + S[s + 1] * f in float32, rows are combined by the same rule), m = v = 0, step = 0.  A value inside
+ *            a frame's mask or in a picture that is not finite refuses the whole load (the message names the first such frame)
+ *            and leaves nothing loaded.  A frame whose mask is all zero is no error: it stays at 0 and comes back all NaN.
+ * set_state / get_state: Zc, m, v as [n][ny / 2][nx / 2] and the step count, in and out; a run continued through them equals one
+ *            longer run bit for bit.
+ * optimize:  `iters` Adam steps of every loaded frame.  trace (host, may be null): [n][trace_cap][4], per frame the rows of
+ *            wass_vref_optimize; *n_trace: rows written per frame.  Made on the device, read once at the end.
+ * result:    d_out [n][ny][nx] = inside ? (float)(-(double)Z * baseline) : NaN with Z = resize(Zc) * mask; d_Z (may be null): Z.
+ * Null pointers, n outside 1 .. nb, nb < 1, iters < 0, dimensions outside create's, a call before a load: WASS_ERR_INVALID_ARG. */
+int wass_vref_batch_scratch_bytes(int nb, int ny, int nx, int ih0, int iw0, int ih1, int iw1, size_t* bytes);
+int wass_vref_batch_create(wass_ctx* ctx, int nb, int ny, int nx, const float* d_xb, const float* d_yb, const double Rp2c[9],
+                           const double Tp2c[3], const double P0cam[12], const double P1cam[12], int ih0, int iw0, int ih1, int iw1,
+                           const float* kernels, wass_vref** out);
+void wass_vref_batch_destroy(wass_vref* h);
+int wass_vref_batch_load(wass_vref* h, int n, const float* d_Zi, const float* d_mask, const float* d_I0, const float* d_I1, double baseline);
+int wass_vref_batch_set_state(wass_vref* h, const float* d_Zc, const float* d_m, const float* d_v, int64_t step);
+int wass_vref_batch_get_state(wass_vref* h, float* d_Zc, float* d_m, float* d_v, int64_t* step);
+int wass_vref_batch_optimize(wass_vref* h, int iters, double alpha, double lr, double eps, int report_every, double* trace, int trace_cap,
+                             int* n_trace);
+int wass_vref_batch_result(wass_vref* h, float* d_out, float* d_Z);
+
 #ifdef __cplusplus
 }
 #endif

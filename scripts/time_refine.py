@@ -8,10 +8,20 @@ the reference's TensorFlow loop, as scripts/time_grid_dct.py does for the DCT in
 Prints one JSON line: ms for the whole optimize (down-sampling, 400 steps, the loss trace, the result on the host), ms per
 iteration, kernel launches per iteration (three per step; one more per row of the loss trace, one forward pass
 after the last step and three checks of the input before the first) and the torch loop's figures.
+
+    python scripts/time_refine.py --batch 1,2,4,8,16 [--parent-lib OTHER/libwassgpu.so] [--reps 5]
+
+times the refinement of a sequence instead (one JSON line again): SequenceRefiner.refine (load, 400 steps, result; device tensors in
+and out) per batch size on distinct frames, ms per call and per frame, the median of --reps after a warm-up of every shape;
+refine_surface frame by frame (create, host down-sampling, destroy) against refine_sequence on the same host arrays; and, with
+--parent-lib, the single entry (optimize_coarse on device tensors) of this build and of that build of the library, alternated in
+fresh processes (WASS_GPU_LIB), with the run-to-run spread of the repeated single run.
 """
 import argparse
+import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -92,8 +102,95 @@ def torch_loop(a, Z0, iters, alpha=10.0, lr=1e-3):
     return zc.detach(), [float(v) for v in losses]
 
 
+def sequence_frames(n, ih, iw, count):
+    """`count` distinct frames on the rig: the set-up mapping, surfaces in metres (z up), uint8 pictures"""
+    args, Z0 = rig(n, ih, iw)
+    setup = {"Rpl": np.eye(3), "Tpl": -np.asarray(args["Tp2c"], float).reshape(3, 1), "P0cam": args["P0cam"], "P1cam": args["P1cam"],
+             "XX": args["XX"], "YY": args["YY"], "CAM_BASELINE": args["baseline"]}
+    yy, xx = np.mgrid[0:n, 0:n] / n
+    Zi = np.stack([(-0.1 * np.sin(9 * xx + 0.3 * f) * np.cos(7 * yy - 0.2 * f)).astype(np.float32) for f in range(count)])
+    I0 = np.stack([np.round(texture(ih, iw, 10 + 2 * f)).astype(np.uint8) for f in range(count)])
+    I1 = np.stack([np.round(texture(ih, iw, 11 + 2 * f)).astype(np.uint8) for f in range(count)])
+    return setup, Zi, I0, I1
+
+
+def single_loop(a):
+    """the single entry on device tensors, --reps times after a warm-up: what a child process of time_sequence prints"""
+    args, Z0 = rig(a.n, a.ih, a.iw)
+    with wass_amd.Context(0) as ctx, refinement.VariationalRefinement(ctx=ctx, **args) as vr:
+        d_zc = torch.as_tensor(refinement.downsample_linear(Z0, a.n // 2, a.n // 2), device="cuda")
+        vr.optimize_coarse(d_zc, a.iters)
+        ms = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            vr.optimize_coarse(d_zc, a.iters)
+            ms.append((time.perf_counter() - t0) * 1e3)
+    print(json.dumps({"ms": ms}))
+
+
+def time_sequence(a):
+    sizes = sorted({int(v) for v in a.batch.split(",")})
+    setup, Zi, I0, I1 = sequence_frames(a.n, a.ih, a.iw, max(max(sizes), 4))
+    res = {"n": a.n, "picture": [a.ih, a.iw], "iters": a.iters, "reps": a.reps, "batches": {}}
+    opts = refinement.RefineOptions(max_iters=a.iters)
+    lib = wass_amd._lib.load()
+    with wass_amd.Context(0) as ctx:
+        dev = torch.device("cuda", ctx.device_id)
+        d_Zi, d_I0, d_I1 = (torch.from_numpy(v).to(dev) for v in (Zi, I0, I1))
+        d_I0, d_I1 = d_I0.float(), d_I1.float()
+        for b in sizes:
+            nbytes = ctypes.c_size_t(0)
+            lib.wass_vref_batch_scratch_bytes(b, a.n, a.n, a.ih, a.iw, a.ih, a.iw, ctypes.byref(nbytes))
+            with refinement.SequenceRefiner(setup, ((a.ih, a.iw), (a.ih, a.iw)), b, ctx) as sr:
+                out = torch.empty((b, a.n, a.n), dtype=torch.float32, device=dev)
+                sr.refine(d_Zi[:b], d_I0[:b], d_I1[:b], refinement.RefineOptions(max_iters=3), out=out)          # warm-up of this shape
+                ms = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    sr.refine(d_Zi[:b], d_I0[:b], d_I1[:b], opts, out=out)
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                e = [float(sr.losses[b - 1][0][3]), float(sr.losses[b - 1][-1][3])]
+            med = float(np.median(ms))
+            res["batches"][str(b)] = {"ms_per_call": round(med, 3), "ms_per_frame": round(med / b, 3), "all": [round(t, 3) for t in ms],
+                                      "scratch_MiB": round(nbytes.value / 2 ** 20, 1), "energy_first_last_of_last_frame": e}
+        # what a user of a sequence sees: host arrays in, host arrays out, 4 frames
+        nf = 4
+        refinement.refine_surface(Zi[0], np.ones_like(Zi[0]), I0[0], I1[0], setup, ctx=ctx, max_iters=3)
+        refinement.refine_sequence(Zi[:nf], I0[:nf], I1[:nf], setup, options=refinement.RefineOptions(max_iters=3), ctx=ctx)
+        one, seq = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            for f in range(nf):
+                refinement.refine_surface(Zi[f], np.ones_like(Zi[f]), I0[f], I1[f], setup, ctx=ctx, max_iters=a.iters)
+            one.append((time.perf_counter() - t0) * 1e3 / nf)
+            t0 = time.perf_counter()
+            refinement.refine_sequence(Zi[:nf], I0[:nf], I1[:nf], setup, options=opts, ctx=ctx)
+            seq.append((time.perf_counter() - t0) * 1e3 / nf)
+        res["host_arrays_ms_per_frame"] = {"refine_surface": round(float(np.median(one)), 3), "refine_sequence": round(float(np.median(seq)), 3),
+                                           "refine_sequence_batch": opts.batch, "frames": nf}
+    # the single entry of this build and of another one, alternated in fresh processes
+    if a.parent_lib:
+        runs = {"this": [], "parent": []}
+        cmd = [sys.executable, os.path.abspath(__file__), "--single-child", "--n", str(a.n), "--iw", str(a.iw), "--ih", str(a.ih), "--iters",
+               str(a.iters), "--reps", str(a.reps)]
+        for _ in range(3):
+            for which in ("this", "parent"):
+                env = dict(os.environ)
+                env.pop("WASS_GPU_LIB", None)
+                if which == "parent":
+                    env["WASS_GPU_LIB"] = os.path.abspath(a.parent_lib)
+                line = subprocess.run(cmd, env=env, capture_output=True, text=True, check=True, timeout=300).stdout.strip().splitlines()[-1]
+                runs[which].append(round(float(np.median(json.loads(line)["ms"])), 3))
+        res["single_entry_ms"] = {k: {"medians_of_runs": v, "median": round(float(np.median(v)), 3), "spread": round(max(v) - min(v), 3)}
+                                  for k, v in runs.items()}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", help="comma-separated batch sizes: time the refinement of a sequence instead")
+    ap.add_argument("--parent-lib", help="another build of libwassgpu.so whose single entry is timed in alternation")
+    ap.add_argument("--single-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--iw", type=int, default=2456)
     ap.add_argument("--ih", type=int, default=2058)
@@ -101,6 +198,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
     a = ap.parse_args()
+    if a.single_child:
+        return single_loop(a)
+    if a.batch:
+        return time_sequence(a)
     args, Z0 = rig(a.n, a.ih, a.iw)
     res = {"n": a.n, "picture": [a.ih, a.iw], "iters": a.iters}
     with wass_amd.Context(0) as ctx, refinement.VariationalRefinement(ctx=ctx, **args) as vr:

@@ -325,6 +325,15 @@ SYMBOLS = {
     "wass_vref_adjoint": (_i, [_vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
     "wass_vref_optimize": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int64), _i, C.c_double, C.c_double, C.c_double, _i, _vp, _i,
                                 C.POINTER(_i), _vp]),
+    "wass_vref_batch_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz)]),
+    "wass_vref_batch_create": (_i, [_vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), _i, _i, _i, _i, _vp, C.POINTER(_vp)]),
+    "wass_vref_batch_destroy": (None, [_vp]),
+    "wass_vref_batch_load": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_double]),
+    "wass_vref_batch_set_state": (_i, [_vp, _vp, _vp, _vp, C.c_int64]),
+    "wass_vref_batch_get_state": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int64)]),
+    "wass_vref_batch_optimize": (_i, [_vp, _i, C.c_double, C.c_double, C.c_double, _i, _vp, _i, C.POINTER(_i)]),
+    "wass_vref_batch_result": (_i, [_vp, _vp, _vp]),
     "wass_planes_mean_accumulate": (None, [C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_planes_mean_finish": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     "wass_ctx_wait_for_stream": (_i, [_vp, _vp]),

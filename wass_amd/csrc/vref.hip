@@ -48,6 +48,17 @@
 //   k_vref_step      one coarse node per lane: the gather over gZ, then Adam in place  -> Zc, m, v
 // Every report_every iterations k_vref_forward also leaves fp64 block partials of the two sums and k_vref_loss folds them into a
 // row of the trace on the device; the trace is read once, after the last iteration.
+//
+// Batches: every kernel of the loop takes its frame from blockIdx.z (k_vref_loss: from its workgroup index) and offsets what belongs
+// to a frame -- mask, pictures, Zc, m, v, Zdx, Zdy, gd, gZ, the block partials, the trace rows -- by the frame's stride `fs`; XX / b,
+// YY / b, the cameras, the kernels, the axis tables and lr_t are shared (all frames of a batch are at the same Adam step).  Bounds are
+// tested on the frame's own (y, x) before the offset is added, so a halo or a gather never reaches the next frame's plane.  A value
+// is the same sequence of operations whatever the frame index and the partials of frame f are folded with frame f's only, in the
+// order of the single run: frame f of a batch IS the single run of frame f, bit for bit, and the single entry points are a batch of one.
+//   k_vref_ingest    per fine node: mask = caller's mask != 0, or !isnan(Zi); zin = mask ? (float)(-(double)Zi / baseline) : 0
+//   k_vref_down      per coarse node: cv.resize's INTER_LINEAR rule (refinement.downsample_linear) from host tables s, s + 1, f:
+//                    row = S[s] * (1 - f) + S[s + 1] * f in float32, the two rows combined by the same rule; m = v = 0
+//   k_vref_finish    per fine node: Z = resize(Zc) * mask, out = mask ? (float)(-(double)Z * baseline) : NaN
 #include "common.h"
 
 #include <math.h>
@@ -106,6 +117,7 @@ __device__ __forceinline__ VrefSample vref_bilinear(const float* __restrict__ I,
 }
 
 struct VrefFwd {
+    size_t fs;                 // the frame's stride in floats: frame blockIdx.z of every per-frame pointer below starts at blockIdx.z * fs
     const float* Z;            // full-resolution input (COARSE = false)
     const float* Zc;           // the variable (COARSE = true)
     int Ny, Nx, Wc;
@@ -124,6 +136,19 @@ __global__ void __launch_bounds__(VR_THREADS) k_vref_forward(VrefFwd a, VrefAxis
     __shared__ float zt[VR_LH][VR_LW];
     __shared__ double red[2][VR_THREADS];
     const int x0 = blockIdx.x * VR_TW, y0 = blockIdx.y * VR_TH;
+    {                                                   // this frame's planes: every per-frame pointer moves once, in scalar registers
+        const size_t fo = (size_t)blockIdx.z * a.fs;
+        if (COARSE) a.Zc += fo; else a.Z += fo;
+        a.mask += fo; a.I0 += fo; a.I1 += fo;
+        if (a.Zdx) a.Zdx += fo;
+        if (a.Zdy) a.Zdy += fo;
+        if (a.gd) a.gd += fo;
+        if (a.I0s) a.I0s += fo;
+        if (a.I1s) a.I1s += fo;
+        if (a.uv) a.uv += fo;
+        if (a.Zmasked) a.Zmasked += fo;
+        if (a.partial) a.partial += fo / 2;             // fs is even: a frame is a multiple of 256 bytes
+    }
     for (int i = threadIdx.x; i < VR_LH * VR_LW; i += VR_THREADS) {
         const int r = i / VR_LW, c = i - r * VR_LW, gy = y0 + r - VR_HALO, gx = x0 + c - VR_HALO;
         float z = 0.0f;
@@ -212,11 +237,13 @@ __global__ void __launch_bounds__(VR_THREADS) k_vref_forward(VrefFwd a, VrefAxis
     }
 }
 
-// one workgroup: the block partials folded in a fixed order into row [steps, data, smooth, energy] of the trace
-__global__ void __launch_bounds__(VR_THREADS) k_vref_loss(const double* __restrict__ partial, int nblocks, double n_nodes, double alpha,
-                                                          double steps, double* __restrict__ row)
+// one workgroup per frame: the frame's block partials folded in a fixed order into row [steps, data, smooth, energy] of its trace
+__global__ void __launch_bounds__(VR_THREADS) k_vref_loss(const double* __restrict__ partial, size_t fs, int nblocks, double n_nodes, double alpha,
+                                                          double steps, double* __restrict__ row, size_t row_stride)
 {
     __shared__ double red[2][VR_THREADS];
+    partial += (size_t)blockIdx.x * (fs / 2);
+    row += (size_t)blockIdx.x * row_stride;
     double sd = 0.0, ss = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += VR_THREADS) { sd += partial[2 * b]; ss += partial[2 * b + 1]; }
     red[0][threadIdx.x] = sd;
@@ -237,10 +264,12 @@ __global__ void __launch_bounds__(VR_THREADS) k_vref_loss(const double* __restri
 
 // gZ = gd + (sx + sy) * cS, the correlations with the flipped kernels (kf: already flipped by the host)
 __global__ void __launch_bounds__(VR_THREADS) k_vref_smooth(const float* __restrict__ Zdx, const float* __restrict__ Zdy, const float* __restrict__ gd,
-                                                            int Ny, int Nx, float cS, VrefKer kf, float* __restrict__ gZ)
+                                                            size_t fs, int Ny, int Nx, float cS, VrefKer kf, float* __restrict__ gZ)
 {
     __shared__ float dxt[VR_LH][VR_LW], dyt[VR_LH][VR_LW];
     const int x0 = blockIdx.x * VR_TW, y0 = blockIdx.y * VR_TH;
+    const size_t fo = (size_t)blockIdx.z * fs;
+    Zdx += fo; Zdy += fo; gd += fo; gZ += fo;
     for (int i = threadIdx.x; i < VR_LH * VR_LW; i += VR_THREADS) {
         const int r = i / VR_LW, c = i - r * VR_LW, gy = y0 + r - VR_HALO, gx = x0 + c - VR_HALO;
         const bool in = gy >= 0 && gy < Ny && gx >= 0 && gx < Nx;
@@ -271,9 +300,11 @@ struct VrefAdam {
 };
 // the adjoint of the resize as a gather, then (ADAM) the update in place
 template <bool ADAM>
-__global__ void __launch_bounds__(VR_THREADS) k_vref_step(const float* __restrict__ gZ, int Nx, int Hc, int Wc, VrefAxis ay, VrefAxis ax,
+__global__ void __launch_bounds__(VR_THREADS) k_vref_step(const float* __restrict__ gZ, size_t fs, int Nx, int Hc, int Wc, VrefAxis ay, VrefAxis ax,
                                                           float* __restrict__ gC, float* __restrict__ Zc, VrefAdam ad)
 {
+    const size_t fo = (size_t)blockIdx.z * fs;
+    gZ += fo;
     const int cx = blockIdx.x * 64 + (threadIdx.x & 63), cy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (cx >= Wc || cy >= Hc) return;
     const int ya = ay.r0[cy], yb = ay.r1[cy], xa = ax.r0[cx], xb = ax.r1[cx];
@@ -289,7 +320,7 @@ __global__ void __launch_bounds__(VR_THREADS) k_vref_step(const float* __restric
         }
         g = g + wy * row;
     }
-    const size_t i = (size_t)cy * Wc + cx;
+    const size_t i = fo + (size_t)cy * Wc + cx;
     if (gC) gC[i] = g;
     if (ADAM) {
         float m = ad.m[i], v = ad.v[i];
@@ -301,18 +332,85 @@ __global__ void __launch_bounds__(VR_THREADS) k_vref_step(const float* __restric
     }
 }
 
-__global__ void __launch_bounds__(256) k_vref_finite(const float* __restrict__ a, size_t n, int* __restrict__ bad)
+// flag = min(flag, index of the frame) over the values that are not finite; `per` values per frame
+__global__ void __launch_bounds__(256) k_vref_finite(const float* __restrict__ a, size_t n, size_t per, int* __restrict__ flag)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && !isfinite(a[i])) atomicOr(bad, 1);
+    if (i < n && !isfinite(a[i])) atomicMin(flag, (int)(i / per));
+}
+
+// `count` floats per frame from src (frame stride ss) to dst (frame stride ds); blockIdx.z: the frame
+__global__ void __launch_bounds__(256) k_vref_copy(float* __restrict__ dst, size_t ds, const float* __restrict__ src, size_t ss, size_t count)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < count) dst[(size_t)blockIdx.z * ds + i] = src[(size_t)blockIdx.z * ss + i];
+}
+
+// Zi [n][N] metres, z up, NaN outside; mask_in [n][N] or null -> the frame's mask (1 / 0) and zin in the plane's frame; a value inside
+// the mask that is not finite (after the division as well) leaves its frame's index in flag
+__global__ void __launch_bounds__(256) k_vref_ingest(const float* __restrict__ Zi, const float* __restrict__ mask_in, size_t N, double baseline,
+                                                     size_t fs, float* __restrict__ mask, float* __restrict__ zin, int* __restrict__ flag)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const size_t f = blockIdx.z;
+    const float z = Zi[f * N + i];
+    const bool in = mask_in ? mask_in[f * N + i] != 0.0f : !isnan(z);
+    float v = 0.0f;
+    if (in) {
+        v = (float)(-(double)z / baseline);
+        if (!isfinite(v)) atomicMin(flag, (int)f);
+    }
+    mask[f * fs + i] = in ? 1.0f : 0.0f;
+    zin[f * fs + i] = v;
+}
+
+// per-axis tables of cv.resize's INTER_LINEAR rule, device pointers, per coarse index
+struct VrefDown {
+    const int* s; const int* s1; const float* f;
+};
+
+__global__ void __launch_bounds__(VR_THREADS) k_vref_down(const float* __restrict__ zin, size_t fs, int Nx, int Hc, int Wc, VrefDown dy, VrefDown dx,
+                                                          float* __restrict__ Zc, float* __restrict__ m, float* __restrict__ v)
+{
+    const int cx = blockIdx.x * 64 + (threadIdx.x & 63), cy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (cx >= Wc || cy >= Hc) return;
+    const size_t fo = (size_t)blockIdx.z * fs;
+    const float* S0 = zin + fo + (size_t)dy.s[cy] * Nx;
+    const float* S1 = zin + fo + (size_t)dy.s1[cy] * Nx;
+    const int xa = dx.s[cx], xb = dx.s1[cx];
+    const float fx = dx.f[cx], fy = dy.f[cy], gx = 1.0f - fx, gy = 1.0f - fy;
+    const float r0 = S0[xa] * gx + S0[xb] * fx, r1 = S1[xa] * gx + S1[xb] * fx;
+    const size_t i = fo + (size_t)cy * Wc + cx;
+    Zc[i] = r0 * gy + r1 * fy;
+    m[i] = 0.0f;
+    v[i] = 0.0f;
+}
+
+// out [n][N] metres, NaN outside the mask; Zm [n][N] (may be null) = resize(Zc) * mask
+__global__ void __launch_bounds__(256) k_vref_finish(const float* __restrict__ Zc, const float* __restrict__ mask, size_t fs, int Ny, int Nx, int Wc,
+                                                     VrefAxis ay, VrefAxis ax, double baseline, float* __restrict__ out, float* __restrict__ Zm)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= Nx || y >= Ny) return;
+    const size_t fo = (size_t)blockIdx.z * fs, i = (size_t)y * Nx + x, o = (size_t)blockIdx.z * Ny * Nx + i;
+    const float mk = mask[fo + i];
+    const float z = vref_resize_at(Zc + fo, Wc, ay, ax, y, x) * mk;
+    if (Zm) Zm[o] = z;
+    out[o] = mk != 0.0f ? (float)(-(double)z * baseline) : __builtin_nanf("");
 }
 
 static inline size_t vr_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// One allocation: what every frame shares, then nb frames of `frame` bytes each.  The f_ offsets count from a frame's start.
 struct VrefLayout {
-    size_t N, Nc, off_x, off_y, off_mask, off_I0, off_I1, off_z, off_zdx, off_zdy, off_gd, off_gz, off_partial, off_flag, off_tab, total;
+    size_t N, Nc, off_x, off_y, off_flag, off_tab, shared;
+    size_t f_mask, f_zin, f_zdx, f_zdy, f_gd, f_gz, f_I0, f_I1, f_zc, f_m, f_v, f_partial, frame, total;
     int bx, by, nblocks;
 };
+
+constexpr int VR_MAX_BATCH = 4096;
+constexpr int VR_NO_FRAME = 0x7f7f7f7f;      // what hipMemset(0x7f) leaves in the flag
 
 static bool vref_dims_ok(int ny, int nx, int ih0, int iw0, int ih1, int iw1)
 {
@@ -320,7 +418,7 @@ static bool vref_dims_ok(int ny, int nx, int ih0, int iw0, int ih1, int iw1)
            ih1 <= 32768 && iw1 <= 32768;
 }
 
-static VrefLayout vref_layout(int ny, int nx, int ih0, int iw0, int ih1, int iw1)
+static VrefLayout vref_layout(int nb, int ny, int nx, int ih0, int iw0, int ih1, int iw1)
 {
     VrefLayout L;
     L.N = (size_t)ny * nx;
@@ -328,22 +426,29 @@ static VrefLayout vref_layout(int ny, int nx, int ih0, int iw0, int ih1, int iw1
     L.bx = (nx + VR_TW - 1) / VR_TW;
     L.by = (ny + VR_TH - 1) / VR_TH;
     L.nblocks = L.bx * L.by;
+    const size_t plane = vr_align(L.N * 4), coarse = vr_align(L.Nc * 4);
     size_t o = 0;
-    const size_t plane = vr_align(L.N * 4);
     L.off_x = o; o += plane;
     L.off_y = o; o += plane;
-    L.off_mask = o; o += plane;
-    L.off_I0 = o; o += vr_align((size_t)ih0 * iw0 * 4);
-    L.off_I1 = o; o += vr_align((size_t)ih1 * iw1 * 4);
-    L.off_z = o; o += plane;
-    L.off_zdx = o; o += plane;
-    L.off_zdy = o; o += plane;
-    L.off_gd = o; o += plane;
-    L.off_gz = o; o += plane;
-    L.off_partial = o; o += vr_align((size_t)L.nblocks * 16);
     L.off_flag = o; o += 256;
-    L.off_tab = o; o += vr_align((size_t)(ny + nx) * 12 + (size_t)(ny / 2 + nx / 2) * 8);
-    L.total = o;
+    // resize: lo, hi, t per fine index, r0, r1 per coarse index; down-sampling: s, s1, f per coarse index
+    L.off_tab = o; o += vr_align((size_t)(ny + nx) * 12 + (size_t)(ny / 2 + nx / 2) * 20);
+    L.shared = o;
+    o = 0;
+    L.f_mask = o; o += plane;
+    L.f_zin = o; o += plane;
+    L.f_zdx = o; o += plane;
+    L.f_zdy = o; o += plane;
+    L.f_gd = o; o += plane;
+    L.f_gz = o; o += plane;
+    L.f_I0 = o; o += vr_align((size_t)ih0 * iw0 * 4);
+    L.f_I1 = o; o += vr_align((size_t)ih1 * iw1 * 4);
+    L.f_zc = o; o += coarse;
+    L.f_m = o; o += coarse;
+    L.f_v = o; o += coarse;
+    L.f_partial = o; o += vr_align((size_t)L.nblocks * 16);
+    L.frame = o;
+    L.total = L.shared + (size_t)nb * L.frame;
     return L;
 }
 
@@ -373,21 +478,47 @@ static void vref_axis_tables(int in, int out, std::vector<int>& lo, std::vector<
     }
 }
 
+// cv.resize's INTER_LINEAR rule per axis (refinement.downsample_linear): f = (float)((d + 0.5) * (in / out) - 0.5) from fp64,
+// s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= in - 1: s = in - 1, f = 0; s1 = min(s + 1, in - 1)
+static void vref_down_tables(int in, int out, std::vector<int>& s, std::vector<int>& s1, std::vector<float>& f)
+{
+    s.resize(out); s1.resize(out); f.resize(out);
+    const double scale = (double)in / (double)out;
+    for (int d = 0; d < out; ++d) {
+        float fv = (float)(((double)d + 0.5) * scale - 0.5);
+        int sv = (int)floorf(fv);
+        fv = fv - (float)sv;
+        if (sv < 0) { sv = 0; fv = 0.0f; }
+        if (sv >= in - 1) { sv = in - 1; fv = 0.0f; }
+        s[d] = sv;
+        s1[d] = sv + 1 < in - 1 ? sv + 1 : in - 1;
+        f[d] = fv;
+    }
+}
+
 }  // namespace wass
 
 using namespace wass;
 
 struct wass_vref {
     wass_ctx* c = nullptr;
+    bool batch = false;          // made by wass_vref_batch_create: owns mask, pictures, Zc, m, v of nb frames
+    int nb = 1, n = 0;           // frames allocated, frames loaded
+    int64_t step = 0;            // Adam steps the loaded frames have taken (batch)
+    double baseline = 1.0;       // of the last load (batch)
     int ny = 0, nx = 0, hc = 0, wc = 0, ih0 = 0, iw0 = 0, ih1 = 0, iw1 = 0;
     VrefLayout L = {};
     char* mem = nullptr;
-    double* trace = nullptr;     // device rows of the loss trace, grown on demand
+    double* trace = nullptr;     // device rows of the loss trace [nb][trace_cap][4], grown on demand
     int trace_cap = 0;
     VrefCam cam = {};
     VrefKer ker = {}, kerf = {};
     VrefAxis ay = {}, ax = {};
-    float* p(size_t off) const { return (float*)(mem + off); }
+    VrefDown dy = {}, dx = {};
+    float* p(size_t off) const { return (float*)(mem + off); }                 // shared
+    float* fp(size_t off) const { return (float*)(mem + L.shared + off); }     // frame 0; frame f: + f * fs()
+    size_t fs() const { return L.frame / 4; }
+    int* flag() const { return (int*)(mem + L.off_flag); }
 };
 
 namespace {
@@ -396,37 +527,63 @@ VrefFwd vref_fwd_args(const wass_vref* h)
 {
     VrefFwd a;
     memset(&a, 0, sizeof a);
+    a.fs = h->fs();
     a.Ny = h->ny; a.Nx = h->nx; a.Wc = h->wc;
-    a.Xb = h->p(h->L.off_x); a.Yb = h->p(h->L.off_y); a.mask = h->p(h->L.off_mask);
-    a.I0 = h->p(h->L.off_I0); a.H0 = h->ih0; a.W0 = h->iw0;
-    a.I1 = h->p(h->L.off_I1); a.H1 = h->ih1; a.W1 = h->iw1;
+    a.Xb = h->p(h->L.off_x); a.Yb = h->p(h->L.off_y); a.mask = h->fp(h->L.f_mask);
+    a.I0 = h->fp(h->L.f_I0); a.H0 = h->ih0; a.W0 = h->iw0;
+    a.I1 = h->fp(h->L.f_I1); a.H1 = h->ih1; a.W1 = h->iw1;
     a.cD = (float)(2.0 / (255.0 * (double)h->L.N));
     return a;
 }
 
-void vref_launch_forward(const wass_vref* h, const VrefFwd& a, bool coarse, hipStream_t s)
+// n: the frames of the launch (grid z).  A pointer of the caller's (n = 1 only) needs no stride.
+void vref_launch_forward(const wass_vref* h, const VrefFwd& a, bool coarse, int n, hipStream_t s)
 {
-    const dim3 grid((unsigned)h->L.bx, (unsigned)h->L.by);
+    const dim3 grid((unsigned)h->L.bx, (unsigned)h->L.by, (unsigned)n);
     if (coarse) hipLaunchKernelGGL(k_vref_forward<true>, grid, dim3(VR_THREADS), 0, s, a, h->ay, h->ax, h->cam, h->ker);
     else hipLaunchKernelGGL(k_vref_forward<false>, grid, dim3(VR_THREADS), 0, s, a, h->ay, h->ax, h->cam, h->ker);
 }
 
-void vref_launch_loss(const wass_vref* h, double alpha, double steps, double* d_row, hipStream_t s)
+// row `row` of every frame's trace
+void vref_launch_loss(const wass_vref* h, double alpha, double steps, int row, int n, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_vref_loss, dim3(1), dim3(VR_THREADS), 0, s, (const double*)(h->mem + h->L.off_partial), h->L.nblocks, (double)h->L.N, alpha,
-                       steps, d_row);
+    hipLaunchKernelGGL(k_vref_loss, dim3((unsigned)n), dim3(VR_THREADS), 0, s, (const double*)h->fp(h->L.f_partial), h->fs(), h->L.nblocks,
+                       (double)h->L.N, alpha, steps, h->trace + 4 * (size_t)row, 4 * (size_t)h->trace_cap);
 }
 
 // gd, Zdx, Zdy of the handle -> gZ of the handle -> gC and / or the Adam step
-void vref_launch_backward(const wass_vref* h, double alpha, float* d_gC, float* d_Zc, const VrefAdam* ad, hipStream_t s)
+void vref_launch_backward(const wass_vref* h, double alpha, float* d_gC, float* d_Zc, const VrefAdam* ad, int n, hipStream_t s)
 {
     const float cS = (float)(2.0 * alpha / (double)h->L.N);
-    hipLaunchKernelGGL(k_vref_smooth, dim3((unsigned)h->L.bx, (unsigned)h->L.by), dim3(VR_THREADS), 0, s, (const float*)h->p(h->L.off_zdx),
-                       (const float*)h->p(h->L.off_zdy), (const float*)h->p(h->L.off_gd), h->ny, h->nx, cS, h->kerf, h->p(h->L.off_gz));
-    const dim3 grid((unsigned)((h->wc + 63) / 64), (unsigned)((h->hc + 3) / 4));
+    const VrefLayout& L = h->L;
+    hipLaunchKernelGGL(k_vref_smooth, dim3((unsigned)L.bx, (unsigned)L.by, (unsigned)n), dim3(VR_THREADS), 0, s, (const float*)h->fp(L.f_zdx),
+                       (const float*)h->fp(L.f_zdy), (const float*)h->fp(L.f_gd), h->fs(), h->ny, h->nx, cS, h->kerf, h->fp(L.f_gz));
+    const dim3 grid((unsigned)((h->wc + 63) / 64), (unsigned)((h->hc + 3) / 4), (unsigned)n);
     VrefAdam none = {};
-    if (ad) hipLaunchKernelGGL(k_vref_step<true>, grid, dim3(VR_THREADS), 0, s, (const float*)h->p(h->L.off_gz), h->nx, h->hc, h->wc, h->ay, h->ax, d_gC, d_Zc, *ad);
-    else hipLaunchKernelGGL(k_vref_step<false>, grid, dim3(VR_THREADS), 0, s, (const float*)h->p(h->L.off_gz), h->nx, h->hc, h->wc, h->ay, h->ax, d_gC, d_Zc, none);
+    if (ad) hipLaunchKernelGGL(k_vref_step<true>, grid, dim3(VR_THREADS), 0, s, (const float*)h->fp(L.f_gz), h->fs(), h->nx, h->hc, h->wc, h->ay, h->ax, d_gC, d_Zc, *ad);
+    else hipLaunchKernelGGL(k_vref_step<false>, grid, dim3(VR_THREADS), 0, s, (const float*)h->fp(L.f_gz), h->fs(), h->nx, h->hc, h->wc, h->ay, h->ax, d_gC, d_Zc, none);
+}
+
+int vref_flag_reset(wass_vref* h, hipStream_t s)
+{
+    WASS_HIP(h->c, hipMemsetAsync(h->flag(), 0x7f, 4, s));
+    return WASS_OK;
+}
+
+// the flag after everything enqueued so far: the first frame that left its index there, or -1.  synchronises
+int vref_flag_read(wass_vref* h, hipStream_t s, int* frame)
+{
+    int v = VR_NO_FRAME;
+    WASS_HIP(h->c, hipGetLastError());
+    WASS_HIP(h->c, hipMemcpyAsync(&v, h->flag(), 4, hipMemcpyDeviceToHost, s));
+    WASS_HIP(h->c, hipStreamSynchronize(s));
+    *frame = v == VR_NO_FRAME ? -1 : v;
+    return WASS_OK;
+}
+
+void vref_launch_finite(wass_vref* h, const float* a, size_t total, size_t per, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_vref_finite, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, total, per, h->flag());
 }
 
 // every one of the `count` planes of n floats finite?  synchronises
@@ -434,15 +591,11 @@ int vref_all_finite(wass_vref* h, const float* const* planes, int count, size_t 
 {
     wass_ctx* c = h->c;
     hipStream_t s = c->ts();
-    int* flag = (int*)(h->mem + h->L.off_flag);
-    WASS_HIP(c, hipMemsetAsync(flag, 0, 4, s));
-    for (int k = 0; k < count; ++k)
-        hipLaunchKernelGGL(k_vref_finite, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes[k], n, flag);
-    WASS_HIP(c, hipGetLastError());
-    int bad = 0;
-    WASS_HIP(c, hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
-    WASS_HIP(c, hipStreamSynchronize(s));
-    if (bad) return set_err(c, WASS_ERR_INVALID_ARG, "%s holds a value that is not finite", what);
+    int rc = vref_flag_reset(h, s), bad = -1;
+    if (rc) return rc;
+    for (int k = 0; k < count; ++k) vref_launch_finite(h, planes[k], n, n, s);
+    if ((rc = vref_flag_read(h, s, &bad))) return rc;
+    if (bad >= 0) return set_err(c, WASS_ERR_INVALID_ARG, "%s holds a value that is not finite", what);
     return WASS_OK;
 }
 
@@ -456,44 +609,73 @@ int vref_trace_rows(wass_vref* h, int rows)
         h->trace = nullptr;
         h->trace_cap = 0;
     }
-    if (hipMalloc((void**)&h->trace, (size_t)rows * 32) != hipSuccess) {
+    if (hipMalloc((void**)&h->trace, (size_t)h->nb * rows * 32) != hipSuccess) {
         h->trace = nullptr;
-        return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc of %d rows of the loss trace failed", rows);
+        return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc of %d x %d rows of the loss trace failed", h->nb, rows);
     }
     h->trace_cap = rows;
     return WASS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int wass_vref_scratch_bytes(int ny, int nx, int ih0, int iw0, int ih1, int iw1, size_t* bytes)
+void vref_copy_frames(float* dst, size_t ds, const float* src, size_t ss, size_t count, int n, hipStream_t s)
 {
-    if (!bytes || !vref_dims_ok(ny, nx, ih0, iw0, ih1, iw1)) return WASS_ERR_INVALID_ARG;
-    *bytes = vref_layout(ny, nx, ih0, iw0, ih1, iw1).total;
+    hipLaunchKernelGGL(k_vref_copy, dim3((unsigned)((count + 255) / 256), 1, (unsigned)n), dim3(256), 0, s, dst, ds, src, ss, count);
+}
+
+// The loop of both optimize entries: `iters` steps of n frames whose Zc, m, v start at the given pointers with the handle's frame
+// stride (the caller's own planes when n = 1), from Adam step `step`.  trace: host [n][trace_cap][4].  Synchronises.
+int vref_run(wass_vref* h, int n, float* d_Zc, float* d_m, float* d_v, int64_t step, int iters, double alpha, double lr, double eps,
+             int report_every, double* trace, int trace_cap, int* n_trace, float* d_Zout)
+{
+    wass_ctx* c = h->c;
+    // the rows of the trace: before the first step, after step ii (from 0) where ii % report_every == 0, after the last
+    const int every = report_every > 0 ? report_every : 0;
+    const int rows_max = 2 + (every ? (iters + every - 1) / every : 0);
+    const bool want = trace && trace_cap > 0;
+    int rc;
+    if (want && (rc = vref_trace_rows(h, rows_max))) return rc;
+    hipStream_t s = c->ts();
+    const VrefLayout& L = h->L;
+    VrefFwd base = vref_fwd_args(h);
+    base.Zc = d_Zc;
+    int rows = 0;
+    for (int it = 0; it < iters; ++it) {
+        VrefFwd a = base;
+        a.Zdx = h->fp(L.f_zdx); a.Zdy = h->fp(L.f_zdy); a.gd = h->fp(L.f_gd);
+        const bool report = want && rows < trace_cap && (it == 0 || (every && (it - 1) % every == 0));
+        if (report) a.partial = (double*)h->fp(L.f_partial);
+        vref_launch_forward(h, a, true, n, s);
+        if (report) vref_launch_loss(h, alpha, (double)it, rows++, n, s);
+        const double t = (double)(step + it + 1);
+        VrefAdam ad;
+        ad.m = d_m; ad.v = d_v;
+        ad.c1 = (float)(1.0 - VR_B1); ad.c2 = (float)(1.0 - VR_B2);
+        ad.lr_t = (float)(lr * sqrt(1.0 - pow(VR_B2, t)) / (1.0 - pow(VR_B1, t)));
+        ad.eps = (float)eps;
+        vref_launch_backward(h, alpha, nullptr, d_Zc, &ad, n, s);
+    }
+    const bool last_row = want && rows < trace_cap && (iters > 0 || rows == 0);
+    if (last_row || d_Zout) {
+        VrefFwd a = base;
+        a.Zmasked = d_Zout;
+        if (last_row) a.partial = (double*)h->fp(L.f_partial);
+        vref_launch_forward(h, a, true, n, s);
+        if (last_row) vref_launch_loss(h, alpha, (double)iters, rows++, n, s);
+    }
+    WASS_HIP(c, hipGetLastError());
+    if (rows)
+        for (int f = 0; f < n; ++f)
+            WASS_HIP(c, hipMemcpyAsync(trace + 4 * (size_t)f * trace_cap, h->trace + 4 * (size_t)f * h->trace_cap, (size_t)rows * 32,
+                                       hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipStreamSynchronize(s));
+    if (n_trace) *n_trace = rows;
     return WASS_OK;
 }
 
-void wass_vref_destroy(wass_vref* h)
+// the handle with everything the frames share: XX / b, YY / b, the cameras, the kernels, the axis tables.  Synchronises.
+int vref_new(wass_ctx* c, int nb, int ny, int nx, const float* d_xb, const float* d_yb, const double Rp2c[9], const double Tp2c[3],
+             const double P0cam[12], const double P1cam[12], int ih0, int iw0, int ih1, int iw1, const float* kernels, wass_vref** out)
 {
-    if (!h) return;
-    if (h->c) (void)hipSetDevice(h->c->device);
-    if (h->mem || h->trace) (void)hipDeviceSynchronize();
-    if (h->mem) (void)hipFree(h->mem);
-    if (h->trace) (void)hipFree(h->trace);
-    delete h;
-}
-
-int wass_vref_create(wass_ctx* c, int ny, int nx, const float* d_xb, const float* d_yb, const float* d_mask, const double Rp2c[9],
-                     const double Tp2c[3], const double P0cam[12], const double P1cam[12], const float* d_I0, int ih0, int iw0,
-                     const float* d_I1, int ih1, int iw1, const float* kernels, wass_vref** out)
-{
-    if (!c) return WASS_ERR_INVALID_ARG;
-    if (!out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
-    if (!d_xb || !d_yb || !d_mask || !Rp2c || !Tp2c || !P0cam || !P1cam || !d_I0 || !d_I1 || !kernels)
-        return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     if (ny < 2 || nx < 2 || ny > 32768 || nx > 32768) return set_err(c, WASS_ERR_INVALID_ARG, "grid of %d x %d: 2 .. 32768 nodes per axis", ny, nx);
     if (!vref_dims_ok(ny, nx, ih0, iw0, ih1, iw1))
         return set_err(c, WASS_ERR_INVALID_ARG, "pictures of %d x %d and %d x %d: 2 .. 32768 pixels per side", ih0, iw0, ih1, iw1);
@@ -505,9 +687,9 @@ int wass_vref_create(wass_ctx* c, int ny, int nx, const float* d_xb, const float
     WASS_HIP(c, hipSetDevice(c->device));
     wass_vref* h = new (std::nothrow) wass_vref;
     if (!h) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
-    h->c = c; h->ny = ny; h->nx = nx; h->hc = ny / 2; h->wc = nx / 2;
+    h->c = c; h->nb = nb; h->ny = ny; h->nx = nx; h->hc = ny / 2; h->wc = nx / 2;
     h->ih0 = ih0; h->iw0 = iw0; h->ih1 = ih1; h->iw1 = iw1;
-    h->L = vref_layout(ny, nx, ih0, iw0, ih1, iw1);
+    h->L = vref_layout(nb, ny, nx, ih0, iw0, ih1, iw1);
     const VrefLayout& L = h->L;
     hipError_t e = hipMalloc((void**)&h->mem, L.total);
     if (e != hipSuccess) {
@@ -527,42 +709,42 @@ int wass_vref_create(wass_ctx* c, int ny, int nx, const float* d_xb, const float
         h->ker.kx[i] = kernels[i]; h->ker.ky[i] = kernels[49 + i];
         h->kerf.kx[i] = kernels[48 - i]; h->kerf.ky[i] = kernels[49 + 48 - i];
     }
-    // the resize tables: per fine index lo, hi, t; per coarse index the range of fine indices
-    std::vector<int> lo[2], hi[2], r0[2], r1[2];
-    std::vector<float> t[2];
+    // the resize tables: per fine index lo, hi, t; per coarse index the range of fine indices; then the down-sampling's s, s1, f
+    std::vector<int> lo[2], hi[2], r0[2], r1[2], ds[2], ds1[2];
+    std::vector<float> t[2], df[2];
     vref_axis_tables(h->hc, ny, lo[0], hi[0], t[0], r0[0], r1[0]);
     vref_axis_tables(h->wc, nx, lo[1], hi[1], t[1], r0[1], r1[1]);
+    vref_down_tables(ny, h->hc, ds[0], ds1[0], df[0]);
+    vref_down_tables(nx, h->wc, ds[1], ds1[1], df[1]);
     hipStream_t s = c->ts();
     char* tab = h->mem + L.off_tab;
     bool ok = true;
+    auto put = [&](const void* src, size_t count) {
+        const void* at = tab;
+        ok = ok && hipMemcpyAsync(tab, src, count * 4, hipMemcpyHostToDevice, s) == hipSuccess;
+        tab += count * 4;
+        return at;
+    };
     VrefAxis* axes[2] = {&h->ay, &h->ax};
-    for (int k = 0; k < 2 && ok; ++k) {
+    VrefDown* downs[2] = {&h->dy, &h->dx};
+    for (int k = 0; k < 2; ++k) {
         const size_t nf = lo[k].size(), nc = r0[k].size();
         VrefAxis& A = *axes[k];
-        A.lo = (const int*)tab; ok = ok && hipMemcpyAsync(tab, lo[k].data(), nf * 4, hipMemcpyHostToDevice, s) == hipSuccess; tab += nf * 4;
-        A.hi = (const int*)tab; ok = ok && hipMemcpyAsync(tab, hi[k].data(), nf * 4, hipMemcpyHostToDevice, s) == hipSuccess; tab += nf * 4;
-        A.t = (const float*)tab; ok = ok && hipMemcpyAsync(tab, t[k].data(), nf * 4, hipMemcpyHostToDevice, s) == hipSuccess; tab += nf * 4;
-        A.r0 = (const int*)tab; ok = ok && hipMemcpyAsync(tab, r0[k].data(), nc * 4, hipMemcpyHostToDevice, s) == hipSuccess; tab += nc * 4;
-        A.r1 = (const int*)tab; ok = ok && hipMemcpyAsync(tab, r1[k].data(), nc * 4, hipMemcpyHostToDevice, s) == hipSuccess; tab += nc * 4;
+        A.lo = (const int*)put(lo[k].data(), nf);
+        A.hi = (const int*)put(hi[k].data(), nf);
+        A.t = (const float*)put(t[k].data(), nf);
+        A.r0 = (const int*)put(r0[k].data(), nc);
+        A.r1 = (const int*)put(r1[k].data(), nc);
+        VrefDown& D = *downs[k];
+        D.s = (const int*)put(ds[k].data(), nc);
+        D.s1 = (const int*)put(ds1[k].data(), nc);
+        D.f = (const float*)put(df[k].data(), nc);
     }
     const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
     ok = ok && hipMemcpyAsync(h->mem + L.off_x, d_xb, L.N * 4, dd, s) == hipSuccess;
     ok = ok && hipMemcpyAsync(h->mem + L.off_y, d_yb, L.N * 4, dd, s) == hipSuccess;
-    ok = ok && hipMemcpyAsync(h->mem + L.off_mask, d_mask, L.N * 4, dd, s) == hipSuccess;
-    ok = ok && hipMemcpyAsync(h->mem + L.off_I0, d_I0, (size_t)ih0 * iw0 * 4, dd, s) == hipSuccess;
-    ok = ok && hipMemcpyAsync(h->mem + L.off_I1, d_I1, (size_t)ih1 * iw1 * 4, dd, s) == hipSuccess;
     ok = ok && hipStreamSynchronize(s) == hipSuccess;                              // the host tables leave scope
     int rc = ok ? WASS_OK : set_err(c, WASS_ERR_DEVICE, "refinement set-up failed: %s", hipGetErrorString(hipGetLastError()));
-    if (!rc) {
-        const float* planes[3] = {h->p(L.off_x), h->p(L.off_y), h->p(L.off_mask)};
-        rc = vref_all_finite(h, planes, 3, L.N, "XX / b, YY / b or the mask");
-    }
-    if (!rc) {
-        const float* p0[1] = {h->p(L.off_I0)};
-        const float* p1[1] = {h->p(L.off_I1)};
-        rc = vref_all_finite(h, p0, 1, (size_t)ih0 * iw0, "picture 0");
-        if (!rc) rc = vref_all_finite(h, p1, 1, (size_t)ih1 * iw1, "picture 1");
-    }
     if (rc) {
         wass_vref_destroy(h);
         return rc;
@@ -571,9 +753,87 @@ int wass_vref_create(wass_ctx* c, int ny, int nx, const float* d_xb, const float
     return WASS_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int wass_vref_scratch_bytes(int ny, int nx, int ih0, int iw0, int ih1, int iw1, size_t* bytes)
+{
+    return wass_vref_batch_scratch_bytes(1, ny, nx, ih0, iw0, ih1, iw1, bytes);
+}
+
+int wass_vref_batch_scratch_bytes(int nb, int ny, int nx, int ih0, int iw0, int ih1, int iw1, size_t* bytes)
+{
+    if (!bytes || nb < 1 || nb > VR_MAX_BATCH || !vref_dims_ok(ny, nx, ih0, iw0, ih1, iw1)) return WASS_ERR_INVALID_ARG;
+    *bytes = vref_layout(nb, ny, nx, ih0, iw0, ih1, iw1).total;
+    return WASS_OK;
+}
+
+void wass_vref_destroy(wass_vref* h)
+{
+    if (!h) return;
+    if (h->c) (void)hipSetDevice(h->c->device);
+    if (h->mem || h->trace) (void)hipDeviceSynchronize();
+    if (h->mem) (void)hipFree(h->mem);
+    if (h->trace) (void)hipFree(h->trace);
+    delete h;
+}
+
+void wass_vref_batch_destroy(wass_vref* h) { wass_vref_destroy(h); }
+
+int wass_vref_create(wass_ctx* c, int ny, int nx, const float* d_xb, const float* d_yb, const float* d_mask, const double Rp2c[9],
+                     const double Tp2c[3], const double P0cam[12], const double P1cam[12], const float* d_I0, int ih0, int iw0,
+                     const float* d_I1, int ih1, int iw1, const float* kernels, wass_vref** out)
+{
+    if (!c) return WASS_ERR_INVALID_ARG;
+    if (!out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!d_xb || !d_yb || !d_mask || !Rp2c || !Tp2c || !P0cam || !P1cam || !d_I0 || !d_I1 || !kernels)
+        return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    wass_vref* h = nullptr;
+    int rc = vref_new(c, 1, ny, nx, d_xb, d_yb, Rp2c, Tp2c, P0cam, P1cam, ih0, iw0, ih1, iw1, kernels, &h);
+    if (rc) return rc;
+    const VrefLayout& L = h->L;
+    hipStream_t s = c->ts();
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    bool ok = hipMemcpyAsync(h->fp(L.f_mask), d_mask, L.N * 4, dd, s) == hipSuccess;
+    ok = ok && hipMemcpyAsync(h->fp(L.f_I0), d_I0, (size_t)ih0 * iw0 * 4, dd, s) == hipSuccess;
+    ok = ok && hipMemcpyAsync(h->fp(L.f_I1), d_I1, (size_t)ih1 * iw1 * 4, dd, s) == hipSuccess;
+    rc = ok ? WASS_OK : set_err(c, WASS_ERR_DEVICE, "refinement set-up failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc) {
+        const float* planes[3] = {h->p(L.off_x), h->p(L.off_y), h->fp(L.f_mask)};
+        rc = vref_all_finite(h, planes, 3, L.N, "XX / b, YY / b or the mask");
+    }
+    if (!rc) {
+        const float* p0[1] = {h->fp(L.f_I0)};
+        const float* p1[1] = {h->fp(L.f_I1)};
+        rc = vref_all_finite(h, p0, 1, (size_t)ih0 * iw0, "picture 0");
+        if (!rc) rc = vref_all_finite(h, p1, 1, (size_t)ih1 * iw1, "picture 1");
+    }
+    if (rc) {
+        wass_vref_destroy(h);
+        return rc;
+    }
+    h->n = 1;
+    *out = h;
+    return WASS_OK;
+}
+
+// the single entries take a handle of wass_vref_create only: a batch handle's frames are loaded, not passed in
+#define VREF_SINGLE(h)                                                                                             \
+    do {                                                                                                           \
+        if (!(h)) return WASS_ERR_INVALID_ARG;                                                                     \
+        if ((h)->batch) return set_err((h)->c, WASS_ERR_INVALID_ARG, "a handle of wass_vref_batch_create: use the wass_vref_batch_ entries"); \
+    } while (0)
+#define VREF_BATCH(h)                                                                                              \
+    do {                                                                                                           \
+        if (!(h)) return WASS_ERR_INVALID_ARG;                                                                     \
+        if (!(h)->batch) return set_err((h)->c, WASS_ERR_INVALID_ARG, "a handle of wass_vref_create: use the wass_vref_ entries"); \
+    } while (0)
+
 int wass_vref_sample(wass_vref* h, const float* d_Z, float* d_I0s, float* d_I1s, float* d_uv)
 {
-    if (!h) return WASS_ERR_INVALID_ARG;
+    VREF_SINGLE(h);
     wass_ctx* c = h->c;
     if (!d_Z || !d_I0s || !d_I1s || !d_uv) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
@@ -582,7 +842,7 @@ int wass_vref_sample(wass_vref* h, const float* d_Z, float* d_I0s, float* d_I1s,
     if (rc) return rc;
     VrefFwd a = vref_fwd_args(h);
     a.Z = d_Z; a.I0s = d_I0s; a.I1s = d_I1s; a.uv = d_uv;
-    vref_launch_forward(h, a, false, c->ts());
+    vref_launch_forward(h, a, false, 1, c->ts());
     WASS_HIP(c, hipGetLastError());
     WASS_HIP(c, hipStreamSynchronize(c->ts()));
     return WASS_OK;
@@ -590,7 +850,7 @@ int wass_vref_sample(wass_vref* h, const float* d_Z, float* d_I0s, float* d_I1s,
 
 int wass_vref_zgrad(wass_vref* h, const float* d_Z, float* d_Zdx, float* d_Zdy)
 {
-    if (!h) return WASS_ERR_INVALID_ARG;
+    VREF_SINGLE(h);
     wass_ctx* c = h->c;
     if (!d_Z || !d_Zdx || !d_Zdy) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
@@ -599,7 +859,7 @@ int wass_vref_zgrad(wass_vref* h, const float* d_Z, float* d_Zdx, float* d_Zdy)
     if (rc) return rc;
     VrefFwd a = vref_fwd_args(h);
     a.Z = d_Z; a.Zdx = d_Zdx; a.Zdy = d_Zdy;
-    vref_launch_forward(h, a, false, c->ts());
+    vref_launch_forward(h, a, false, 1, c->ts());
     WASS_HIP(c, hipGetLastError());
     WASS_HIP(c, hipStreamSynchronize(c->ts()));
     return WASS_OK;
@@ -607,7 +867,7 @@ int wass_vref_zgrad(wass_vref* h, const float* d_Z, float* d_Zdx, float* d_Zdy)
 
 int wass_vref_loss(wass_vref* h, const float* d_Z, double* data_loss, double* smoothness_loss)
 {
-    if (!h) return WASS_ERR_INVALID_ARG;
+    VREF_SINGLE(h);
     wass_ctx* c = h->c;
     if (!d_Z || !data_loss || !smoothness_loss) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
@@ -617,9 +877,9 @@ int wass_vref_loss(wass_vref* h, const float* d_Z, double* data_loss, double* sm
     if ((rc = vref_trace_rows(h, 1))) return rc;
     hipStream_t s = c->ts();
     VrefFwd a = vref_fwd_args(h);
-    a.Z = d_Z; a.partial = (double*)(h->mem + h->L.off_partial);
-    vref_launch_forward(h, a, false, s);
-    vref_launch_loss(h, 0.0, 0.0, h->trace, s);
+    a.Z = d_Z; a.partial = (double*)h->fp(h->L.f_partial);
+    vref_launch_forward(h, a, false, 1, s);
+    vref_launch_loss(h, 0.0, 0.0, 0, 1, s);
     WASS_HIP(c, hipGetLastError());
     double row[4];
     WASS_HIP(c, hipMemcpyAsync(row, h->trace, sizeof row, hipMemcpyDeviceToHost, s));
@@ -631,7 +891,7 @@ int wass_vref_loss(wass_vref* h, const float* d_Z, double* data_loss, double* sm
 
 int wass_vref_gradient(wass_vref* h, const float* d_Zc, double alpha, float* d_gC, float* d_gZ)
 {
-    if (!h) return WASS_ERR_INVALID_ARG;
+    VREF_SINGLE(h);
     wass_ctx* c = h->c;
     if (!d_Zc || !d_gC) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     if (!isfinite(alpha)) return set_err(c, WASS_ERR_INVALID_ARG, "alpha is not finite");
@@ -641,18 +901,18 @@ int wass_vref_gradient(wass_vref* h, const float* d_Zc, double alpha, float* d_g
     if (rc) return rc;
     hipStream_t s = c->ts();
     VrefFwd a = vref_fwd_args(h);
-    a.Zc = d_Zc; a.Zdx = h->p(h->L.off_zdx); a.Zdy = h->p(h->L.off_zdy); a.gd = h->p(h->L.off_gd);
-    vref_launch_forward(h, a, true, s);
-    vref_launch_backward(h, alpha, d_gC, nullptr, nullptr, s);
+    a.Zc = d_Zc; a.Zdx = h->fp(h->L.f_zdx); a.Zdy = h->fp(h->L.f_zdy); a.gd = h->fp(h->L.f_gd);
+    vref_launch_forward(h, a, true, 1, s);
+    vref_launch_backward(h, alpha, d_gC, nullptr, nullptr, 1, s);
     WASS_HIP(c, hipGetLastError());
-    if (d_gZ) WASS_HIP(c, hipMemcpyAsync(d_gZ, h->p(h->L.off_gz), h->L.N * 4, hipMemcpyDeviceToDevice, s));
+    if (d_gZ) WASS_HIP(c, hipMemcpyAsync(d_gZ, h->fp(h->L.f_gz), h->L.N * 4, hipMemcpyDeviceToDevice, s));
     WASS_HIP(c, hipStreamSynchronize(s));
     return WASS_OK;
 }
 
 int wass_vref_adjoint(wass_vref* h, const float* d_Zdx, const float* d_Zdy, const float* d_gd, double alpha, float* d_gC, float* d_gZ)
 {
-    if (!h) return WASS_ERR_INVALID_ARG;
+    VREF_SINGLE(h);
     wass_ctx* c = h->c;
     if (!d_Zdx || !d_Zdy || !d_gd || !d_gC) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     if (!isfinite(alpha)) return set_err(c, WASS_ERR_INVALID_ARG, "alpha is not finite");
@@ -662,12 +922,12 @@ int wass_vref_adjoint(wass_vref* h, const float* d_Zdx, const float* d_Zdy, cons
     if (rc) return rc;
     hipStream_t s = c->ts();
     const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
-    WASS_HIP(c, hipMemcpyAsync(h->p(h->L.off_zdx), d_Zdx, h->L.N * 4, dd, s));
-    WASS_HIP(c, hipMemcpyAsync(h->p(h->L.off_zdy), d_Zdy, h->L.N * 4, dd, s));
-    WASS_HIP(c, hipMemcpyAsync(h->p(h->L.off_gd), d_gd, h->L.N * 4, dd, s));
-    vref_launch_backward(h, alpha, d_gC, nullptr, nullptr, s);
+    WASS_HIP(c, hipMemcpyAsync(h->fp(h->L.f_zdx), d_Zdx, h->L.N * 4, dd, s));
+    WASS_HIP(c, hipMemcpyAsync(h->fp(h->L.f_zdy), d_Zdy, h->L.N * 4, dd, s));
+    WASS_HIP(c, hipMemcpyAsync(h->fp(h->L.f_gd), d_gd, h->L.N * 4, dd, s));
+    vref_launch_backward(h, alpha, d_gC, nullptr, nullptr, 1, s);
     WASS_HIP(c, hipGetLastError());
-    if (d_gZ) WASS_HIP(c, hipMemcpyAsync(d_gZ, h->p(h->L.off_gz), h->L.N * 4, dd, s));
+    if (d_gZ) WASS_HIP(c, hipMemcpyAsync(d_gZ, h->fp(h->L.f_gz), h->L.N * 4, dd, s));
     WASS_HIP(c, hipStreamSynchronize(s));
     return WASS_OK;
 }
@@ -675,7 +935,7 @@ int wass_vref_adjoint(wass_vref* h, const float* d_Zdx, const float* d_Zdy, cons
 int wass_vref_optimize(wass_vref* h, float* d_Zc, float* d_m, float* d_v, int64_t* step, int iters, double alpha, double lr, double eps,
                        int report_every, double* trace, int trace_cap, int* n_trace, float* d_Zout)
 {
-    if (!h) return WASS_ERR_INVALID_ARG;
+    VREF_SINGLE(h);
     wass_ctx* c = h->c;
     if (n_trace) *n_trace = 0;
     if (!d_Zc || !d_m || !d_v || !step) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
@@ -687,44 +947,144 @@ int wass_vref_optimize(wass_vref* h, float* d_Zc, float* d_m, float* d_v, int64_
     const float* planes[3] = {d_Zc, d_m, d_v};
     int rc = vref_all_finite(h, planes, 3, h->L.Nc, "Zc or the Adam state");
     if (rc) return rc;
-    // the rows of the trace: before the first step, after step ii (from 0) where ii % report_every == 0, after the last
-    const int every = report_every > 0 ? report_every : 0;
-    const int rows_max = 2 + (every ? (iters + every - 1) / every : 0);
-    const bool want = trace && trace_cap > 0;
-    if (want && (rc = vref_trace_rows(h, rows_max))) return rc;
+    if ((rc = vref_run(h, 1, d_Zc, d_m, d_v, *step, iters, alpha, lr, eps, report_every, trace, trace_cap, n_trace, d_Zout))) return rc;
+    *step += iters;
+    return WASS_OK;
+}
+
+// ---- batches
+int wass_vref_batch_create(wass_ctx* c, int nb, int ny, int nx, const float* d_xb, const float* d_yb, const double Rp2c[9], const double Tp2c[3],
+                           const double P0cam[12], const double P1cam[12], int ih0, int iw0, int ih1, int iw1, const float* kernels,
+                           wass_vref** out)
+{
+    if (!c) return WASS_ERR_INVALID_ARG;
+    if (!out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!d_xb || !d_yb || !Rp2c || !Tp2c || !P0cam || !P1cam || !kernels) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (nb < 1 || nb > VR_MAX_BATCH) return set_err(c, WASS_ERR_INVALID_ARG, "a batch of %d frames: 1 .. %d", nb, VR_MAX_BATCH);
+    wass_vref* h = nullptr;
+    int rc = vref_new(c, nb, ny, nx, d_xb, d_yb, Rp2c, Tp2c, P0cam, P1cam, ih0, iw0, ih1, iw1, kernels, &h);
+    if (rc) return rc;
+    const float* planes[2] = {h->p(h->L.off_x), h->p(h->L.off_y)};
+    if ((rc = vref_all_finite(h, planes, 2, h->L.N, "XX / b or YY / b"))) {
+        wass_vref_destroy(h);
+        return rc;
+    }
+    h->batch = true;
+    *out = h;
+    return WASS_OK;
+}
+
+int wass_vref_batch_load(wass_vref* h, int n, const float* d_Zi, const float* d_mask, const float* d_I0, const float* d_I1, double baseline)
+{
+    VREF_BATCH(h);
+    wass_ctx* c = h->c;
+    if (!d_Zi || !d_I0 || !d_I1) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (n < 1 || n > h->nb) return set_err(c, WASS_ERR_INVALID_ARG, "%d frames into a handle of %d", n, h->nb);
+    if (!isfinite(baseline) || baseline == 0.0) return set_err(c, WASS_ERR_INVALID_ARG, "the baseline must be finite and not 0");
+    WASS_HIP(c, hipSetDevice(c->device));
+    h->n = 0;                                            // nothing is loaded until this call has gone through
     hipStream_t s = c->ts();
     const VrefLayout& L = h->L;
-    VrefFwd base = vref_fwd_args(h);
-    base.Zc = d_Zc;
-    int rows = 0;
-    for (int it = 0; it < iters; ++it) {
-        VrefFwd a = base;
-        a.Zdx = h->p(L.off_zdx); a.Zdy = h->p(L.off_zdy); a.gd = h->p(L.off_gd);
-        const bool report = want && rows < trace_cap && (it == 0 || (every && (it - 1) % every == 0));
-        if (report) a.partial = (double*)(h->mem + L.off_partial);
-        vref_launch_forward(h, a, true, s);
-        if (report) vref_launch_loss(h, alpha, (double)it, h->trace + 4 * (size_t)rows++, s);
-        const double t = (double)(*step + it + 1);
-        VrefAdam ad;
-        ad.m = d_m; ad.v = d_v;
-        ad.c1 = (float)(1.0 - VR_B1); ad.c2 = (float)(1.0 - VR_B2);
-        ad.lr_t = (float)(lr * sqrt(1.0 - pow(VR_B2, t)) / (1.0 - pow(VR_B1, t)));
-        ad.eps = (float)eps;
-        vref_launch_backward(h, alpha, nullptr, d_Zc, &ad, s);
+    const size_t fs = h->fs(), n0 = (size_t)h->ih0 * h->iw0, n1 = (size_t)h->ih1 * h->iw1;
+    int rc, bad = -1;
+    const float* pics[2] = {d_I0, d_I1};
+    const size_t counts[2] = {n0, n1};
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = vref_flag_reset(h, s))) return rc;
+        vref_launch_finite(h, pics[k], (size_t)n * counts[k], counts[k], s);
+        if ((rc = vref_flag_read(h, s, &bad))) return rc;
+        if (bad >= 0) return set_err(c, WASS_ERR_INVALID_ARG, "picture %d of frame %d holds a value that is not finite", k, bad);
     }
-    const bool last_row = want && rows < trace_cap && (iters > 0 || rows == 0);
-    if (last_row || d_Zout) {
-        VrefFwd a = base;
-        a.Zmasked = d_Zout;
-        if (last_row) a.partial = (double*)(h->mem + L.off_partial);
-        vref_launch_forward(h, a, true, s);
-        if (last_row) vref_launch_loss(h, alpha, (double)iters, h->trace + 4 * (size_t)rows++, s);
-    }
+    if ((rc = vref_flag_reset(h, s))) return rc;
+    hipLaunchKernelGGL(k_vref_ingest, dim3((unsigned)((L.N + 255) / 256), 1, (unsigned)n), dim3(256), 0, s, d_Zi, d_mask, L.N, baseline, fs,
+                       h->fp(L.f_mask), h->fp(L.f_zin), h->flag());
+    vref_copy_frames(h->fp(L.f_I0), fs, d_I0, n0, n0, n, s);
+    vref_copy_frames(h->fp(L.f_I1), fs, d_I1, n1, n1, n, s);
+    hipLaunchKernelGGL(k_vref_down, dim3((unsigned)((h->wc + 63) / 64), (unsigned)((h->hc + 3) / 4), (unsigned)n), dim3(VR_THREADS), 0, s,
+                       (const float*)h->fp(L.f_zin), fs, h->nx, h->hc, h->wc, h->dy, h->dx, h->fp(L.f_zc), h->fp(L.f_m), h->fp(L.f_v));
+    if ((rc = vref_flag_read(h, s, &bad))) return rc;
+    if (bad >= 0) return set_err(c, WASS_ERR_INVALID_ARG, "frame %d holds a value inside its mask that is not finite", bad);
+    h->n = n;
+    h->step = 0;
+    h->baseline = baseline;
+    return WASS_OK;
+}
+
+int wass_vref_batch_set_state(wass_vref* h, const float* d_Zc, const float* d_m, const float* d_v, int64_t step)
+{
+    VREF_BATCH(h);
+    wass_ctx* c = h->c;
+    if (h->n < 1) return set_err(c, WASS_ERR_INVALID_ARG, "no frames are loaded");
+    if (!d_Zc || !d_m || !d_v) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (step < 0) return set_err(c, WASS_ERR_INVALID_ARG, "the Adam state's step count is negative");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    const VrefLayout& L = h->L;
+    int rc = vref_flag_reset(h, s), bad = -1;
+    if (rc) return rc;
+    const float* src[3] = {d_Zc, d_m, d_v};
+    for (int k = 0; k < 3; ++k) vref_launch_finite(h, src[k], (size_t)h->n * L.Nc, L.Nc, s);
+    if ((rc = vref_flag_read(h, s, &bad))) return rc;
+    if (bad >= 0) return set_err(c, WASS_ERR_INVALID_ARG, "Zc or the Adam state of frame %d holds a value that is not finite", bad);
+    const size_t dst[3] = {L.f_zc, L.f_m, L.f_v};
+    for (int k = 0; k < 3; ++k) vref_copy_frames(h->fp(dst[k]), h->fs(), src[k], L.Nc, L.Nc, h->n, s);
     WASS_HIP(c, hipGetLastError());
-    if (rows) WASS_HIP(c, hipMemcpyAsync(trace, h->trace, (size_t)rows * 32, hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipStreamSynchronize(s));
-    *step += iters;
-    if (n_trace) *n_trace = rows;
+    h->step = step;
+    return WASS_OK;
+}
+
+int wass_vref_batch_get_state(wass_vref* h, float* d_Zc, float* d_m, float* d_v, int64_t* step)
+{
+    VREF_BATCH(h);
+    wass_ctx* c = h->c;
+    if (h->n < 1) return set_err(c, WASS_ERR_INVALID_ARG, "no frames are loaded");
+    if (!d_Zc || !d_m || !d_v || !step) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    const VrefLayout& L = h->L;
+    float* dst[3] = {d_Zc, d_m, d_v};
+    const size_t src[3] = {L.f_zc, L.f_m, L.f_v};
+    for (int k = 0; k < 3; ++k) vref_copy_frames(dst[k], L.Nc, h->fp(src[k]), h->fs(), L.Nc, h->n, s);
+    WASS_HIP(c, hipGetLastError());
+    WASS_HIP(c, hipStreamSynchronize(s));
+    *step = h->step;
+    return WASS_OK;
+}
+
+int wass_vref_batch_optimize(wass_vref* h, int iters, double alpha, double lr, double eps, int report_every, double* trace, int trace_cap,
+                             int* n_trace)
+{
+    VREF_BATCH(h);
+    wass_ctx* c = h->c;
+    if (n_trace) *n_trace = 0;
+    if (h->n < 1) return set_err(c, WASS_ERR_INVALID_ARG, "no frames are loaded");
+    if (iters < 0) return set_err(c, WASS_ERR_INVALID_ARG, "iters = %d: not negative", iters);
+    if (!isfinite(alpha) || !isfinite(lr) || !isfinite(eps)) return set_err(c, WASS_ERR_INVALID_ARG, "alpha, lr or eps is not finite");
+    if (trace_cap < 0 || (trace_cap > 0 && !trace) || (trace && !n_trace)) return set_err(c, WASS_ERR_INVALID_ARG, "bad trace arguments");
+    WASS_HIP(c, hipSetDevice(c->device));
+    const VrefLayout& L = h->L;
+    int rc = vref_run(h, h->n, h->fp(L.f_zc), h->fp(L.f_m), h->fp(L.f_v), h->step, iters, alpha, lr, eps, report_every, trace, trace_cap, n_trace,
+                      nullptr);
+    if (rc) return rc;
+    h->step += iters;
+    return WASS_OK;
+}
+
+int wass_vref_batch_result(wass_vref* h, float* d_out, float* d_Z)
+{
+    VREF_BATCH(h);
+    wass_ctx* c = h->c;
+    if (h->n < 1) return set_err(c, WASS_ERR_INVALID_ARG, "no frames are loaded");
+    if (!d_out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    const VrefLayout& L = h->L;
+    hipLaunchKernelGGL(k_vref_finish, dim3((unsigned)((h->nx + 63) / 64), (unsigned)((h->ny + 3) / 4), (unsigned)h->n), dim3(256), 0, s,
+                       (const float*)h->fp(L.f_zc), (const float*)h->fp(L.f_mask), h->fs(), h->ny, h->nx, h->wc, h->ay, h->ax, h->baseline, d_out, d_Z);
+    WASS_HIP(c, hipGetLastError());
+    WASS_HIP(c, hipStreamSynchronize(s));
     return WASS_OK;
 }
 

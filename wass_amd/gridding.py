@@ -10,6 +10,8 @@ uniform [0, 1) draw, not torch.rand's stream; a rectangular grid is solved (the 
 grid_sequence(wass_frames, gridsetup, ...) is the tool's `--action grid` for `--ia DCT` (wassgridsurface.py:235-591) without the
 file output: every frame's mesh_cam.xyzC binned, solved (several frames per set of launches), masked, median filtered (mf),
 turned into the millimetre cube, with the sequence's zmin / zmax / zmean, the per-point mean and the force_zero_mean pass.
+With refine=RefineOptions(...) every frame's surface is also refined against its two pictures (wass_amd.refinement), where the
+reference's grid() has the call commented out: after the filter, before the statistics.
 load_camera_mesh(path) is the reference's mesh_cam.xyzC reader (wass_utils.py:22-35).
 
 setup_grid(wdir, meanplane, baseline, ...) is the tool's `--action setup` (wassgridsurface.py:57-231): the dict of its config.mat
@@ -95,6 +97,7 @@ class GridSequenceResult:
     frame_mean: np.ndarray
     frame_min: np.ndarray
     frame_max: np.ndarray
+    refine_losses: list | None = None   # with refine: per frame the first and the last row [steps, data, smoothness, energy]
 
 
 def _scalar(v) -> float:
@@ -102,14 +105,18 @@ def _scalar(v) -> float:
 
 
 def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_options=None, force_zero_mean: bool = False,
-                  batch: int = 8, cell: str = "median", ctx: Context | None = None, out=None) -> GridSequenceResult:
+                  batch: int = 8, cell: str = "median", ctx: Context | None = None, out=None, refine=None) -> GridSequenceResult:
     """wassgridsurface --action grid with --ia DCT on the GPU.  wass_frames: the NNNNNN_wd directories in sequence order (each
     holds mesh_cam.xyzC); gridsetup: a mapping with the reference's config.mat keys (Rpl, Tpl, CAM_BASELINE, xmin, xmax, ymin,
     ymax, XX or Nx and Ny, fps) or the path of that file; mf: 0, 3 or 5 (--mf); user_mask: height x width, cells where it is 0
     become NaN; alg_options: the DCT options by the reference's names; batch: frames per DCT solve -- 8 by default: in the
     measurement of DESIGN.md ("The DCT interpolator of row f3") the time per frame stops falling there; cell: "median" or
     "mean", the statistic of a grid cell (grid.hip; the reference's random sub-sampling is not reproduced); out: a
-    count x height x width float32 array or np.memmap for the cube (default: a new array)."""
+    count x height x width float32 array or np.memmap for the cube (default: a new array); refine: None, or a
+    wass_amd.refinement.RefineOptions: every frame's surface is refined against undistorted/00000000.png and 00000001.png of its
+    directory (refinement.SequenceRefiner, refine.batch frames per set of launches) after the solve, the user mask and the
+    filter, so the cube and every statistic see the refined surface; gridsetup then needs P0cam, P1cam, XX, YY as well, which
+    setup_grid writes.  The reference's alpha = 10 holds the surface to 0 along the grid's border (RefineOptions has the pointer)."""
     import torch
     if isinstance(gridsetup, (str, os.PathLike)):
         import scipy.io
@@ -131,6 +138,9 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
         out = np.empty((count, H, W), np.float32)
     elif out.shape != (count, H, W) or out.dtype != np.float32:
         raise ValueError(f"out: a float32 array of shape {(count, H, W)} expected")
+    pictures = None
+    if refine is not None:
+        pictures = _refine_inputs(frames, gridsetup, H, W)       # raises before anything touches the device
     if ctx is None:
         ctx = Context(0)
     dev = torch.device("cuda", ctx.device_id)
@@ -143,11 +153,18 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
     torch.cuda.synchronize(dev)                                  # from here on the buffers are used on the context's stream
     seq = GridSequence(ctx, W, H)
     infos, empty = [], []
+    refiner, traces = None, None
     try:
+        if refine is not None:
+            from .refinement import SequenceRefiner
+            rb = max(1, min(int(refine.batch), nb_max))
+            refiner, traces = SequenceRefiner(gridsetup, pictures, rb, ctx), []
+            d_ref = torch.empty_like(d_cells)
         with ThreadPoolExecutor(max_workers=min(nb_max, 8)) as pool:
             for i0 in range(0, count, batch):
                 paths = frames[i0:i0 + batch]
                 nb = len(paths)
+                views = pool.map(_load_pictures, paths) if refiner is not None else None      # decoded beside the meshes and the solve
                 clouds = list(pool.map(lambda d: load_camera_mesh(os.path.join(d, "mesh_cam.xyzC")), paths))
                 meshes = []
                 for k, pts in enumerate(clouds):
@@ -160,6 +177,14 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
                 if mf:
                     ctx.grid_median_dev(d_grid[:nb], d_filt[:nb], mf, d_mask)
                     d_zi = d_filt
+                if refiner is not None:
+                    views = list(views)
+                    for k0 in range(0, nb, refiner.batch):
+                        k = slice(k0, min(nb, k0 + refiner.batch))
+                        refiner.refine(d_zi[k], np.stack([v[0] for v in views[k]]), np.stack([v[1] for v in views[k]]), refine,
+                                       out=d_ref[k], first_frame=i0 + k0)
+                        traces += [[t[0].tolist(), t[-1].tolist()] for t in refiner.losses]
+                    d_zi = d_ref
                 seq.push_dev(d_zi[:nb], d_mm[:nb])
                 out[i0:i0 + nb] = d_mm[:nb].cpu().numpy()
                 infos += info
@@ -175,11 +200,54 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
                 out[i0:i0 + nb] = d_mm[:nb].cpu().numpy()
     finally:
         seq.close()
+        if refiner is not None:
+            refiner.close()
     idx = np.arange(count, dtype=np.float64)
     workdir = np.array([int(os.path.basename(os.path.normpath(f))[:-3]) for f in frames], np.int64)
     return GridSequenceResult(Z=out, time=idx / fps if fps > 0 else np.zeros(count), workdir=workdir, zmin=st["zmin"], zmax=st["zmax"],
                               zmean=st["zmean"], mean_perpoint_mm=st["mean_perpoint_mm"], dct_info=infos, empty_frames=empty,
-                              frame_mean=st["frame_mean"], frame_min=st["frame_min"], frame_max=st["frame_max"])
+                              frame_mean=st["frame_mean"], frame_min=st["frame_min"], frame_max=st["frame_max"], refine_losses=traces)
+
+
+REFINE_KEYS = ("Rpl", "Tpl", "CAM_BASELINE", "P0cam", "P1cam", "XX", "YY")
+REFINE_PICTURES = ("00000000.png", "00000001.png")
+
+
+def _load_pictures(framedir):
+    """the two undistorted pictures of a frame directory as uint8 grey"""
+    from PIL import Image
+    out = []
+    for name in REFINE_PICTURES:
+        with Image.open(os.path.join(framedir, "undistorted", name)) as im:
+            out.append(np.asarray(im.convert("L"), np.uint8))
+    return out
+
+
+def _refine_inputs(frames, gridsetup, H, W):
+    """What grid_sequence(refine=...) needs beyond the meshes, checked without a device: the keys of gridsetup (ValueError naming
+    the missing ones), both pictures of every frame (FileNotFoundError naming the file) and one size per camera over the
+    sequence (ValueError naming the first frame that differs).  Returns ((ih0, iw0), (ih1, iw1)); only the headers are read."""
+    from PIL import Image
+    missing = [k for k in REFINE_KEYS if k not in gridsetup]
+    if missing:
+        raise ValueError("refine: gridsetup lacks " + ", ".join(missing) + " (setup_grid writes them)")
+    for k in ("XX", "YY"):
+        if tuple(np.asarray(gridsetup[k]).shape) != (H, W):
+            raise ValueError(f"refine: {k} of shape {tuple(np.asarray(gridsetup[k]).shape)}, the grid is {(H, W)}")
+    sizes = [None, None]
+    for d in frames:
+        for cam, name in enumerate(REFINE_PICTURES):
+            path = os.path.join(d, "undistorted", name)
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"refine: {path} is missing")
+            with Image.open(path) as im:
+                size = (im.size[1], im.size[0])
+            if sizes[cam] is None:
+                sizes[cam] = size
+            elif size != sizes[cam]:
+                raise ValueError(f"refine: {path} of frame {d} is {size[0]} x {size[1]}, the pictures of camera {cam} before it are "
+                                 f"{sizes[cam][0]} x {sizes[cam][1]}")
+    return tuple(sizes)
 
 
 # ---------------------------------------------------------------------------------------------------------------- grid set-up

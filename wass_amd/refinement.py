@@ -16,6 +16,11 @@ tf.image.resize and tfa's sampler are restated from their published definitions,
 refine_surface(Zi, mask, I0, I1, gridsetup) is what the commented block of the reference's grid() amounts to
 (wassgridsurface.py:382-435).  Pictures may be uint8 or float32; every array may be a host array or a device tensor, and a
 result comes back on the side its Z came from.
+
+refine_sequence(Zi, I0, I1, gridsetup) is refine_surface for the n frames of a sequence, several frames per kernel launch: the
+library's kernels take their frame from blockIdx.z, the set-up the frames share is copied once, and the -Zi / baseline, the
+down-sampling and the -Z * baseline run on the device.  Frame i of its result equals refine_surface of frame i bit for bit.
+SequenceRefiner is the handle behind it (device tensors in and out), RefineOptions what grid_sequence(refine=...) takes.
 """
 from __future__ import annotations
 
@@ -281,3 +286,230 @@ def refine_surface(Zi, mask, I0, I1, gridsetup, ctx: Context | None = None, **kw
     out = (-z.astype(np.float64) * baseline).astype(np.float32)
     out[~inside] = np.nan
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- a sequence
+@dataclasses.dataclass
+class RefineOptions:
+    """The refinement of every frame of a sequence.  max_iters, alpha, lr: the reference's defaults; Adam runs max_iters steps for
+    every frame.  With the reference's alpha = 10 and its zero-padded smoothness term a constant offset of the surface costs energy
+    along the border of the grid ("Variational refinement", "What the tests found out about the model"): that holds
+    for every frame of a sequence.  batch: frames per set of launches -- 4 by default: DESIGN.md, "Variational refinement",
+    "Batches", has the measurement: the time per frame stops falling at 4."""
+    max_iters: int = 400
+    alpha: float = 10.0
+    lr: float = 1e-3
+    report_every: int = 10
+    batch: int = 4
+
+
+def _plane_to_camera(gridsetup):
+    baseline = _scalar(gridsetup["CAM_BASELINE"])
+    if not np.isfinite(baseline) or baseline == 0:
+        raise ValueError("CAM_BASELINE must be finite and not 0")
+    Rp2c = np.asarray(gridsetup["Rpl"], np.float64).reshape(3, 3).T
+    Tp2c = -Rp2c @ np.asarray(gridsetup["Tpl"], np.float64).reshape(3, 1)
+    return baseline, Rp2c, Tp2c
+
+
+class SequenceRefiner:
+    """The handle of a sequence's refinement: XX / b, YY / b, the cameras, the kernels and the axis tables are copied to the device
+    once, with room for `batch` frames.  gridsetup: setup_grid's mapping (Rpl, Tpl, P0cam, P1cam, XX, YY, CAM_BASELINE);
+    image_shapes: ((ih0, iw0), (ih1, iw1)).  refine() may be called any number of times, with 1 .. batch frames each."""
+
+    def __init__(self, gridsetup, image_shapes, batch: int = 4, ctx: Context | None = None):
+        import torch
+        self.baseline, Rp2c, Tp2c = _plane_to_camera(gridsetup)
+        XX, YY = gridsetup["XX"], gridsetup["YY"]
+        self.shape = tuple(int(v) for v in XX.shape)
+        if len(self.shape) != 2 or tuple(YY.shape) != self.shape or min(self.shape) < 2:
+            raise ValueError(f"XX and YY must be one Ny x Nx shape of at least 2 x 2, got {tuple(XX.shape)}, {tuple(YY.shape)}")
+        self.coarse_shape = (self.shape[0] // 2, self.shape[1] // 2)
+        self.image_shapes = tuple((int(h), int(w)) for h, w in image_shapes)
+        if len(self.image_shapes) != 2 or min(min(s) for s in self.image_shapes) < 2:
+            raise ValueError(f"image_shapes {image_shapes}: two pictures of at least 2 x 2 pixels")
+        self.batch = int(batch)
+        if self.batch < 1:
+            raise ValueError("batch must be at least 1")
+        mats = []
+        for name, m, size in (("Rpl", Rp2c, 9), ("Tpl", Tp2c, 3), ("P0cam", gridsetup["P0cam"], 12), ("P1cam", gridsetup["P1cam"], 12)):
+            a = np.ascontiguousarray(np.asarray(m, np.float64))
+            if a.size != size or not np.isfinite(a).all():
+                raise ValueError(f"{name}: {size} finite values expected")
+            mats.append(a.reshape(-1))
+        self.losses = []                                         # per frame of the last refine(): rows [steps, data, smoothness, energy]
+        self._h = None
+        self._ctx = ctx if ctx is not None else Context(0)
+        self._dev = torch.device("cuda", self._ctx.device_id)
+        xb = (self._to_dev(XX, torch.float64) / self.baseline).to(torch.float32).contiguous()     # fp64 quotients, then float32
+        yb = (self._to_dev(YY, torch.float64) / self.baseline).to(torch.float32).contiguous()
+        dsx, dsy = derivative_of_gaussian_win(7, sigma=0.8)
+        kernels = np.ascontiguousarray(np.stack([dsx, dsy]).astype(np.float32))
+        torch.cuda.synchronize(self._dev)
+        h = C.c_void_p()
+        dp = C.POINTER(C.c_double)
+        (ih0, iw0), (ih1, iw1) = self.image_shapes
+        self._ctx._check(self._ctx._lib.wass_vref_batch_create(
+            self._ctx._h, self.batch, self.shape[0], self.shape[1], xb.data_ptr(), yb.data_ptr(), mats[0].ctypes.data_as(dp),
+            mats[1].ctypes.data_as(dp), mats[2].ctypes.data_as(dp), mats[3].ctypes.data_as(dp), ih0, iw0, ih1, iw1, kernels.ctypes.data, C.byref(h)))
+        self._h = h
+        self._n = 0
+
+    def _to_dev(self, a, dtype):
+        import torch
+        if _is_device(a):
+            if a.device != self._dev:
+                raise ValueError(f"a tensor on {a.device}, the context is on {self._dev}")
+            return a.to(dtype).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(self._dev).to(dtype).contiguous()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._ctx._lib.wass_vref_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _call(self, rc, first_frame=0):
+        """a refusal that names a frame becomes a ValueError with the frame's index in the caller's sequence"""
+        import re
+        from .stereo import WassError
+        try:
+            self._ctx._check(rc)
+        except WassError as e:
+            m = re.search(r"frame (\d+)", str(e))
+            if e.code == -1 and m:
+                k = int(m.group(1))
+                raise ValueError(str(e).replace(f"frame {k}", f"frame {k + first_frame}")) from None
+            raise
+
+    # ---- the steps of refine(), for callers that want to look in between
+    def load(self, Zi, I0, I1, mask=None, first_frame=0):
+        """n <= batch frames onto the device: Zi n x Ny x Nx in metres (NaN outside), the pictures n x ih x iw (uint8 or float32),
+        mask n x Ny x Nx or Ny x Nx (a node is inside where it is not 0; default: where Zi is not NaN)."""
+        import torch
+        n = int(Zi.shape[0])
+        if tuple(int(v) for v in Zi.shape) != (n,) + self.shape or not 1 <= n <= self.batch:
+            raise ValueError(f"Zi of shape {tuple(Zi.shape)}: 1 .. {self.batch} frames of {self.shape} expected")
+        for name, I, shp in (("I0", I0, self.image_shapes[0]), ("I1", I1, self.image_shapes[1])):
+            if tuple(int(v) for v in I.shape) != (n,) + shp:
+                raise ValueError(f"{name} of shape {tuple(I.shape)}, expected {(n,) + shp}")
+        keep = [self._to_dev(Zi, torch.float32), self._to_dev(I0, torch.float32), self._to_dev(I1, torch.float32)]
+        d_mask = None
+        if mask is not None:
+            d_mask = self._to_dev(mask, torch.float32)
+            if tuple(d_mask.shape) == self.shape:
+                d_mask = d_mask.expand(n, *self.shape).contiguous()
+            if tuple(d_mask.shape) != (n,) + self.shape:
+                raise ValueError(f"mask of shape {tuple(mask.shape)}, expected {(n,) + self.shape} or {self.shape}")
+        torch.cuda.synchronize(self._dev)
+        self._n = 0
+        self._call(self._ctx._lib.wass_vref_batch_load(self._h, n, keep[0].data_ptr(), d_mask.data_ptr() if d_mask is not None else None,
+                                                       keep[1].data_ptr(), keep[2].data_ptr(), self.baseline), first_frame)
+        self._n = n
+
+    def _new(self, *shape):
+        import torch
+        t = torch.empty(shape, dtype=torch.float32, device=self._dev)
+        torch.cuda.synchronize(self._dev)
+        return t
+
+    def set_state(self, Zc, m=None, v=None, step=0):
+        """the coarse fields (n x Hc x Wc) and the optimiser's state of the loaded frames; m, v default to zeros"""
+        import torch
+        shape = (self._n,) + self.coarse_shape
+        t = []
+        for name, a in (("Zc", Zc), ("m", m), ("v", v)):
+            d = torch.zeros(shape, dtype=torch.float32, device=self._dev) if a is None else self._to_dev(a, torch.float32)
+            if tuple(d.shape) != shape:
+                raise ValueError(f"{name} of shape {tuple(d.shape)}, expected {shape}")
+            t.append(d)
+        torch.cuda.synchronize(self._dev)
+        self._call(self._ctx._lib.wass_vref_batch_set_state(self._h, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), int(step)))
+
+    def get_state(self):
+        """(Zc, m, v, step) of the loaded frames: device tensors n x Hc x Wc"""
+        t = [self._new(self._n, *self.coarse_shape) for _ in range(3)]
+        st = C.c_int64(0)
+        self._call(self._ctx._lib.wass_vref_batch_get_state(self._h, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), C.byref(st)))
+        return t[0], t[1], t[2], int(st.value)
+
+    def optimize(self, iters, alpha=10.0, lr=1e-3, eps=1e-7, report_every=10):
+        """`iters` Adam steps of every loaded frame; .losses: per frame the rows [steps done in this call, data, smoothness, energy]"""
+        iters, every = int(iters), int(report_every)
+        if iters < 0:
+            raise ValueError("iters must not be negative")
+        cap = 2 + ((iters + every - 1) // every if every > 0 else 0)
+        trace = np.zeros((max(self._n, 1), cap, 4), np.float64)
+        n = C.c_int(0)
+        self._call(self._ctx._lib.wass_vref_batch_optimize(self._h, iters, float(alpha), float(lr), float(eps), every, trace.ctypes.data, cap,
+                                                           C.byref(n)))
+        self.losses = [trace[f, :n.value].copy() for f in range(self._n)]
+
+    def result(self, out=None, with_plane=False):
+        """the refined surfaces in metres, NaN outside the masks (n x Ny x Nx, a device tensor; out: where to put them); with_plane:
+        also resize(Zc) * mask in the plane's frame"""
+        import torch
+        shape = (self._n,) + self.shape
+        if out is None:
+            out = self._new(*shape)
+        elif not _is_device(out) or tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous float32 device tensor of shape {shape} expected")
+        z = self._new(*shape) if with_plane else None
+        torch.cuda.synchronize(self._dev)
+        self._call(self._ctx._lib.wass_vref_batch_result(self._h, out.data_ptr(), z.data_ptr() if with_plane else None))
+        return (out, z) if with_plane else out
+
+    def refine(self, Zi, I0, I1, options: RefineOptions | None = None, mask=None, out=None, first_frame=0):
+        """load, options.max_iters steps, result: device tensors in, a device tensor out; the loss traces stay in .losses.
+        first_frame: the index of Zi[0] in the caller's sequence, for the message of a refusal."""
+        o = options if options is not None else RefineOptions()
+        self.load(Zi, I0, I1, mask, first_frame)
+        self.optimize(o.max_iters, alpha=o.alpha, lr=o.lr, report_every=o.report_every)
+        return self.result(out)
+
+
+def refine_sequence(Zi, I0, I1, gridsetup, mask=None, options: RefineOptions | None = None, ctx: Context | None = None, out=None):
+    """refine_surface for a sequence.  Zi: n x Ny x Nx in metres, z up, NaN outside (a host array, an np.memmap or a device
+    tensor); I0, I1: n x ih x iw, uint8 or float32; mask: n x Ny x Nx or Ny x Nx, a node is inside where it is not 0 (default:
+    where Zi is not NaN); out: an n x Ny x Nx float32 host array or memmap (a device tensor when Zi is one) that receives the
+    result.  The frames go through the device in sub-batches of options.batch, the last one ragged.  Returns (the refined cube,
+    the loss trace of every frame); frame i equals refine_surface(Zi[i], mask_i, I0[i], I1[i], gridsetup) bit for bit."""
+    import torch
+    o = options if options is not None else RefineOptions()
+    n = int(Zi.shape[0])
+    if len(Zi.shape) != 3 or n < 1:
+        raise ValueError(f"Zi of shape {tuple(Zi.shape)}: n x Ny x Nx expected")
+    if int(I0.shape[0]) != n or int(I1.shape[0]) != n:
+        raise ValueError("Zi, I0 and I1 must hold the same number of frames")
+    dev_in = _is_device(Zi)
+    shape = tuple(int(v) for v in Zi.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=Zi.device) if dev_in else np.empty(shape, np.float32)
+    elif tuple(out.shape) != shape or _is_device(out) != dev_in or str(out.dtype).split(".")[-1] != "float32":
+        raise ValueError(f"out: float32 of shape {shape} on the side of Zi expected")
+    per_frame_mask = mask is not None and len(mask.shape) == 3
+    nb = max(1, min(int(o.batch), n))
+    losses = []
+    with SequenceRefiner(gridsetup, (tuple(I0.shape[1:]), tuple(I1.shape[1:])), nb, ctx) as sr:
+        d_mask = None if mask is None or per_frame_mask else sr._to_dev(mask, torch.float32)
+        for i0 in range(0, n, nb):
+            k = slice(i0, min(n, i0 + nb))
+            part = (lambda a: a[k] if _is_device(a) else np.ascontiguousarray(a[k]))
+            mk = d_mask if not per_frame_mask else part(mask)
+            if dev_in:
+                sr.refine(Zi[k], part(I0), part(I1), o, mk, out=out[k], first_frame=i0)
+            else:
+                out[k] = sr.refine(part(Zi), part(I0), part(I1), o, mk, first_frame=i0).cpu().numpy()
+            losses += sr.losses
+    return out, losses
