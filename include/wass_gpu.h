@@ -897,6 +897,54 @@ int wass_zeromean(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride
 int wass_zeromean_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, float* d_out,
                       size_t out_stride_t, size_t out_stride_y);
 
+/* ---- Wave-by-wave statistics of the gridded cube (beyond the reference: DESIGN.md "Wave-by-wave statistics" is the
+ * specification).  For the series z[0 .. count - 1] of every cell of a count x H x W float32 cube (strides in elements, as for
+ * wass_sosfiltfilt), in fp64, every product, quotient and sum rounded on its own, sums first frame to last:
+ *   mean = sum(z) / count; eta = (z - mean) * datascale, or z * datascale with demean == 0; the moments sum(eta^2) / count,
+ *   sum(eta^2 * eta) / count, sum(eta^2 * eta^2) / count; the largest and the smallest eta;
+ *   an up-crossing at i where eta[i] < 0 <= eta[i + 1], at tau = i + eta[i] / (eta[i] - eta[i + 1]) samples; crossing ==
+ *   WASS_WS_DOWN looks for the up-crossings of -eta.  Wave k spans the samples after crossing k up to crossing k + 1: H_k = its
+ *   largest minus its smallest eta, T_k = (tau[k + 1] - tau[k]) * dt.  With C crossings there are Nw = max(C - 1, 0) waves.
+ *   Over the waves in time order: the means of H_k and of H_k^2, the largest H_k and the T_k of the first wave that has it,
+ *   Tz = ((tau[C - 1] - tau[0]) * dt) / Nw, and the means of H_k and T_k over the n13 = (Nw + 2) / 3 waves with the largest
+ *   H_k (of equal heights at the cut the earlier wave is taken; the sums run in time order over the waves taken).
+ * fields holds WASS_WS_NFIELDS maps of H x W doubles in the order of the enum; n_cross H x W int32 = C.  A series with a sample
+ * that is not finite gives NaN in every field and -1 in n_cross, and touches no other cell; the wave fields are NaN where
+ * Nw == 0.  With hist_bins > 0 every wave of every such series is counted in hist[min((int)floor(H_k / hist_width),
+ * hist_bins - 1)]; hist is zeroed first.  WASS_ERR_INVALID_ARG: count < 1, dt not positive or not finite, datascale not
+ * finite, another crossing, hist_bins < 0, hist_bins > 0 with hist_width <= 0.
+ * Rows go in slabs of at most slab_rows (0: as many as fit 16 GiB of scratch): 2 * (count / 2) * rows * W * 8 bytes for the
+ * waves, and for the host form count * rows * W * 4 for the cube, (WASS_WS_NFIELDS * 8 + 4) * rows * W for the results and
+ * hist_bins * 8, each part rounded up to 256 bytes; wass_wavestats_scratch_bytes says how much and how many rows, without a
+ * GPU, and checks the same arguments.  The result does not depend on the slab height and is the same bits on every run.
+ * _dev: in, fields, n_cross and hist are device memory.  Both forms return after a synchronisation. */
+enum {
+    WASS_WS_MEAN = 0,      /* mean * datascale */
+    WASS_WS_M2,
+    WASS_WS_M3,
+    WASS_WS_M4,
+    WASS_WS_ETA_MAX,
+    WASS_WS_ETA_MIN,
+    WASS_WS_H_MEAN,
+    WASS_WS_H_SQMEAN,
+    WASS_WS_H_MAX,
+    WASS_WS_T_HMAX,
+    WASS_WS_T_Z,
+    WASS_WS_H_13,
+    WASS_WS_T_13,
+    WASS_WS_NFIELDS
+};
+#define WASS_WS_UP 0
+#define WASS_WS_DOWN 1
+int wass_wavestats_scratch_bytes(int count, int H, int W, double dt, double datascale, int crossing, int hist_bins, double hist_width,
+                                 int slab_rows, int host, size_t* bytes, int* rows_per_slab);
+int wass_wavestats(wass_ctx* ctx, const float* in, size_t stride_t, size_t stride_y, int count, int H, int W, double dt, double datascale,
+                   int crossing, int demean, int hist_bins, double hist_width, int slab_rows, double* fields, int32_t* n_cross,
+                   uint64_t* hist);
+int wass_wavestats_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, double dt,
+                       double datascale, int crossing, int demean, int hist_bins, double hist_width, int slab_rows, double* d_fields,
+                       int32_t* d_n_cross, uint64_t* d_hist);
+
 /* ---- Feature matcher: the game-theoretic inlier selection of wass_match (src/wass_match/GTMatcher.cpp, iidyn.cpp) as array
  * functions.  A feature is four float32, x y scale angle (the head of a record of FeatureSet::save); a candidate is a pair of
  * int32, (feature of A, feature of B).

@@ -280,6 +280,9 @@ SYMBOLS = {
                                 C.POINTER(C.c_float)]),
     "wass_zeromean": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _sz, _sz]),
     "wass_zeromean_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _sz, _sz]),
+    "wass_wavestats_scratch_bytes": (_i, [_i, _i, _i, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_wavestats": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, C.c_double, C.c_double, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
+    "wass_wavestats_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, C.c_double, C.c_double, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
     "wass_match_scratch_bytes": (_i, [_i, _i, C.POINTER(_sz)]),
     "wass_match_knn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "wass_match_knn_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),

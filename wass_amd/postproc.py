@@ -1401,3 +1401,156 @@ def zeromean(data, out=None, ctx: Context | None = None):
     if suffix:
         ctx.synchronize()
     return out
+
+
+# ---- wave-by-wave statistics of the cube: zero crossings, H1/3, moments (beyond the reference; DESIGN.md has the definitions) ----
+WAVE_FIELDS = ("mean", "m2", "m3", "m4", "eta_max", "eta_min", "h_mean", "h_sqmean", "h_max", "t_hmax", "t_z", "h_13", "t_13")
+_CROSSINGS = {"up": 0, "down": 1}
+
+
+def _wave_args(count, H, W, dt, datascale, crossing, hist_bins, hist_width, slab_rows):
+    if crossing not in _CROSSINGS:
+        raise ValueError("crossing must be 'up' or 'down'")
+    count, H, W, hist_bins, slab_rows = int(count), int(H), int(W), int(hist_bins), int(slab_rows)
+    dt, datascale, hist_width = float(dt), float(datascale), float(hist_width)
+    if count < 1 or H < 1 or W < 1:
+        raise ValueError("empty cube")
+    if not (dt > 0 and np.isfinite(dt)):
+        raise ValueError("dt must be positive and finite")
+    if not np.isfinite(datascale):
+        raise ValueError("datascale must be finite")
+    if hist_bins < 0 or (hist_bins > 0 and not hist_width > 0):
+        raise ValueError("hist_bins > 0 needs hist_width > 0")
+    if slab_rows < 0:
+        raise ValueError("slab_rows must not be negative")
+    return count, H, W, dt, datascale, _CROSSINGS[crossing], hist_bins, hist_width, slab_rows
+
+
+def _wave_strides(st, sy, count, H, W):
+    """the stride of an axis of length 1 is never used, and numpy and torch may report anything for it (0 for a new axis)"""
+    sy = W if H == 1 else int(sy)
+    return (H * sy if count == 1 else int(st)), sy
+
+
+def wave_statistics_scratch_bytes(count: int, H: int, W: int, dt: float = 1.0, datascale: float = 1.0, crossing: str = "up",
+                                  hist_bins: int = 0, hist_width: float = 0.0, slab_rows: int = 0, host: bool = True):
+    """(bytes of device scratch, rows per slab) of one wave_statistics call; no GPU needed.  Per slab of `rows` rows:
+    2 * (count // 2) * rows * W * 8 bytes for the waves and, for a host cube, count * rows * W * 4 for the cube, 13 * rows * W * 8
+    and rows * W * 4 for the results and hist_bins * 8, each part rounded up to 256 bytes."""
+    from . import _lib
+    count, H, W, dt, datascale, cr, hist_bins, hist_width, slab_rows = _wave_args(count, H, W, dt, datascale, crossing, hist_bins, hist_width, slab_rows)
+    b, r = C.c_size_t(), C.c_int()
+    rc = _lib.load().wass_wavestats_scratch_bytes(count, H, W, dt, datascale, cr, hist_bins, hist_width, slab_rows, int(bool(host)),
+                                                  C.byref(b), C.byref(r))
+    if rc:
+        raise ValueError(f"wass_wavestats_scratch_bytes({count}, {H}, {W}): error {rc}")
+    return b.value, r.value
+
+
+@dataclass
+class WaveStatistics:
+    """What wave_statistics returns: H x W maps, numpy arrays for a host cube and tensors for a device cube.  The floating maps
+    are float64 and NaN where the cell's series holds a sample that is not finite; the wave maps are NaN where the cell has no wave."""
+    mean: object            # time mean of the cell, times datascale
+    m2: object              # mean of eta^2 (the variance with demean=True), eta^3, eta^4
+    m3: object
+    m4: object
+    eta_max: object
+    eta_min: object
+    h_mean: object          # mean of the wave heights H_k, and of H_k^2
+    h_sqmean: object
+    h_max: object           # the highest wave and the period of the first wave that high
+    t_hmax: object
+    t_z: object             # mean zero-crossing period: first crossing to last, over the number of waves
+    h_13: object            # mean height and period of the highest third of the waves
+    t_13: object
+    n_cross: object         # int32: zero crossings of the kind asked for; -1 in an invalid cell
+    n_waves: object         # int32: max(n_cross - 1, 0); -1 in an invalid cell
+    sigma: object           # sqrt(m2)
+    hs_m0: object           # 4 sigma
+    skewness: object        # m3 / (m2 sigma)
+    kurtosis: object        # m4 / m2^2
+    h_rms: object           # sqrt(h_sqmean)
+    hist: np.ndarray | None = None      # uint64 [hist_bins]: the heights of all waves of all valid cells, bins of hist_width, the last open
+    hist_width: float = 0.0
+    dt: float = 0.0
+    crossing: str = "up"
+
+    def _host(self, name) -> np.ndarray:
+        v = getattr(self, name)
+        return v.cpu().numpy() if _is_device(v) else np.asarray(v)
+
+    def summary(self) -> dict:
+        """Scalars over the valid cells, NaN-aware: their number, the number of waves, the medians of h_13, t_13, t_z and hs_m0,
+        the largest h_max and eta_max and their cells (row, column; None if there is none)."""
+        n_cross = self._host("n_cross")
+        valid = n_cross >= 0
+        out = {"valid_cells": int(valid.sum()), "n_waves": int(self._host("n_waves")[valid].sum())}
+        for name in ("h_13", "t_13", "t_z", "hs_m0"):
+            v = self._host(name)
+            v = v[np.isfinite(v)]
+            out["median_" + name] = float(np.median(v)) if v.size else float("nan")
+        for name in ("h_max", "eta_max"):
+            v = self._host(name)
+            if np.isnan(v).all():
+                out[name], out[name + "_cell"] = float("nan"), None
+            else:
+                at = int(np.nanargmax(v))
+                out[name], out[name + "_cell"] = float(v.flat[at]), (at // v.shape[1], at % v.shape[1])
+        return out
+
+
+def wave_statistics(data, dt: float, datascale: float = 1.0, crossing: str = "up", demean: bool = True, hist_bins: int = 0,
+                    hist_width: float = 0.0, ctx: Context | None = None, slab_rows: int = 0) -> WaveStatistics:
+    """The time-domain half of the wave product, for every cell of a count x H x W float32 cube: the individual waves between the
+    zero up-crossings (crossing="down": down-crossings) of eta = (z - time mean) * datascale (demean=False: z * datascale), their
+    heights H_k (crest minus trough) and periods T_k (crossings linearly interpolated, times dt), and from them the significant
+    height h_13 and its period t_13 (the means over the highest third, (Nw + 2) // 3 waves), h_max and its period, the mean
+    zero-crossing period t_z, h_mean and h_rms; and the surface moments: sigma, hs_m0 = 4 sigma, skewness, kurtosis, eta_max,
+    eta_min.  Pass datascale=1e-3 for GridSequenceResult.Z (millimetres) to get metres.  `data` is a host array or memmap (numpy
+    maps come back) or a device tensor (tensors come back); strided views whose last axis is contiguous are taken as they are.
+    All arithmetic is fp64 in a fixed order ("Wave-by-wave statistics"): the result is the same bits on every run and
+    does not depend on slab_rows, which caps the rows worked on at a time.  sigma, hs_m0, skewness, kurtosis and h_rms are
+    computed with numpy from the device's maps.  hist_bins > 0 also pools the heights of all waves into hist_bins bins of
+    hist_width (the last one open).  A cell with a NaN or an infinity in any frame is invalid: NaN maps, n_cross = n_waves = -1."""
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W, dt, datascale, cr, hist_bins, hist_width, slab_rows = _wave_args(*data.shape, dt, datascale, crossing, hist_bins, hist_width, slab_rows)
+    if ctx is None:
+        ctx = Context(0)
+    nf = len(WAVE_FIELDS)
+    hist = np.zeros(hist_bins, np.uint64) if hist_bins else None
+    args = (count, H, W, dt, datascale, cr, int(bool(demean)), hist_bins, hist_width, slab_rows)
+    if _is_device(data):
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+        d_fields = torch.empty((nf, H, W), dtype=torch.float64, device=data.device)
+        d_ncross = torch.empty((H, W), dtype=torch.int32, device=data.device)
+        d_hist = torch.empty(hist_bins, dtype=torch.int64, device=data.device) if hist_bins else None    # the call zeroes it
+        torch.cuda.current_stream(data.device).synchronize()
+        ctx._check(ctx._lib.wass_wavestats_dev(ctx._h, data.data_ptr(), *_wave_strides(data.stride(0), data.stride(1), count, H, W), *args,
+                                               d_fields.data_ptr(), d_ncross.data_ptr(), d_hist.data_ptr() if hist_bins else None))
+        fields, n_cross = d_fields.cpu().numpy(), d_ncross.cpu().numpy()
+        if hist_bins:
+            hist = d_hist.cpu().numpy().view(np.uint64)
+    else:
+        src = _host_f32_rows(data)
+        fields, n_cross = np.empty((nf, H, W), np.float64), np.empty((H, W), np.int32)
+        ctx._check(ctx._lib.wass_wavestats(ctx._h, src.ctypes.data, *_wave_strides(src.strides[0] // 4, src.strides[1] // 4, count, H, W), *args,
+                                           fields.ctypes.data, n_cross.ctypes.data, hist.ctypes.data if hist_bins else None))
+    m2, m3, m4, h_sqmean = (fields[WAVE_FIELDS.index(n)] for n in ("m2", "m3", "m4", "h_sqmean"))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sigma = np.sqrt(m2)
+        derived = {"n_waves": np.where(n_cross < 0, n_cross, np.maximum(n_cross - 1, 0)).astype(np.int32), "sigma": sigma, "hs_m0": 4.0 * sigma,
+                   "skewness": m3 / (m2 * sigma), "kurtosis": m4 / (m2 * m2), "h_rms": np.sqrt(h_sqmean)}
+    if _is_device(data):
+        import torch
+        maps = {n: d_fields[k] for k, n in enumerate(WAVE_FIELDS)}
+        maps["n_cross"] = d_ncross
+        maps.update({n: torch.from_numpy(np.ascontiguousarray(v)).to(data.device) for n, v in derived.items()})
+    else:
+        maps = {n: fields[k] for k, n in enumerate(WAVE_FIELDS)}
+        maps["n_cross"] = n_cross
+        maps.update(derived)
+    return WaveStatistics(hist=hist, hist_width=hist_width, dt=dt, crossing=crossing, **maps)
