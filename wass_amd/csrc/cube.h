@@ -1,0 +1,157 @@
+// cube.h -- what the one-shot operators of the count x H x W cube share (filter, radiance, polarimetric, pyramid, visibility,
+// wavestats; prepare_pol takes the keys): the host scaffolding of a call that allocates its scratch, runs and frees it, and the
+// ordered-key maxima of their kernels.  Plain functions and one RAII struct; every operator keeps its own plan and byte formula.
+// A call makes ONE hipMalloc and one hipFree by design: the scratch of a cube is gigabytes and is not kept in the context.
+#pragma once
+
+#include "common.h"
+
+namespace wass {
+
+// ---------------------------------------------------------------- host side
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// One hipMalloc of `total` bytes, handed out in 256-aligned pieces in the order asked, freed when the struct goes out of scope.
+// A total of 0 makes no call at all, and every piece of it is a pointer nobody may follow.
+struct Arena {
+    char* mem = nullptr;
+    size_t used = 0;
+    Arena() = default;
+    Arena(const Arena&) = delete;
+    Arena& operator=(const Arena&) = delete;
+    ~Arena() { if (mem) (void)hipFree(mem); }
+    int reserve(wass_ctx* c, size_t total, const char* what)
+    {
+        if (total && hipMalloc((void**)&mem, total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for %s failed", total, what);
+        return WASS_OK;
+    }
+    template <class T> T* take(size_t bytes)
+    {
+        T* p = (T*)(mem + used);
+        used += align256(bytes);
+        return p;
+    }
+};
+
+// The end of an operator `what`: the pending error e becomes the call's, unless rc already holds one; with `sync` the stream is
+// waited for, which a call that holds an Arena must do before it returns (the scratch is freed then).
+inline int finish(wass_ctx* c, int rc, hipError_t e, hipStream_t s, const char* what, bool sync = true)
+{
+    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    if (sync) {
+        e = hipStreamSynchronize(s);
+        if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// Rows of H x W per slab: as many as `avail` bytes hold at per_row bytes each (per_row 0: nothing grows with the rows), then at
+// most 0x7fffff00 / W, H and, where it is positive, `asked`.
+inline int slab_rows(size_t avail, size_t per_row, int H, int W, int asked, int* rows_out)
+{
+    size_t rows = per_row ? avail / per_row : (size_t)H;
+    if (rows < 1) return WASS_ERR_NO_MEMORY;
+    const size_t most = 0x7fffff00u / (size_t)W;        // the series of a slab are indexed with 32 bits
+    if (rows > most) rows = most;
+    if (rows > (size_t)H) rows = (size_t)H;
+    if (asked > 0 && rows > (size_t)asked) rows = (size_t)asked;
+    if (rows < 1) return WASS_ERR_UNSUPPORTED;
+    *rows_out = (int)rows;
+    return WASS_OK;
+}
+
+// Frames per launch: `asked` (0: dflt), at most count and most, halved until total(b) is at most cap.  0: not even one frame fits.
+// total(b) is called last with the batch returned, so it may fill in the plan as it goes.
+template <class F> int fit_batch(int asked, int dflt, int most, int count, size_t cap, F total)
+{
+    int b = asked ? asked : dflt;
+    if (b > count) b = count;
+    if (b > most) b = most;
+    while (b >= 1 && total(b) > cap) b /= 2;
+    return b;
+}
+
+// `count` frames, rows r0 .. r0 + rows - 1 of each, between a host cube (elements of `elem` bytes, st and sy elements from frame
+// to frame and row to row, the last axis dense) and a dense count x rows x W block on the device.  A whole batch is rows == H
+// with `host` at its first frame.
+inline hipError_t upload_rows(void* dev, const void* host, size_t elem, int count, int r0, int rows, int W, size_t st, size_t sy, hipStream_t s)
+{
+    const size_t rowb = (size_t)W * elem, plane = (size_t)rows * rowb;
+    hipError_t e = hipSuccess;
+    for (int t = 0; t < count && e == hipSuccess; ++t)
+        e = hipMemcpy2DAsync((char*)dev + (size_t)t * plane, rowb, (const char*)host + ((size_t)t * st + (size_t)r0 * sy) * elem, sy * elem, rowb, rows,
+                             hipMemcpyHostToDevice, s);
+    return e;
+}
+
+inline hipError_t download_rows(void* host, const void* dev, size_t elem, int count, int r0, int rows, int W, size_t st, size_t sy, hipStream_t s)
+{
+    const size_t rowb = (size_t)W * elem, plane = (size_t)rows * rowb;
+    hipError_t e = hipSuccess;
+    for (int t = 0; t < count && e == hipSuccess; ++t)
+        e = hipMemcpy2DAsync((char*)host + ((size_t)t * st + (size_t)r0 * sy) * elem, sy * elem, (const char*)dev + (size_t)t * plane, rowb, rowb, rows,
+                             hipMemcpyDeviceToHost, s);
+    return e;
+}
+
+// ---------------------------------------------------------------- device side
+// An unsigned key that orders like the number it was made from.  No number has key 0 or ~0: the callers keep 0 for "nothing seen".
+__device__ __forceinline__ unsigned order_key(float v)
+{
+    const unsigned b = __float_as_uint(v);
+    return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ unsigned long long order_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__host__ __device__ __forceinline__ float order_unkey(unsigned k)
+{
+    return __builtin_bit_cast(float, (k >> 31) ? (k & 0x7fffffffu) : ~k);
+}
+
+__host__ __device__ __forceinline__ double order_unkey(unsigned long long k)
+{
+    return __builtin_bit_cast(double, (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
+}
+
+__device__ __forceinline__ unsigned wave_max(unsigned k)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned other = (unsigned)__shfl_xor((int)k, o, 64);
+        k = other > k ? other : k;
+    }
+    return k;
+}
+
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long k)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(k, o, 64);
+        k = other > k ? other : k;
+    }
+    return k;
+}
+
+// The largest key of a block of 64 x BY threads into *dst (0 = nothing seen, and nothing is written); every thread of the block
+// calls it, and a kernel may call it more than once.
+template <int BY, class K> __device__ __forceinline__ void block_max(K k, K* dst)
+{
+    __shared__ K part[BY];
+    k = wave_max(k);
+    __syncthreads();                                    // `part` may still be read by an earlier call
+    if (threadIdx.x == 0) part[threadIdx.y] = k;
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+#pragma unroll
+        for (int w = 1; w < BY; ++w) k = part[w] > k ? part[w] : k;
+        if (k) atomicMax(dst, k);
+    }
+}
+
+}  // namespace wass

@@ -15,7 +15,10 @@
 // Rows are filtered in slabs so that the fp64 hand-over, (count + 2 padlen) * rows * W * 8 bytes, and the staging of a host
 // cube, count * rows * W * 4 bytes, stay under FILT_SCRATCH_CAP; a series never crosses a slab, so the result does not
 // depend on the slab height.  No atomics: the same input gives the same bits.
+// Host side: filt_plan keeps the byte formula; the slab rule, the scratch, the staging of a host slab and the end of the call
+// are cube.h's.
 #include "common.h"
+#include "cube.h"
 
 namespace wass {
 
@@ -172,24 +175,16 @@ struct FiltPlan {
     size_t ypad_bytes = 0, stage_bytes = 0, total = 0;
 };
 
-static size_t filt_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // 0, or why the problem cannot be planned
-static int filt_plan(int count, int H, int W, int padlen, int slab_rows, bool host, FiltPlan& p)
+static int filt_plan(int count, int H, int W, int padlen, int slab, bool host, FiltPlan& p)
 {
-    if (count < 1 || H < 1 || W < 1 || padlen < 0 || slab_rows < 0 || count <= padlen) return WASS_ERR_INVALID_ARG;
+    if (count < 1 || H < 1 || W < 1 || padlen < 0 || slab < 0 || count <= padlen) return WASS_ERR_INVALID_ARG;
     const size_t P = (size_t)count + 2 * (size_t)padlen;
     const size_t per_row = P * (size_t)W * 8 + (host ? (size_t)count * (size_t)W * 4 : 0);
-    size_t rows = (FILT_SCRATCH_CAP - 512) / per_row;
-    if (rows < 1) return WASS_ERR_NO_MEMORY;
-    const size_t most = 0x7fffff00u / (size_t)W;         // the series of a slab are indexed with 32 bits
-    if (rows > most) rows = most;
-    if (rows > (size_t)H) rows = (size_t)H;
-    if (slab_rows > 0 && rows > (size_t)slab_rows) rows = (size_t)slab_rows;
-    if (rows < 1) return WASS_ERR_UNSUPPORTED;
-    p.rows = (int)rows;
-    p.ypad_bytes = filt_align(P * rows * (size_t)W * 8);
-    p.stage_bytes = host ? filt_align((size_t)count * rows * (size_t)W * 4) : 0;
+    const int rc = slab_rows(FILT_SCRATCH_CAP - 512, per_row, H, W, slab, &p.rows);
+    if (rc) return rc;
+    p.ypad_bytes = align256(P * (size_t)p.rows * (size_t)W * 8);
+    p.stage_bytes = host ? align256((size_t)count * (size_t)p.rows * (size_t)W * 4) : 0;
     p.total = p.ypad_bytes + p.stage_bytes;
     return WASS_OK;
 }
@@ -226,34 +221,27 @@ static int filt_run(wass_ctx* c, bool host, const float* in, size_t st, size_t s
         return set_err(c, WASS_ERR_INVALID_ARG, "bad strides");
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the filter scratch failed", p.total);
-    double* ypad = (double*)mem;
-    float* stage = (float*)(mem + p.ypad_bytes);
-    const size_t rowb = (size_t)W * 4;
+    Arena mem;
+    if ((rc = mem.reserve(c, p.total, "the filter scratch"))) return rc;
+    double* ypad = mem.take<double>(p.ypad_bytes);
+    float* stage = mem.take<float>(p.stage_bytes);
     for (int r0 = 0; r0 < H && !rc; r0 += p.rows) {
         const int rows = H - r0 < p.rows ? H - r0 : p.rows;
         const unsigned nser = (unsigned)((size_t)rows * W);
         if (host) {
             const size_t plane = (size_t)rows * W;
-            hipError_t e = hipSuccess;
-            for (int t = 0; t < count && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(stage + t * plane, rowb, in + t * st + (size_t)r0 * sy, sy * 4, rowb, rows, hipMemcpyHostToDevice, s);
+            hipError_t e = upload_rows(stage, in, 4, count, r0, rows, W, st, sy, s);
             if (e != hipSuccess) { rc = set_err(c, WASS_ERR_DEVICE, "upload of a slab: %s", hipGetErrorString(e)); break; }
             // the backward pass reads the hand-over only: the result may take the staged input's place
             rc = filter_slab(c, s, ns, stage, (long long)plane, W, W, nser, count, padlen, a, ypad, remove_mean != 0, stage, (long long)plane, W);
-            for (int t = 0; t < count && !rc && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(out + t * ost + (size_t)r0 * osy, osy * 4, stage + t * plane, rowb, rowb, rows, hipMemcpyDeviceToHost, s);
+            if (!rc) e = download_rows(out, stage, 4, count, r0, rows, W, ost, osy, s);
             if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "download of a slab: %s", hipGetErrorString(e));
         } else {
             rc = filter_slab(c, s, ns, in + (size_t)r0 * sy, (long long)st, (long long)sy, W, nser, count, padlen, a, ypad, remove_mean != 0,
                              out + (size_t)r0 * osy, (long long)ost, (long long)osy);
         }
     }
-    const hipError_t e = hipStreamSynchronize(s);       // the scratch is freed below
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "temporal filter: %s", hipGetErrorString(e));
-    (void)hipFree(mem);
-    return rc;
+    return finish(c, rc, hipSuccess, s, "temporal filter");
 }
 
 }  // namespace wass

@@ -18,7 +18,10 @@
 //   k_pol_finish        Savg / valid, Navg / |Navg|, Zavg / total_frames
 //   k_clip              np.clip in float32 (NaN kept) and the range of what is not NaN (integer atomics on ordered keys)
 //   k_zeromean          per cell the fp64 sum over the frames in order, / count, out = (float)((double)z - mean)
+// Host side: pol_plan keeps the byte formula; the batch and slab rules, the scratch, the staging of a host batch or slab and the
+// end of a call are cube.h's.
 #include "common.h"
+#include "cube.h"
 #include "surface.h"
 
 #include <cfloat>
@@ -33,8 +36,6 @@ constexpr int POL_DEFAULT_BATCH = 8;
 constexpr int POL_BX = 64, POL_BY = 4;                  // a block: 4 waves, each 64 cells of one row
 constexpr int POL_BITS = 5, POL_TAB = 1 << POL_BITS, POL_TAB2 = POL_TAB * POL_TAB;
 constexpr int POL_U = 8;                                // frames loaded ahead of the fp64 chain of k_zeromean
-
-static size_t pol_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------- the bilinear table (imgwarp.cpp interpolateLinear, initInterTab2D)
 // tab[((fy * 32 + fx) * 2 + ky) * 2 + kx] = ty[ky] * tx[kx], t = (1 - f / 32, f / 32): every value a multiple of 1 / 1024, exact
@@ -139,20 +140,19 @@ static int remap_f32_run(wass_ctx* c, bool host, const float* src, int sw, int s
     rc = ensure_bilinear_tab(c);
     if (rc) return rc;
     hipStream_t s = c->ts();
-    const size_t n = (size_t)dw * dh, src_bytes = pol_align((size_t)sh * sw * 4), nb = pol_align(n * 4);
-    char* mem = nullptr;
+    const size_t n = (size_t)dw * dh, src_bytes = align256((size_t)sh * sw * 4), nb = align256(n * 4);
+    Arena mem;
     const float *dsrc = src, *dmx = mx, *dmy = my;
     float* ddst = dst;
     size_t dss = ss;
     hipError_t e = hipSuccess;
     if (host) {
-        const size_t total = src_bytes + 3 * nb;
-        if (hipMalloc((void**)&mem, total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the remap failed", total);
-        float* a = (float*)mem;
-        float* b = (float*)(mem + src_bytes);
-        float* d = (float*)(mem + src_bytes + nb);
-        ddst = (float*)(mem + src_bytes + 2 * nb);
-        e = hipMemcpy2DAsync(a, (size_t)sw * 4, src, ss * 4, (size_t)sw * 4, sh, hipMemcpyHostToDevice, s);
+        if ((rc = mem.reserve(c, src_bytes + 3 * nb, "the remap"))) return rc;
+        float* a = mem.take<float>(src_bytes);
+        float* b = mem.take<float>(nb);
+        float* d = mem.take<float>(nb);
+        ddst = mem.take<float>(nb);
+        e = upload_rows(a, src, 4, 1, 0, sh, sw, 0, ss, s);
         if (e == hipSuccess) e = hipMemcpyAsync(b, mx, n * 4, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d, my, n * 4, hipMemcpyHostToDevice, s);
         dsrc = a; dmx = b; dmy = d; dss = (size_t)sw;
@@ -163,14 +163,7 @@ static int remap_f32_run(wass_ctx* c, bool host, const float* src, int sw, int s
         e = hipGetLastError();
         if (e == hipSuccess && host) e = hipMemcpyAsync(dst, ddst, n * 4, hipMemcpyDeviceToHost, s);
     }
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "remap_linear_f32: %s", hipGetErrorString(e));
-    if (host) {
-        e = hipStreamSynchronize(s);
-        if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "remap_linear_f32: %s", hipGetErrorString(e));
-        (void)hipFree(mem);
-    }
-    return rc;
+    return finish(c, WASS_OK, e, s, "remap_linear_f32", host);
 }
 
 // ---------------------------------------------------------------- polarimetric_setup
@@ -314,32 +307,25 @@ static int pol_plan(int count, int H, int W, int Ih, int Iw, int batch, bool hos
         return WASS_ERR_INVALID_ARG;
     const size_t HW = (size_t)H * W;
     if (HW > 0x7fffff00u) return WASS_ERR_UNSUPPORTED;
-    int b = batch ? batch : POL_DEFAULT_BATCH;
-    if (b > count) b = count;
-    if (b > POL_MAX_BATCH) b = POL_MAX_BATCH;
-    p.grid_bytes = host ? 2 * pol_align(HW * 8) : 0;
-    p.acc_bytes = host ? pol_align(HW * 64) : 0;
-    for (;; b /= 2) {
-        if (b < 1) return WASS_ERR_NO_MEMORY;
+    p.grid_bytes = host ? 2 * align256(HW * 8) : 0;
+    p.acc_bytes = host ? align256(HW * 64) : 0;
+    p.batch = fit_batch(batch, POL_DEFAULT_BATCH, POL_MAX_BATCH, count, POL_SCRATCH_CAP, [&](int b) {
         const size_t n = (size_t)b * HW;
-        p.st_bytes = host ? pol_align((size_t)b * 3 * Ih * Iw * 4) : 0;
-        p.z_bytes = host ? pol_align(n * 4) : 0;
-        p.mask_bytes = host || !(outputs & POL_OUT_OCC) ? pol_align(n) : 0;
-        p.ang_bytes = host || !(outputs & POL_OUT_ANG) ? pol_align(n * 4) : 0;
-        p.S_bytes = host || !(outputs & POL_OUT_S) ? pol_align(n * 12) : 0;
-        p.dolp_bytes = host && (outputs & POL_OUT_DOLP) ? pol_align(n * 4) : 0;
-        p.nrm_bytes = host && (outputs & POL_OUT_NRM) ? pol_align(n * 24) : 0;
-        p.ray_bytes = host && (outputs & POL_OUT_RAYS) ? pol_align(n * 24) : 0;
+        p.st_bytes = host ? align256((size_t)b * 3 * Ih * Iw * 4) : 0;
+        p.z_bytes = host ? align256(n * 4) : 0;
+        p.mask_bytes = host || !(outputs & POL_OUT_OCC) ? align256(n) : 0;
+        p.ang_bytes = host || !(outputs & POL_OUT_ANG) ? align256(n * 4) : 0;
+        p.S_bytes = host || !(outputs & POL_OUT_S) ? align256(n * 12) : 0;
+        p.dolp_bytes = host && (outputs & POL_OUT_DOLP) ? align256(n * 4) : 0;
+        p.nrm_bytes = host && (outputs & POL_OUT_NRM) ? align256(n * 24) : 0;
+        p.ray_bytes = host && (outputs & POL_OUT_RAYS) ? align256(n * 24) : 0;
         p.own = p.grid_bytes + p.acc_bytes + p.st_bytes + p.z_bytes + p.mask_bytes + p.ang_bytes + p.S_bytes + p.dolp_bytes + p.nrm_bytes + p.ray_bytes;
         int used = 0;
-        const int rc = wass_visibility_scratch_bytes(b, H, W, b, 0, &p.vis_bytes, &used);
-        if (rc == WASS_ERR_NO_MEMORY) continue;
-        if (rc) return rc;
-        p.total = p.own + p.vis_bytes;
-        if (p.total <= POL_SCRATCH_CAP) break;
-    }
-    p.batch = b;
-    return WASS_OK;
+        // the sizes were checked above, so the visibility map's plan can only fail for want of memory
+        if (wass_visibility_scratch_bytes(b, H, W, b, 0, &p.vis_bytes, &used)) return ~(size_t)0;
+        return p.total = p.own + p.vis_bytes;
+    });
+    return p.batch ? WASS_OK : WASS_ERR_NO_MEMORY;
 }
 
 static int pol_run(wass_ctx* c, bool host, const float* stokes, size_t sst, size_t ssc, size_t ssy, int Ih, int Iw, const float* in, size_t st,
@@ -379,21 +365,19 @@ static int pol_run(wass_ctx* c, bool host, const float* stokes, size_t sst, size
     g.scale = (float)prm->datascale;
     if (!(g.dx > 0.0) || !(g.dy > 0.0)) return set_err(c, WASS_ERR_INVALID_ARG, "the grid spacing must be positive (dx = %g, dy = %g)", g.dx, g.dy);
     const size_t HW = (size_t)H * W, II = (size_t)Ih * Iw;
-    char* mem = nullptr;
-    if (p.own && hipMalloc((void**)&mem, p.own) != hipSuccess)
-        return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the polarimetric scratch failed", p.own);
-    char* q = mem;
-    double* dXX = (double*)q;               q += p.grid_bytes / 2;
-    double* dYY = (double*)q;               q += p.grid_bytes / 2;
-    double* dacc = (double*)q;              q += p.acc_bytes;
-    float* sst_ = (float*)q;                q += p.st_bytes;
-    float* sz = (float*)q;                  q += p.z_bytes;
-    unsigned char* smask = (unsigned char*)q; q += p.mask_bytes;
-    float* sang = (float*)q;                q += p.ang_bytes;
-    float* sS = (float*)q;                  q += p.S_bytes;
-    float* sdolp = (float*)q;               q += p.dolp_bytes;
-    double* snrm = (double*)q;              q += p.nrm_bytes;
-    double* sray = (double*)q;
+    Arena mem;                                              // the device form with every per-frame output given: nothing
+    if ((rc = mem.reserve(c, p.own, "the polarimetric scratch"))) return rc;
+    double* dXX = mem.take<double>(p.grid_bytes / 2);
+    double* dYY = mem.take<double>(p.grid_bytes / 2);
+    double* dacc = mem.take<double>(p.acc_bytes);
+    float* sst_ = mem.take<float>(p.st_bytes);
+    float* sz = mem.take<float>(p.z_bytes);
+    unsigned char* smask = mem.take<unsigned char>(p.mask_bytes);
+    float* sang = mem.take<float>(p.ang_bytes);
+    float* sS = mem.take<float>(p.S_bytes);
+    float* sdolp = mem.take<float>(p.dolp_bytes);
+    double* snrm = mem.take<double>(p.nrm_bytes);
+    double* sray = mem.take<double>(p.ray_bytes);
     hipError_t e = hipSuccess;
     if (host) {
         e = hipMemcpyAsync(dXX, XX, HW * 8, hipMemcpyHostToDevice, s);
@@ -414,12 +398,9 @@ static int pol_run(wass_ctx* c, bool host, const float* stokes, size_t sst, size
         const float* zin = in + (size_t)t0 * st;
         long long zst = (long long)st, zsy = (long long)sy;
         if (host) {
-            for (int t = 0; t < nb && e == hipSuccess; ++t) {
-                for (int k = 0; k < 3 && e == hipSuccess; ++k)
-                    e = hipMemcpy2DAsync(sst_ + ((size_t)t * 3 + k) * II, (size_t)Iw * 4, pic + t * sst + k * ssc, ssy * 4, (size_t)Iw * 4, Ih,
-                                         hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipMemcpy2DAsync(sz + t * HW, (size_t)W * 4, zin + t * st, sy * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, s);
-            }
+            for (int t = 0; t < nb && e == hipSuccess; ++t)     // a frame's three channels: a cube of three pictures, ssc apart
+                e = upload_rows(sst_ + (size_t)t * 3 * II, pic + t * sst, 4, 3, 0, Ih, Iw, ssc, ssy, s);
+            if (e == hipSuccess) e = upload_rows(sz, zin, 4, nb, 0, H, W, st, sy, s);
             if (e != hipSuccess) break;
             pic = sst_; pt = 3 * II; pc = II; py = (size_t)Iw; zin = sz; zst = (long long)HW; zsy = W;
         }
@@ -456,40 +437,12 @@ static int pol_run(wass_ctx* c, bool host, const float* stokes, size_t sst, size
         e = hipGetLastError();
     }
     if (!rc && e == hipSuccess && host) e = hipMemcpyAsync(acc, dacc, HW * 64, hipMemcpyDeviceToHost, s);
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "polarimetric set-up: %s", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);                            // the scratch is freed below
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "polarimetric set-up: %s", hipGetErrorString(e));
+    rc = finish(c, rc, e, s, "polarimetric set-up");
     if (!rc && not_upward) *not_upward = up_total;
-    if (mem) (void)hipFree(mem);
     return rc;
 }
 
 // ---------------------------------------------------------------- clip and zeromean
-// an unsigned key that orders like the float it was made from; no number has key 0 or ~0
-__device__ __forceinline__ unsigned pol_key(float v)
-{
-    const unsigned b = __float_as_uint(v);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-
-static float pol_unkey(unsigned k)
-{
-    const unsigned b = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    float v;
-    memcpy(&v, &b, 4);
-    return v;
-}
-
-__device__ __forceinline__ unsigned pol_wave_max(unsigned k)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned other = (unsigned)__shfl_xor((int)k, o, 64);
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
 // rec[0] = the largest ~key (the minimum), rec[1] = the largest key (the maximum) of the clipped values that are not NaN; 0 = none
 __global__ void __launch_bounds__(POL_BX * POL_BY) k_clip(const float* x, long long st, long long sy, int H, int W, float lo, float hi, float* out,
                                                           long long ot, long long oy, unsigned* __restrict__ rec)
@@ -502,10 +455,10 @@ __global__ void __launch_bounds__(POL_BX * POL_BY) k_clip(const float* x, long l
         v = v < lo ? lo : v;                            // np.maximum, then np.minimum; NaN fails both comparisons and stays
         v = v > hi ? hi : v;
         out[(long long)blockIdx.z * ot + (long long)i * oy + j] = v;
-        if (v == v) { khi = pol_key(v); klo = ~khi; }
+        if (v == v) { khi = order_key(v); klo = ~khi; }
     }
-    klo = pol_wave_max(klo);
-    khi = pol_wave_max(khi);
+    klo = wave_max(klo);
+    khi = wave_max(khi);
     if (threadIdx.x == 0) { part[0][threadIdx.y] = klo; part[1][threadIdx.y] = khi; }
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0) {
@@ -570,26 +523,24 @@ static int clip_run(wass_ctx* c, bool host, const float* in, size_t st, size_t s
     const size_t HW = (size_t)H * W;
     size_t b = count < POL_MAX_BATCH ? count : POL_MAX_BATCH;
     if (host)
-        while (b > 1 && 256 + 2 * pol_align(b * HW * 4) > POL_SCRATCH_CAP) b /= 2;
-    const size_t stage = host ? pol_align(b * HW * 4) : 0, total = 256 + 2 * stage;
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the clip failed", total);
-    unsigned* rec = (unsigned*)mem;
-    float* sin_ = (float*)(mem + 256);
-    float* sout = (float*)(mem + 256 + stage);
-    hipError_t e = hipMemsetAsync(mem, 0, 256, s);
+        while (b > 1 && 256 + 2 * align256(b * HW * 4) > POL_SCRATCH_CAP) b /= 2;
+    const size_t stage = host ? align256(b * HW * 4) : 0, total = 256 + 2 * stage;
+    Arena mem;
+    if ((rc = mem.reserve(c, total, "the clip"))) return rc;
+    unsigned* rec = mem.take<unsigned>(256);
+    float* sin_ = mem.take<float>(stage);
+    float* sout = mem.take<float>(stage);
+    hipError_t e = hipMemsetAsync(rec, 0, 256, s);
     const dim3 block(POL_BX, POL_BY);
     for (int t0 = 0; t0 < count && e == hipSuccess; t0 += (int)b) {
         const int nb = count - t0 < (int)b ? count - t0 : (int)b;
         const dim3 grid((W + POL_BX - 1) / POL_BX, (H + POL_BY - 1) / POL_BY, nb);
         if (host) {
-            for (int t = 0; t < nb && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(sin_ + t * HW, (size_t)W * 4, in + (size_t)(t0 + t) * st, sy * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, s);
+            e = upload_rows(sin_, in + (size_t)t0 * st, 4, nb, 0, H, W, st, sy, s);
             if (e != hipSuccess) break;
             hipLaunchKernelGGL(k_clip, grid, block, 0, s, (const float*)sin_, (long long)HW, (long long)W, H, W, lo, hi, sout, (long long)HW, (long long)W, rec);
             e = hipGetLastError();
-            for (int t = 0; t < nb && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(out + (size_t)(t0 + t) * ost, osy * 4, sout + t * HW, (size_t)W * 4, (size_t)W * 4, H, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = download_rows(out + (size_t)t0 * ost, sout, 4, nb, 0, H, W, ost, osy, s);
         } else {
             hipLaunchKernelGGL(k_clip, grid, block, 0, s, in + (size_t)t0 * st, (long long)st, (long long)sy, H, W, lo, hi, out + (size_t)t0 * ost,
                                (long long)ost, (long long)osy, rec);
@@ -598,14 +549,10 @@ static int clip_run(wass_ctx* c, bool host, const float* in, size_t st, size_t s
     }
     unsigned r[2] = { 0, 0 };
     if (e == hipSuccess) e = hipMemcpyAsync(r, rec, 8, hipMemcpyDeviceToHost, s);
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "clip: %s", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "clip: %s", hipGetErrorString(e));
-    (void)hipFree(mem);
+    rc = finish(c, WASS_OK, e, s, "clip");
     if (!rc) {
-        if (vmin) *vmin = r[0] ? pol_unkey(~r[0]) : NAN;
-        if (vmax) *vmax = r[1] ? pol_unkey(r[1]) : NAN;
+        if (vmin) *vmin = r[0] ? order_unkey(~r[0]) : NAN;
+        if (vmax) *vmax = r[1] ? order_unkey(r[1]) : NAN;
     }
     return rc;
 }
@@ -618,46 +565,32 @@ static int zeromean_run(wass_ctx* c, bool host, const float* in, size_t st, size
     if (rc) return rc;
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    size_t rows = (size_t)H;
-    if (host) {
-        const size_t per_row = (size_t)count * (size_t)W * 4;
-        rows = (POL_SCRATCH_CAP - 256) / per_row;
-        if (rows < 1) return set_err(c, WASS_ERR_NO_MEMORY, "one row of %d frames does not fit the scratch cap of %zu bytes", count, POL_SCRATCH_CAP);
-        if (rows > (size_t)H) rows = (size_t)H;
-    }
-    char* mem = nullptr;
-    const size_t total = pol_align((size_t)count * rows * (size_t)W * 4);
-    if (host && hipMalloc((void**)&mem, total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for zeromean failed", total);
-    float* stage = (float*)mem;
-    const size_t rowb = (size_t)W * 4;
+    int rows = H;
+    if (host && slab_rows(POL_SCRATCH_CAP - 256, (size_t)count * (size_t)W * 4, H, W, 0, &rows))
+        return set_err(c, WASS_ERR_NO_MEMORY, "one row of %d frames does not fit the scratch cap of %zu bytes", count, POL_SCRATCH_CAP);
+    Arena mem;                                              // the device form: nothing
+    const size_t stage_bytes = host ? align256((size_t)count * (size_t)rows * (size_t)W * 4) : 0;
+    if ((rc = mem.reserve(c, stage_bytes, "zeromean"))) return rc;
+    float* stage = mem.take<float>(stage_bytes);
     hipError_t e = hipSuccess;
-    for (int r0 = 0; r0 < H && e == hipSuccess; r0 += (int)rows) {
-        const int nr = H - r0 < (int)rows ? H - r0 : (int)rows;
+    for (int r0 = 0; r0 < H && e == hipSuccess; r0 += rows) {
+        const int nr = H - r0 < rows ? H - r0 : rows;
         const unsigned nser = (unsigned)((size_t)nr * W);
         const dim3 grid((nser + 255u) / 256u), block(256);
         if (host) {
             const size_t plane = (size_t)nr * W;
-            for (int t = 0; t < count && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(stage + t * plane, rowb, in + t * st + (size_t)r0 * sy, sy * 4, rowb, nr, hipMemcpyHostToDevice, s);
+            e = upload_rows(stage, in, 4, count, r0, nr, W, st, sy, s);
             if (e != hipSuccess) break;
             hipLaunchKernelGGL(k_zeromean, grid, block, 0, s, (const float*)stage, (long long)plane, (long long)W, W, nser, count, stage, (long long)plane,
                                (long long)W);
             e = hipGetLastError();
-            for (int t = 0; t < count && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(out + t * ost + (size_t)r0 * osy, osy * 4, stage + t * plane, rowb, rowb, nr, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = download_rows(out, stage, 4, count, r0, nr, W, ost, osy, s);
         } else {
             hipLaunchKernelGGL(k_zeromean, grid, block, 0, s, in, (long long)st, (long long)sy, W, nser, count, out, (long long)ost, (long long)osy);
             e = hipGetLastError();
         }
     }
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "zeromean: %s", hipGetErrorString(e));
-    if (host) {
-        e = hipStreamSynchronize(s);                        // the scratch is freed below
-        if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "zeromean: %s", hipGetErrorString(e));
-        (void)hipFree(mem);
-    }
-    return rc;
+    return finish(c, WASS_OK, e, s, "zeromean", host);
 }
 
 }  // namespace wass

@@ -13,10 +13,11 @@
 //                   Every float32 product and sum is rounded on its own (the library is built with -ffp-contract=off); quotients and
 //                   roots are formed in fp64 and rounded again, which is the correctly rounded float32 result; exp and atan2 are fp64.
 //   k_prepare_pol_ranges   the ranges of S0, S1, S2 and DOLP (NaN skipped): k_prepare_pol leaves one record of ordered integer keys per
-//                   block, this kernel takes their maxima.  No float atomics, no dependence on the order of execution.
+//                   block (cube.h's order_key), this kernel takes their maxima.  No float atomics, no dependence on the order of execution.
 //
 // OpenCV is absent here: written from knowledge of OpenCV 4.5.5 (resize.cpp, imgwarp.cpp, undistort.dispatch.cpp), PARITY UNPINNED.
 #include "common.h"
+#include "cube.h"          // align256, order_key, order_unkey, wave_max
 #include "undistort_map.h"
 
 #include <cmath>
@@ -120,28 +121,6 @@ __device__ __forceinline__ float hdr_weight(float I)
     return (float)exp((double)arg);
 }
 
-// an unsigned key that orders like the float it was made from; no number has key 0 or ~0
-__device__ __forceinline__ unsigned prep_key(float v)
-{
-    const unsigned b = __float_as_uint(v);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float prep_unkey(unsigned k)
-{
-    return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ __forceinline__ unsigned prep_wave_max(unsigned k)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned other = (unsigned)__shfl_xor((int)k, o, 64);
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
 __global__ void __launch_bounds__(PP_BX * PP_BY) k_prepare_pol(const uint8_t* __restrict__ mosaic, size_t stride, int m, int n,
                                                                const double* __restrict__ xs, const double* __restrict__ ys, const Dist12 D,
                                                                double fx, double fy, double u0, double v0, int hdr, const PrepOut o,
@@ -191,9 +170,9 @@ __global__ void __launch_bounds__(PP_BX * PP_BY) k_prepare_pol(const uint8_t* __
         const float S2 = I45 - I135;
         const size_t HW = (size_t)H * W, i = (size_t)y * W + x;
         if (o.S) { o.S[i] = S0; o.S[HW + i] = S1; o.S[2 * HW + i] = S2; }
-        if (S0 == S0) { key[1] = prep_key(S0); key[0] = ~key[1]; }
-        if (S1 == S1) { key[3] = prep_key(S1); key[2] = ~key[3]; }
-        if (S2 == S2) { key[5] = prep_key(S2); key[4] = ~key[5]; }
+        if (S0 == S0) { key[1] = order_key(S0); key[0] = ~key[1]; }
+        if (S1 == S1) { key[3] = order_key(S1); key[2] = ~key[3]; }
+        if (S2 == S2) { key[5] = order_key(S2); key[4] = ~key[5]; }
         float pic;
         if (hdr) {
             const float w0 = hdr_weight(I0), w45 = hdr_weight(I45), w90 = hdr_weight(I90), w135 = hdr_weight(I135);
@@ -208,7 +187,7 @@ __global__ void __launch_bounds__(PP_BX * PP_BY) k_prepare_pol(const uint8_t* __
         if (o.dolp) {
             const float q = S1 * S1 + S2 * S2;
             const float dolp = div_f32((float)sqrt((double)q), S0);
-            if (dolp == dolp) { key[7] = prep_key(dolp); key[6] = ~key[7]; }
+            if (dolp == dolp) { key[7] = order_key(dolp); key[6] = ~key[7]; }
             o.dolp[i] = sat_u8(dolp * 255.0f);
         }
         if (o.aolp || o.aolp_f32) {
@@ -229,7 +208,7 @@ __global__ void __launch_bounds__(PP_BX * PP_BY) k_prepare_pol(const uint8_t* __
     // the block's record: every lane takes part, the ones outside the picture with key 0 (= nothing)
 #pragma unroll
     for (int k = 0; k < PP_NKEY; ++k) {
-        const unsigned v = prep_wave_max(key[k]);
+        const unsigned v = wave_max(key[k]);
         if (threadIdx.x == 0) red[k][threadIdx.y] = v;
     }
     __syncthreads();
@@ -255,7 +234,7 @@ __global__ void __launch_bounds__(256) k_prepare_pol_ranges(const unsigned* __re
     }
 #pragma unroll
     for (int k = 0; k < PP_NKEY; ++k) {
-        const unsigned v = prep_wave_max(key[k]);
+        const unsigned v = wave_max(key[k]);
         if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
     }
     __syncthreads();
@@ -264,11 +243,9 @@ __global__ void __launch_bounds__(256) k_prepare_pol_ranges(const unsigned* __re
         unsigned v = red[k][0];
 #pragma unroll
         for (int wv = 1; wv < 4; ++wv) v = red[k][wv] > v ? red[k][wv] : v;
-        ranges[k] = !v ? __uint_as_float(0x7fc00000u) : prep_unkey((k & 1) ? v : ~v);
+        ranges[k] = !v ? __uint_as_float(0x7fc00000u) : order_unkey((k & 1) ? v : ~v);
     }
 }
-
-static size_t prep_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static int prep_check(wass_ctx* c, const void* mosaic, int cols, int rows, size_t stride, const double* K, const double* dist, int n_dist,
                       const wass_pol_prep_params* prm, const wass_pol_prep_out* out)
@@ -303,7 +280,7 @@ static int prep_dev(wass_ctx* c, const uint8_t* d_mosaic, int cols, int rows, si
     const double* dxy = nullptr;
     if ((rc = undistort_tables(c, K, W, H, &dxy))) return rc;
     const dim3 block(PP_BX, PP_BY), grid((W + PP_BX - 1) / PP_BX, (H + PP_BY - 1) / PP_BY);
-    const size_t nblocks = (size_t)grid.x * grid.y, part_bytes = prep_align(nblocks * PP_NKEY * sizeof(unsigned));
+    const size_t nblocks = (size_t)grid.x * grid.y, part_bytes = align256(nblocks * PP_NKEY * sizeof(unsigned));
     if ((rc = ensure(c, c->prep_pol, part_bytes + 256))) return rc;
     unsigned* part = (unsigned*)c->prep_pol.p;
     float* d_ranges = (float*)((char*)c->prep_pol.p + part_bytes);
@@ -357,9 +334,9 @@ extern "C" int wass_prepare_pol(wass_ctx* c, const uint8_t* mosaic, int cols, in
     const int W = cols / 2 * 2, H = rows / 2 * 2, b = params->outputs;
     const size_t HW = (size_t)W * H;
     // the staged results, in the order of the members; only what was asked for
-    const size_t sz[7] = { (b & WASS_PREP_STOKES) ? prep_align(HW * 12) : 0, prep_align(HW), (b & WASS_PREP_DOLP) ? prep_align(HW) : 0,
-                           (b & WASS_PREP_AOLP) ? prep_align(HW) : 0, (b & WASS_PREP_CHANNELS) ? prep_align(HW * 4) : 0,
-                           (b & WASS_PREP_IMAGE_F32) ? prep_align(HW * 4) : 0, (b & WASS_PREP_AOLP_F32) ? prep_align(HW * 4) : 0 };
+    const size_t sz[7] = { (b & WASS_PREP_STOKES) ? align256(HW * 12) : 0, align256(HW), (b & WASS_PREP_DOLP) ? align256(HW) : 0,
+                           (b & WASS_PREP_AOLP) ? align256(HW) : 0, (b & WASS_PREP_CHANNELS) ? align256(HW * 4) : 0,
+                           (b & WASS_PREP_IMAGE_F32) ? align256(HW * 4) : 0, (b & WASS_PREP_AOLP_F32) ? align256(HW * 4) : 0 };
     size_t off[8] = { 0 };
     for (int k = 0; k < 7; ++k) off[k + 1] = off[k] + sz[k];
     if ((rc = ensure(c, c->tmp_in0, HW)) || (rc = ensure(c, c->tmp_out, off[7]))) return rc;

@@ -26,7 +26,10 @@
 //   wass_radiance_up*   per batch: k_pyr_scale, `levels` times k_pyrup<float>, then radiance.hip's k_radiance (unchanged, called
 //                  with scale 1, which leaves zf as it is) on the upsampled heights and the grid upsampled once per call with
 //                  k_pyrup<double>.
+// Host side: pyr_plan and radup_plan keep their byte formulas; the batch rule, the scratch, the staging of a host batch and the
+// end of a call are cube.h's.
 #include "common.h"
+#include "cube.h"
 
 namespace wass {
 
@@ -36,8 +39,6 @@ constexpr int PYR_DEFAULT_BATCH = 8;
 constexpr int PYR_BX = 64, PYR_BY = 4;                  // a block: 4 waves, each 64 source cells of one row
 constexpr int PYR_MAX_LEVELS = 4;
 constexpr int PYR_MAX_SIDE = 65536;                     // of the result
-
-static size_t pyr_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 template <typename T> struct PyrPair;
 template <> struct PyrPair<float> { typedef float2 type; };
@@ -146,19 +147,14 @@ static int pyr_plan(int count, int H, int W, int levels, int elem, int batch, bo
     const int rc = pyr_sizes_ok(H, W, levels);
     if (rc) return rc;
     const size_t HW = (size_t)H * W;
-    int b = batch ? batch : PYR_DEFAULT_BATCH;
-    if (b > count) b = count;
-    if (b > PYR_MAX_BATCH) b = PYR_MAX_BATCH;
-    for (;; b /= 2) {
-        if (b < 1) return WASS_ERR_NO_MEMORY;
-        p.in_bytes = host ? pyr_align((size_t)b * HW * elem) : 0;
-        p.out_bytes = host ? pyr_align(((size_t)b * HW << (2 * levels)) * elem) : 0;
+    p.batch = fit_batch(batch, PYR_DEFAULT_BATCH, PYR_MAX_BATCH, count, PYR_SCRATCH_CAP, [&](int b) {
+        p.in_bytes = host ? align256((size_t)b * HW * elem) : 0;
+        p.out_bytes = host ? align256(((size_t)b * HW << (2 * levels)) * elem) : 0;
         p.total = p.in_bytes + p.out_bytes;
-        for (int l = 1; l < levels; ++l) p.total += p.mid_bytes[l - 1] = pyr_align(((size_t)b * HW << (2 * l)) * elem);
-        if (p.total <= PYR_SCRATCH_CAP) break;
-    }
-    p.batch = b;
-    return WASS_OK;
+        for (int l = 1; l < levels; ++l) p.total += p.mid_bytes[l - 1] = align256(((size_t)b * HW << (2 * l)) * elem);
+        return p.total;
+    });
+    return p.batch ? WASS_OK : WASS_ERR_NO_MEMORY;
 }
 
 template <typename T>
@@ -175,13 +171,12 @@ static int pyr_run(wass_ctx* c, bool host, const T* in, size_t ist, size_t isy, 
     if (!host && (const void*)in == (const void*)out) return set_err(c, WASS_ERR_INVALID_ARG, "pyrUp cannot work in place");
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    char* mem = nullptr;
-    if (p.total && hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for pyrUp failed", p.total);
-    char* q = mem;
-    T* sin = (T*)q;     q += p.in_bytes;
+    Arena mem;                                              // one level on the device: nothing
+    if ((rc = mem.reserve(c, p.total, "pyrUp"))) return rc;
+    T* sin = mem.take<T>(p.in_bytes);
     T* mid[PYR_MAX_LEVELS] = {};
-    for (int l = 1; l < levels; ++l) { mid[l - 1] = (T*)q; q += p.mid_bytes[l - 1]; }
-    T* sout = (T*)q;
+    for (int l = 1; l < levels; ++l) mid[l - 1] = mem.take<T>(p.mid_bytes[l - 1]);
+    T* sout = mem.take<T>(p.out_bytes);
     const size_t HW = (size_t)H * W, HWo = Ho * Wo;
     hipError_t e = hipSuccess;
     for (int t0 = 0; t0 < count && e == hipSuccess; t0 += p.batch) {
@@ -189,24 +184,15 @@ static int pyr_run(wass_ctx* c, bool host, const T* in, size_t ist, size_t isy, 
         const T* src = in + (size_t)t0 * ist;
         T* dst = out + (size_t)t0 * ost;
         if (host) {
-            for (int t = 0; t < nb && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(sin + t * HW, (size_t)W * sizeof(T), src + t * ist, isy * sizeof(T), (size_t)W * sizeof(T), H, hipMemcpyHostToDevice, s);
+            e = upload_rows(sin, src, sizeof(T), nb, 0, H, W, ist, isy, s);
             if (e != hipSuccess) break;
             e = pyr_levels<T>(sin, (long long)HW, W, nb, H, W, levels, mid, sout, (long long)HWo, (long long)Wo, s);
-            for (int t = 0; t < nb && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(dst + t * ost, osy * sizeof(T), sout + t * HWo, Wo * sizeof(T), Wo * sizeof(T), Ho, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = download_rows(dst, sout, sizeof(T), nb, 0, (int)Ho, (int)Wo, ost, osy, s);
         } else {
             e = pyr_levels<T>(src, (long long)ist, (long long)isy, nb, H, W, levels, mid, dst, (long long)ost, (long long)osy, s);
         }
     }
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "pyrUp: %s", hipGetErrorString(e));
-    if (mem) {
-        e = hipStreamSynchronize(s);                        // the scratch is freed below
-        if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "pyrUp: %s", hipGetErrorString(e));
-        (void)hipFree(mem);
-    }
-    return rc;
+    return finish(c, WASS_OK, e, s, "pyrUp", p.total != 0);
 }
 
 // ---------------------------------------------------------------- radiance on the upsampled grid
@@ -225,26 +211,21 @@ static int radup_plan(int count, int H, int W, int Ih, int Iw, int levels, int b
     if (rc) return rc;
     const size_t HW = (size_t)H * W, HWu = HW << (2 * levels);
     if (HWu > 0x7fffff00u) return WASS_ERR_UNSUPPORTED;     // as wass_radiance
-    int b = batch ? batch : PYR_DEFAULT_BATCH;
-    if (b > count) b = count;
-    if (b > PYR_MAX_BATCH) b = PYR_MAX_BATCH;
-    p.gsrc_bytes = host ? 2 * pyr_align(HW * 8) : 0;
-    p.gup_bytes = 2 * pyr_align(HWu * 8);
+    p.gsrc_bytes = host ? 2 * align256(HW * 8) : 0;
+    p.gup_bytes = 2 * align256(HWu * 8);
     size_t fixed = p.gsrc_bytes + p.gup_bytes;
-    for (int l = 1; l < levels; ++l) fixed += p.gmid_bytes[l - 1] = pyr_align((HW << (2 * l)) * 8);
-    for (;; b /= 2) {
-        if (b < 1) return WASS_ERR_NO_MEMORY;
-        p.img_bytes = host ? pyr_align((size_t)b * Ih * Iw) : 0;
-        p.zin_bytes = host ? pyr_align((size_t)b * HW * 4) : 0;
-        p.zf_bytes = pyr_align((size_t)b * HW * 4);
-        p.zup_bytes = pyr_align((size_t)b * HWu * 4);
+    for (int l = 1; l < levels; ++l) fixed += p.gmid_bytes[l - 1] = align256((HW << (2 * l)) * 8);
+    p.batch = fit_batch(batch, PYR_DEFAULT_BATCH, PYR_MAX_BATCH, count, PYR_SCRATCH_CAP, [&](int b) {
+        p.img_bytes = host ? align256((size_t)b * Ih * Iw) : 0;
+        p.zin_bytes = host ? align256((size_t)b * HW * 4) : 0;
+        p.zf_bytes = align256((size_t)b * HW * 4);
+        p.zup_bytes = align256((size_t)b * HWu * 4);
         p.out_bytes = host ? p.zup_bytes : 0;
         p.total = fixed + p.img_bytes + p.zin_bytes + p.zf_bytes + p.zup_bytes + p.out_bytes;
-        for (int l = 1; l < levels; ++l) p.total += p.zmid_bytes[l - 1] = pyr_align(((size_t)b * HW << (2 * l)) * 4);
-        if (p.total <= PYR_SCRATCH_CAP) break;
-    }
-    p.batch = b;
-    return WASS_OK;
+        for (int l = 1; l < levels; ++l) p.total += p.zmid_bytes[l - 1] = align256(((size_t)b * HW << (2 * l)) * 4);
+        return p.total;
+    });
+    return p.batch ? WASS_OK : WASS_ERR_NO_MEMORY;
 }
 
 static int radup_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, size_t img_y, int Ih, int Iw, const float* in, size_t st, size_t sy,
@@ -262,20 +243,19 @@ static int radup_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, s
     hipStream_t s = c->ts();
     const int Hu = H << levels, Wu = W << levels;
     const size_t HW = (size_t)H * W, HWu = (size_t)Hu * Wu, II = (size_t)Ih * Iw;
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the upsampled radiance failed", p.total);
-    char* q = mem;
-    double* gsrc[2] = { (double*)q, (double*)(q + p.gsrc_bytes / 2) };      q += p.gsrc_bytes;
+    Arena mem;
+    if ((rc = mem.reserve(c, p.total, "the upsampled radiance"))) return rc;
+    double* gsrc[2] = { mem.take<double>(p.gsrc_bytes / 2), mem.take<double>(p.gsrc_bytes / 2) };
     double* gmid[PYR_MAX_LEVELS] = {};
-    for (int l = 1; l < levels; ++l) { gmid[l - 1] = (double*)q; q += p.gmid_bytes[l - 1]; }
-    double* gup[2] = { (double*)q, (double*)(q + p.gup_bytes / 2) };        q += p.gup_bytes;
-    uint8_t* simg = (uint8_t*)q;    q += p.img_bytes;
-    float* szin = (float*)q;        q += p.zin_bytes;
-    float* zf = (float*)q;          q += p.zf_bytes;
+    for (int l = 1; l < levels; ++l) gmid[l - 1] = mem.take<double>(p.gmid_bytes[l - 1]);
+    double* gup[2] = { mem.take<double>(p.gup_bytes / 2), mem.take<double>(p.gup_bytes / 2) };
+    uint8_t* simg = mem.take<uint8_t>(p.img_bytes);
+    float* szin = mem.take<float>(p.zin_bytes);
+    float* zf = mem.take<float>(p.zf_bytes);
     float* zmid[PYR_MAX_LEVELS] = {};
-    for (int l = 1; l < levels; ++l) { zmid[l - 1] = (float*)q; q += p.zmid_bytes[l - 1]; }
-    float* zup = (float*)q;         q += p.zup_bytes;
-    float* sout = (float*)q;
+    for (int l = 1; l < levels; ++l) zmid[l - 1] = mem.take<float>(p.zmid_bytes[l - 1]);
+    float* zup = mem.take<float>(p.zup_bytes);
+    float* sout = mem.take<float>(p.out_bytes);
     hipError_t e = hipSuccess;
     const double* g[2] = { XX, YY };
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
@@ -296,10 +276,8 @@ static int radup_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, s
         long long zst = (long long)st, zsy = (long long)sy;
         float* o = out + (size_t)t0 * HWu;
         if (host) {
-            for (int t = 0; t < nb && e == hipSuccess; ++t) {
-                e = hipMemcpy2DAsync(simg + t * II, (size_t)Iw, im + t * img_t, img_y, (size_t)Iw, Ih, hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipMemcpy2DAsync(szin + t * HW, (size_t)W * 4, zin + t * st, sy * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, s);
-            }
+            e = upload_rows(simg, im, 1, nb, 0, Ih, Iw, img_t, img_y, s);
+            if (e == hipSuccess) e = upload_rows(szin, zin, 4, nb, 0, H, W, st, sy, s);
             if (e != hipSuccess) break;
             im = simg; it = II; iy = (size_t)Iw; zin = szin; zst = (long long)HW; zsy = W; o = sout;
         }
@@ -311,11 +289,7 @@ static int radup_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, s
         rc = radiance_enqueue(c, im, it, iy, Ih, Iw, zup, HWu, (size_t)Wu, nb, Hu, Wu, gup[0], gup[1], Pcam, 1.0f, o, s);
         if (!rc && host) e = hipMemcpyAsync(out + (size_t)t0 * HWu, sout, (size_t)nb * HWu * 4, hipMemcpyDeviceToHost, s);
     }
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "upsampled radiance: %s", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);                            // the scratch is freed below
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "upsampled radiance: %s", hipGetErrorString(e));
-    (void)hipFree(mem);
-    return rc;
+    return finish(c, rc, e, s, "upsampled radiance");
 }
 
 }  // namespace wass

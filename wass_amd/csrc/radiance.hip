@@ -18,8 +18,11 @@
 //                     the chain.  Rows go in slabs under the scratch cap; a series never crosses a slab.  No atomics.
 //   k_thr_*           Isub = I - (Ibg - min(Ibg)) in float32; per frame the minimum of Ibg, the range of Isub, the 30-bin histogram
 //                     of Isub against 31 given float32 edges (numpy's rule: left edge inclusive, last bin closed) and the mask
-//                     Isub > thr.  Integer atomics only: the same input gives the same bits.
+//                     Isub > thr.  Integer atomics only (cube.h's ordered keys and block maximum): the same input gives the same bits.
+// Host side: every *_plan keeps its byte formula; the batch and slab rules, the scratch, the staging of a host batch or slab
+// (pictures too: they are cubes of bytes) and the end of a call are cube.h's.
 #include "common.h"
+#include "cube.h"
 
 #include <cfloat>
 #include <cmath>
@@ -34,8 +37,6 @@ constexpr int RAD_BX = 64, RAD_BY = 4;                  // a block: 4 waves, eac
 constexpr int RAD_BITS = 5, RAD_TAB = 1 << RAD_BITS, RAD_TAB2 = RAD_TAB * RAD_TAB, RAD_COEF = 1 << 15;
 constexpr int BG_U = 8;                                 // time steps loaded ahead of the running sum
 constexpr int THR_BINS = 30;
-
-static size_t rad_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------- the Lanczos4 table (imgwarp.cpp interpolateLanczos4, initInterTab2D)
 static void lanczos4_1d(float x, float* c)
@@ -224,21 +225,20 @@ static int remap_run(wass_ctx* c, bool host, const uint8_t* src, int sw, int sh,
     rc = ensure_lanczos_tab(c);
     if (rc) return rc;
     hipStream_t s = c->ts();
-    const size_t n = (size_t)dw * dh, src_bytes = rad_align((size_t)sh * sw);
-    char* mem = nullptr;
+    const size_t n = (size_t)dw * dh, src_bytes = align256((size_t)sh * sw);
+    Arena mem;
     const uint8_t* dsrc = src;
     const float *dmx = mx, *dmy = my;
     uint8_t* ddst = dst;
     size_t dss = ss;
     hipError_t e = hipSuccess;
     if (host) {
-        const size_t total = src_bytes + 2 * rad_align(n * 4) + rad_align(n);
-        if (hipMalloc((void**)&mem, total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the remap failed", total);
-        uint8_t* a = (uint8_t*)mem;
-        float* b = (float*)(mem + src_bytes);
-        float* d = (float*)(mem + src_bytes + rad_align(n * 4));
-        ddst = (uint8_t*)(mem + src_bytes + 2 * rad_align(n * 4));
-        e = hipMemcpy2DAsync(a, (size_t)sw, src, ss, (size_t)sw, sh, hipMemcpyHostToDevice, s);
+        if ((rc = mem.reserve(c, src_bytes + 2 * align256(n * 4) + align256(n), "the remap"))) return rc;
+        uint8_t* a = mem.take<uint8_t>(src_bytes);
+        float* b = mem.take<float>(n * 4);
+        float* d = mem.take<float>(n * 4);
+        ddst = mem.take<uint8_t>(n);
+        e = upload_rows(a, src, 1, 1, 0, sh, sw, 0, ss, s);
         if (e == hipSuccess) e = hipMemcpyAsync(b, mx, n * 4, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d, my, n * 4, hipMemcpyHostToDevice, s);
         dsrc = a; dmx = b; dmy = d; dss = (size_t)sw;
@@ -249,14 +249,7 @@ static int remap_run(wass_ctx* c, bool host, const uint8_t* src, int sw, int sh,
         e = hipGetLastError();
         if (e == hipSuccess && host) e = hipMemcpyAsync(dst, ddst, n, hipMemcpyDeviceToHost, s);
     }
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "remap_lanczos4: %s", hipGetErrorString(e));
-    if (host) {
-        e = hipStreamSynchronize(s);
-        if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "remap_lanczos4: %s", hipGetErrorString(e));
-        (void)hipFree(mem);
-    }
-    return rc;
+    return finish(c, WASS_OK, e, s, "remap_lanczos4", host);
 }
 
 struct RadPlan {
@@ -271,20 +264,14 @@ static int rad_plan(int count, int H, int W, int Ih, int Iw, int batch, bool hos
         return WASS_ERR_INVALID_ARG;
     const size_t HW = (size_t)H * W;
     if (HW > 0x7fffff00u) return WASS_ERR_UNSUPPORTED;
-    int b = batch ? batch : RAD_DEFAULT_BATCH;
-    if (b > count) b = count;
-    if (b > RAD_MAX_BATCH) b = RAD_MAX_BATCH;
-    p.grid_bytes = host ? 2 * rad_align(HW * 8) : 0;
-    for (;; b /= 2) {
-        if (b < 1) return WASS_ERR_NO_MEMORY;
-        p.img_bytes = host ? rad_align((size_t)b * Ih * Iw) : 0;
-        p.z_bytes = host ? rad_align((size_t)b * HW * 4) : 0;
+    p.grid_bytes = host ? 2 * align256(HW * 8) : 0;
+    p.batch = fit_batch(batch, RAD_DEFAULT_BATCH, RAD_MAX_BATCH, count, RAD_SCRATCH_CAP, [&](int b) {
+        p.img_bytes = host ? align256((size_t)b * Ih * Iw) : 0;
+        p.z_bytes = host ? align256((size_t)b * HW * 4) : 0;
         p.out_bytes = p.z_bytes;
-        p.total = p.grid_bytes + p.img_bytes + p.z_bytes + p.out_bytes;
-        if (p.total <= RAD_SCRATCH_CAP) break;
-    }
-    p.batch = b;
-    return WASS_OK;
+        return p.total = p.grid_bytes + p.img_bytes + p.z_bytes + p.out_bytes;
+    });
+    return p.batch ? WASS_OK : WASS_ERR_NO_MEMORY;
 }
 
 static int rad_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, size_t img_y, int Ih, int Iw, const float* in, size_t st, size_t sy,
@@ -305,22 +292,19 @@ static int rad_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, siz
     for (int k = 0; k < 12; ++k) P.p[k] = Pcam[k];
     P.scale = (float)datascale;
     const size_t HW = (size_t)H * W, II = (size_t)Ih * Iw;
-    char* mem = nullptr;
+    Arena mem;                                              // the device form: nothing
+    if ((rc = mem.reserve(c, p.total, "the radiance scratch"))) return rc;
+    double* sXX = mem.take<double>(p.grid_bytes / 2);
+    double* sYY = mem.take<double>(p.grid_bytes / 2);
+    uint8_t* simg = mem.take<uint8_t>(p.img_bytes);
+    float* sz = mem.take<float>(p.z_bytes);
+    float* sout = mem.take<float>(p.out_bytes);
     const double *dXX = XX, *dYY = YY;
-    uint8_t* simg = nullptr;
-    float *sz = nullptr, *sout = nullptr;
     hipError_t e = hipSuccess;
     if (host) {
-        if (hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the radiance scratch failed", p.total);
-        char* q = mem;
-        double* a = (double*)q;     q += p.grid_bytes / 2;
-        double* b = (double*)q;     q += p.grid_bytes / 2;
-        simg = (uint8_t*)q;         q += p.img_bytes;
-        sz = (float*)q;             q += p.z_bytes;
-        sout = (float*)q;
-        e = hipMemcpyAsync(a, XX, HW * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(b, YY, HW * 8, hipMemcpyHostToDevice, s);
-        dXX = a; dYY = b;
+        e = hipMemcpyAsync(sXX, XX, HW * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(sYY, YY, HW * 8, hipMemcpyHostToDevice, s);
+        dXX = sXX; dYY = sYY;
     }
     const dim3 block(RAD_BX, RAD_BY);
     for (int t0 = 0; t0 < count && e == hipSuccess; t0 += p.batch) {
@@ -332,10 +316,8 @@ static int rad_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, siz
         long long zst = (long long)st, zsy = (long long)sy;
         float* o = out + (size_t)t0 * HW;
         if (host) {
-            for (int t = 0; t < nb && e == hipSuccess; ++t) {
-                e = hipMemcpy2DAsync(simg + t * II, (size_t)Iw, im + t * img_t, img_y, (size_t)Iw, Ih, hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipMemcpy2DAsync(sz + t * HW, (size_t)W * 4, zin + t * st, sy * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, s);
-            }
+            e = upload_rows(simg, im, 1, nb, 0, Ih, Iw, img_t, img_y, s);
+            if (e == hipSuccess) e = upload_rows(sz, zin, 4, nb, 0, H, W, st, sy, s);
             if (e != hipSuccess) break;
             im = simg; it = II; iy = (size_t)Iw; zin = sz; zst = (long long)HW; zsy = W; o = sout;
         }
@@ -343,14 +325,7 @@ static int rad_run(wass_ctx* c, bool host, const uint8_t* img, size_t img_t, siz
         e = hipGetLastError();
         if (e == hipSuccess && host) e = hipMemcpyAsync(out + (size_t)t0 * HW, sout, (size_t)nb * HW * 4, hipMemcpyDeviceToHost, s);
     }
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "radiance: %s", hipGetErrorString(e));
-    if (host) {
-        e = hipStreamSynchronize(s);                        // the scratch is freed below
-        if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "radiance: %s", hipGetErrorString(e));
-        (void)hipFree(mem);
-    }
-    return rc;
+    return finish(c, WASS_OK, e, s, "radiance", host);
 }
 
 // k_radiance for nb frames of device memory on stream s, for pyramid.hip: the heights arrive as the caller formed them and are
@@ -462,19 +437,12 @@ struct BgPlan {
     size_t stage_bytes = 0, total = 0;                  // the host form stages the slab and its result; the device form needs nothing
 };
 
-static int bg_plan(int count, int H, int W, int size, int slab_rows, bool host, BgPlan& p)
+static int bg_plan(int count, int H, int W, int size, int slab, bool host, BgPlan& p)
 {
-    if (count < 1 || H < 1 || W < 1 || size < 1 || slab_rows < 0) return WASS_ERR_INVALID_ARG;
-    const size_t per_row = (size_t)count * (size_t)W * 4 * 2;
-    size_t rows = host ? (RAD_SCRATCH_CAP - 512) / per_row : (size_t)H;
-    if (rows < 1) return WASS_ERR_NO_MEMORY;
-    const size_t most = 0x7fffff00u / (size_t)W;        // the series of a slab are indexed with 32 bits
-    if (rows > most) rows = most;
-    if (rows > (size_t)H) rows = (size_t)H;
-    if (slab_rows > 0 && rows > (size_t)slab_rows) rows = (size_t)slab_rows;
-    if (rows < 1) return WASS_ERR_UNSUPPORTED;
-    p.rows = (int)rows;
-    p.stage_bytes = host ? rad_align((size_t)count * rows * (size_t)W * 4) : 0;
+    if (count < 1 || H < 1 || W < 1 || size < 1 || slab < 0) return WASS_ERR_INVALID_ARG;
+    const int rc = slab_rows(RAD_SCRATCH_CAP - 512, host ? (size_t)count * (size_t)W * 4 * 2 : 0, H, W, slab, &p.rows);
+    if (rc) return rc;
+    p.stage_bytes = host ? align256((size_t)count * (size_t)p.rows * (size_t)W * 4) : 0;
     p.total = 2 * p.stage_bytes;
     return WASS_OK;
 }
@@ -492,11 +460,10 @@ static int bg_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy,
     if (!host && in == out) return set_err(c, WASS_ERR_INVALID_ARG, "the box filter cannot work in place");
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    char* mem = nullptr;
-    if (host && hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the box filter failed", p.total);
-    float* stage = (float*)mem;
-    float* sout = (float*)(mem + p.stage_bytes);
-    const size_t rowb = (size_t)W * 4;
+    Arena mem;                                              // the device form: nothing
+    if ((rc = mem.reserve(c, p.total, "the box filter"))) return rc;
+    float* stage = mem.take<float>(p.stage_bytes);
+    float* sout = mem.take<float>(p.stage_bytes);
     hipError_t e = hipSuccess;
     for (int r0 = 0; r0 < H && e == hipSuccess; r0 += p.rows) {
         const int rows = H - r0 < p.rows ? H - r0 : p.rows;
@@ -504,71 +471,22 @@ static int bg_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy,
         const dim3 grid((nser + 255u) / 256u), block(256);
         if (host) {
             const size_t plane = (size_t)rows * W;
-            for (int t = 0; t < count && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(stage + t * plane, rowb, in + t * st + (size_t)r0 * sy, sy * 4, rowb, rows, hipMemcpyHostToDevice, s);
+            e = upload_rows(stage, in, 4, count, r0, rows, W, st, sy, s);
             if (e != hipSuccess) break;
             hipLaunchKernelGGL(k_bgimage, grid, block, 0, s, (const float*)stage, (long long)plane, (long long)W, W, nser, count, size, sout,
                                (long long)plane, (long long)W);
             e = hipGetLastError();
-            for (int t = 0; t < count && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(out + t * ost + (size_t)r0 * osy, osy * 4, sout + t * plane, rowb, rowb, rows, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = download_rows(out, sout, 4, count, r0, rows, W, ost, osy, s);
         } else {
             hipLaunchKernelGGL(k_bgimage, grid, block, 0, s, in + (size_t)r0 * sy, (long long)st, (long long)sy, W, nser, count, size,
                                out + (size_t)r0 * osy, (long long)ost, (long long)osy);
             e = hipGetLastError();
         }
     }
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "box filter: %s", hipGetErrorString(e));
-    if (host) {
-        e = hipStreamSynchronize(s);                        // the scratch is freed below
-        if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "box filter: %s", hipGetErrorString(e));
-        (void)hipFree(mem);
-    }
-    return rc;
+    return finish(c, WASS_OK, e, s, "box filter", host);
 }
 
 // ---------------------------------------------------------------- radiance_threshold
-// an unsigned key that orders like the float it was made from; no number has key 0 or ~0
-__device__ __forceinline__ unsigned thr_key(float v)
-{
-    const unsigned b = __float_as_uint(v);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-
-static float thr_unkey(unsigned k)
-{
-    const unsigned b = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    float v;
-    memcpy(&v, &b, 4);
-    return v;
-}
-
-__device__ __forceinline__ unsigned thr_wave_max(unsigned k)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned other = (unsigned)__shfl_xor((int)k, o, 64);
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
-// the block's largest key into *dst (0 = nothing seen); every thread of the block calls it
-__device__ __forceinline__ void thr_block_max(unsigned k, unsigned* dst)
-{
-    __shared__ unsigned part[RAD_BY];
-    k = thr_wave_max(k);
-    __syncthreads();                                    // `part` may still be read by an earlier call
-    if (threadIdx.x == 0) part[threadIdx.y] = k;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-#pragma unroll
-        for (int w = 1; w < RAD_BY; ++w) k = part[w] > k ? part[w] : k;
-        if (k) atomicMax(dst, k);
-    }
-}
-
 // per frame 8 words: [0] ~key of min(Ibg)  [1] ~key of min(Isub)  [2] key of max(Isub)  [3] cells of Isub that are not finite
 // [4] cells of Ibg that are NaN.  All start at 0.
 constexpr int THR_WORDS = 8;
@@ -583,18 +501,17 @@ __global__ void __launch_bounds__(RAD_BX * RAD_BY) k_thr_bgmin(const float* __re
     if (i < H && j < W) {
         const float v = B[(long long)blockIdx.z * bt + (long long)i * by + j];
         nan = v != v;
-        if (!nan) k = ~thr_key(v);
+        if (!nan) k = ~order_key(v);
     }
     const unsigned long long wn = __ballot(nan);
     if (wn && threadIdx.x == 0) atomicAdd(r + 4, (unsigned)__popcll(wn));
-    thr_block_max(k, r);
+    block_max<RAD_BY>(k, r);
 }
 
 __device__ __forceinline__ float thr_bgmin(const unsigned* r)
 {
     if (r[4]) return __uint_as_float(0x7fc00000u);      // np.amin of a frame with a NaN
-    const unsigned k = ~r[0];
-    return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
+    return order_unkey(~r[0]);
 }
 
 __global__ void __launch_bounds__(RAD_BX * RAD_BY) k_thr_range(const float* __restrict__ I, long long it, long long iy,
@@ -609,12 +526,12 @@ __global__ void __launch_bounds__(RAD_BX * RAD_BY) k_thr_range(const float* __re
     if (i < H && j < W) {
         const float v = I[(long long)blockIdx.z * it + (long long)i * iy + j] - (B[(long long)blockIdx.z * bt + (long long)i * by + j] - m);
         bad = !(fabsf(v) <= 3.402823466e38f);
-        if (!bad) { khi = thr_key(v); klo = ~khi; }
+        if (!bad) { khi = order_key(v); klo = ~khi; }
     }
     const unsigned long long wb = __ballot(bad);
     if (wb && threadIdx.x == 0) atomicAdd(r + 3, (unsigned)__popcll(wb));
-    thr_block_max(klo, r + 1);
-    thr_block_max(khi, r + 2);
+    block_max<RAD_BY>(klo, r + 1);
+    block_max<RAD_BY>(khi, r + 2);
 }
 
 // counts[f][30] += the histogram of Isub of frame f against edges[f][31]; m[f] = min(Ibg)
@@ -668,20 +585,14 @@ static int thr_plan(int count, int H, int W, int batch, bool host, ThrPlan& p)
     if (count < 1 || H < 1 || W < 1 || batch < 0 || H > 65536 || W > 65536) return WASS_ERR_INVALID_ARG;
     const size_t HW = (size_t)H * W;
     if (HW > 0x7fffff00u) return WASS_ERR_UNSUPPORTED;
-    int b = batch ? batch : RAD_DEFAULT_BATCH;
-    if (b > count) b = count;
-    if (b > RAD_MAX_BATCH) b = RAD_MAX_BATCH;
-    p.head_bytes = rad_align((size_t)count * THR_WORDS * 4) + 2 * rad_align((size_t)count * 4) + rad_align((size_t)count * (THR_BINS + 1) * 4) +
-                   rad_align((size_t)count * THR_BINS * 4);
-    for (;; b /= 2) {
-        if (b < 1) return WASS_ERR_NO_MEMORY;
-        p.stage_bytes = host ? rad_align((size_t)b * HW * 4) : 0;
-        p.mask_bytes = host ? rad_align((size_t)b * HW) : 0;
-        p.total = p.head_bytes + 2 * p.stage_bytes + p.mask_bytes;
-        if (p.total <= RAD_SCRATCH_CAP) break;
-    }
-    p.batch = b;
-    return WASS_OK;
+    p.head_bytes = align256((size_t)count * THR_WORDS * 4) + 2 * align256((size_t)count * 4) + align256((size_t)count * (THR_BINS + 1) * 4) +
+                   align256((size_t)count * THR_BINS * 4);
+    p.batch = fit_batch(batch, RAD_DEFAULT_BATCH, RAD_MAX_BATCH, count, RAD_SCRATCH_CAP, [&](int b) {
+        p.stage_bytes = host ? align256((size_t)b * HW * 4) : 0;
+        p.mask_bytes = host ? align256((size_t)b * HW) : 0;
+        return p.total = p.head_bytes + 2 * p.stage_bytes + p.mask_bytes;
+    });
+    return p.batch ? WASS_OK : WASS_ERR_NO_MEMORY;
 }
 
 enum ThrMode { THR_RANGE, THR_HIST, THR_MASK };
@@ -711,18 +622,17 @@ static int thr_run(wass_ctx* c, bool host, ThrMode mode, const float* I, size_t 
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
     const size_t HW = (size_t)H * W, n = (size_t)count;
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the threshold scratch failed", p.total);
-    char* q = mem;
-    unsigned* rec = (unsigned*)q;       q += rad_align(n * THR_WORDS * 4);
-    float* dm = (float*)q;              q += rad_align(n * 4);
-    float* dthr = (float*)q;            q += rad_align(n * 4);
-    float* dedges = (float*)q;          q += rad_align(n * (THR_BINS + 1) * 4);
-    unsigned* dcounts = (unsigned*)q;   q += rad_align(n * THR_BINS * 4);
-    float* sI = (float*)q;              q += p.stage_bytes;
-    float* sB = (float*)q;              q += p.stage_bytes;
-    unsigned char* smask = (unsigned char*)q;
-    hipError_t e = hipMemsetAsync(mem, 0, p.head_bytes, s);
+    Arena mem;
+    if ((rc = mem.reserve(c, p.total, "the threshold scratch"))) return rc;
+    unsigned* rec = mem.take<unsigned>(n * THR_WORDS * 4);
+    float* dm = mem.take<float>(n * 4);
+    float* dthr = mem.take<float>(n * 4);
+    float* dedges = mem.take<float>(n * (THR_BINS + 1) * 4);
+    unsigned* dcounts = mem.take<unsigned>(n * THR_BINS * 4);
+    float* sI = mem.take<float>(p.stage_bytes);
+    float* sB = mem.take<float>(p.stage_bytes);
+    unsigned char* smask = mem.take<unsigned char>(p.mask_bytes);
+    hipError_t e = hipMemsetAsync(rec, 0, p.head_bytes, s);   // the head: everything before the staging
     if (e == hipSuccess && mode != THR_RANGE) e = hipMemcpyAsync(dm, io.m_in, n * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && mode == THR_HIST) e = hipMemcpyAsync(dedges, io.edges, n * (THR_BINS + 1) * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && mode == THR_MASK) e = hipMemcpyAsync(dthr, io.thr, n * 4, hipMemcpyHostToDevice, s);
@@ -734,10 +644,8 @@ static int thr_run(wass_ctx* c, bool host, ThrMode mode, const float* I, size_t 
         long long it = (long long)ist, iy = (long long)isy, bt = (long long)bst, by = (long long)bsy;
         unsigned char* m = io.mask ? io.mask + (size_t)t0 * HW : nullptr;
         if (host) {
-            for (int t = 0; t < nb && e == hipSuccess; ++t) {
-                e = hipMemcpy2DAsync(sI + t * HW, (size_t)W * 4, pi + t * ist, isy * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipMemcpy2DAsync(sB + t * HW, (size_t)W * 4, pb + t * bst, bsy * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, s);
-            }
+            e = upload_rows(sI, pi, 4, nb, 0, H, W, ist, isy, s);
+            if (e == hipSuccess) e = upload_rows(sB, pb, 4, nb, 0, H, W, bst, bsy, s);
             if (e != hipSuccess) break;
             pi = sI; pb = sB; it = bt = (long long)HW; iy = by = W; m = smask;
         }
@@ -753,10 +661,7 @@ static int thr_run(wass_ctx* c, bool host, ThrMode mode, const float* I, size_t 
         e = hipGetLastError();
         if (e == hipSuccess && host && mode == THR_MASK) e = hipMemcpyAsync(io.mask + (size_t)t0 * HW, smask, (size_t)nb * HW, hipMemcpyDeviceToHost, s);
     }
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "radiance threshold: %s", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);                            // the scratch is freed below
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "radiance threshold: %s", hipGetErrorString(e));
+    rc = finish(c, WASS_OK, e, s, "radiance threshold");
     if (!rc && mode == THR_RANGE) {
         std::vector<unsigned> r(n * THR_WORDS);
         e = hipMemcpy(r.data(), rec, n * THR_WORDS * 4, hipMemcpyDeviceToHost);
@@ -764,9 +669,9 @@ static int thr_run(wass_ctx* c, bool host, ThrMode mode, const float* I, size_t 
         else
             for (size_t t = 0; t < n; ++t) {
                 const unsigned* w = &r[t * THR_WORDS];
-                io.m_out[t] = w[4] ? NAN : thr_unkey(~w[0]);
-                io.lo[t] = w[1] ? thr_unkey(~w[1]) : NAN;   // no finite cell at all: there is no range
-                io.hi[t] = w[2] ? thr_unkey(w[2]) : NAN;
+                io.m_out[t] = w[4] ? NAN : order_unkey(~w[0]);
+                io.lo[t] = w[1] ? order_unkey(~w[1]) : NAN;   // no finite cell at all: there is no range
+                io.hi[t] = w[2] ? order_unkey(w[2]) : NAN;
                 io.nonfinite[t] = w[3];
             }
     }
@@ -774,7 +679,6 @@ static int thr_run(wass_ctx* c, bool host, ThrMode mode, const float* I, size_t 
         e = hipMemcpy(io.counts, dcounts, n * THR_BINS * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "radiance threshold: %s", hipGetErrorString(e));
     }
-    (void)hipFree(mem);
     return rc;
 }
 

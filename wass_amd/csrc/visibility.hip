@@ -16,8 +16,11 @@
 // addresses do not depend on the heights, only the end of the ray does.  A ray is dropped, not occluded, when it leaves the
 // grid or rises above the frame's maximum (p2 only grows); NaN fails every comparison, so a NaN cell never occludes and its
 // own ray is dropped at once.  The loop is bounded by max(H, W) steps whatever the input.
-// The only atomics are integer ones (a maximum of order-preserving keys, counts): the same input gives the same bits.
+// The only atomics are integer ones (a maximum of order-preserving keys, cube.h's, and counts): the same input gives the same bits.
+// Host side: vis_plan keeps the byte formula; the batch rule, the scratch, the staging of a host batch and the end of a call are
+// cube.h's.
 #include "common.h"
+#include "cube.h"
 #include "surface.h"     // vis_slope: shared with polarimetric.hip
 
 namespace wass {
@@ -28,42 +31,8 @@ constexpr int VIS_DEFAULT_BATCH = 8;
 constexpr int VIS_U = 4;                                // steps whose heights are loaded ahead of the comparisons
 constexpr int VIS_BX = 64, VIS_BY = 4;                  // a block: 4 waves, each 64 cells of one row
 
-// an unsigned key that orders like the double it was made from; no finite value has key 0, which stands for "nothing seen"
-__device__ __forceinline__ unsigned long long vis_key(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double vis_unkey(unsigned long long k)
-{
-    if (!k) return -INFINITY;
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-__device__ __forceinline__ unsigned long long vis_wave_max(unsigned long long k)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(k, o, 64);
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
-// the block's largest key to *dst; every thread of the block calls it
-__device__ __forceinline__ void vis_block_max(unsigned long long k, unsigned long long* dst)
-{
-    __shared__ unsigned long long part[VIS_BY];
-    k = vis_wave_max(k);
-    if (threadIdx.x == 0) part[threadIdx.y] = k;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-#pragma unroll
-        for (int w = 1; w < VIS_BY; ++w) k = part[w] > k ? part[w] : k;
-        if (k) atomicMax(dst, k);
-    }
-}
+// the frame's largest height from its key (cube.h's order_key); key 0, nothing seen, stands for minus infinity
+__device__ __forceinline__ double vis_top(unsigned long long k) { return k ? order_unkey(k) : -INFINITY; }
 
 // d = -(r / |r|), r = cell - camera: the unit direction from the cell to the camera, numpy's operations in numpy's order
 __device__ __forceinline__ void vis_ray(double x, double y, double z, double o0, double o1, double o2, double& d0, double& d1, double& d2)
@@ -132,7 +101,7 @@ __global__ void __launch_bounds__(VIS_BX * VIS_BY) k_vis_prepass(const float* __
         const size_t c = (size_t)i * W + j;
         const double zc = (double)zf / g.dx;
         Zc[f * HW + c] = zc;
-        if (fabs(zc) <= 1.7976931348623157e308) key = vis_key(zc);      // finite
+        if (fabs(zc) <= 1.7976931348623157e308) key = order_key(zc);      // finite
         const double sx = vis_slope(zl, zf, zr, j == 0, j == W - 1, g.dx);
         const double sy_ = vis_slope(zu, zf, zd, i == 0, i == H - 1, g.dy);
         const double nn = sqrt((sx * sx + sy_ * sy_) + 1.0);
@@ -146,7 +115,7 @@ __global__ void __launch_bounds__(VIS_BX * VIS_BY) k_vis_prepass(const float* __
     }
     const unsigned long long wave_up = __ballot(up);
     if (wave_up && threadIdx.x == 0) atomicAdd(notup, (unsigned long long)__popcll(wave_up));
-    vis_block_max(key, keys + f);
+    block_max<VIS_BY>(key, keys + f);
 }
 
 __global__ void __launch_bounds__(VIS_BX * VIS_BY) k_vis_march(const float* __restrict__ Z, long long st, long long sy, int H, int W, const VisGeom g,
@@ -167,7 +136,7 @@ __global__ void __launch_bounds__(VIS_BX * VIS_BY) k_vis_march(const float* __re
             if (d2 > 0.0) {
                 const double a0 = fabs(d0), a1 = fabs(d1);
                 const double m = a0 > a1 ? a0 : a1;     // 0 under the camera: the step is not a number and the ray is dropped
-                occluded = vis_march(plane, H, W, i, j, plane[c], d0 / m, d1 / m, d2 / m, vis_unkey(keys[f]), nmax);
+                occluded = vis_march(plane, H, W, i, j, plane[c], d0 / m, d1 / m, d2 / m, vis_top(keys[f]), nmax);
                 if (occluded) mask[f * HW + c] = 1;
             }
         }
@@ -186,12 +155,12 @@ __global__ void __launch_bounds__(VIS_BX * VIS_BY) k_occ_prepass(const double* _
     if (i < H && j < W) {
         const size_t c = (size_t)i * W + j;
         const double z = ZZ[c];
-        if (fabs(z) <= 1.7976931348623157e308) k = vis_key(z);
+        if (fabs(z) <= 1.7976931348623157e308) k = order_key(z);
         bad = !(rays[3 * c + 2] > 0.0);                 // "rays must go upward"
     }
     const unsigned long long wave_bad = __ballot(bad);
     if (wave_bad && threadIdx.x == 0) atomicAdd(notup, (unsigned long long)__popcll(wave_bad));
-    vis_block_max(k, key);
+    block_max<VIS_BY>(k, key);
 }
 
 __global__ void __launch_bounds__(VIS_BX * VIS_BY) k_occ_march(const double* __restrict__ ZZ, const double* __restrict__ rays, int H, int W,
@@ -207,12 +176,10 @@ __global__ void __launch_bounds__(VIS_BX * VIS_BY) k_occ_march(const double* __r
         const double a0 = fabs(r0), a1 = fabs(r1);
         const double m = a0 > a1 ? a0 : a1;
         const double s1 = r1 / m;
-        occluded = vis_march(ZZ, H, W, i, j, ZZ[c], r0 / m, invert_y ? -s1 : s1, r2 / m, vis_unkey(*key), nmax);
+        occluded = vis_march(ZZ, H, W, i, j, ZZ[c], r0 / m, invert_y ? -s1 : s1, r2 / m, vis_top(*key), nmax);
     }
     mask[c] = occluded ? 1 : 0;
 }
-
-static size_t vis_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct VisPlan {
     int batch = 0;                 // frames per launch
@@ -226,22 +193,16 @@ static int vis_plan(int count, int H, int W, int batch, bool host, VisPlan& p)
     if (count < 1 || H < 2 || W < 2 || batch < 0 || H > 65536 || W > 65536) return WASS_ERR_INVALID_ARG;
     const size_t HW = (size_t)H * W;
     if (HW > 0x7fffff00u) return WASS_ERR_UNSUPPORTED;
-    int b = batch ? batch : VIS_DEFAULT_BATCH;
-    if (b > count) b = count;
-    if (b > VIS_MAX_BATCH) b = VIS_MAX_BATCH;
-    p.head_bytes = vis_align((size_t)count * 8) + vis_align((size_t)count * 4) + 256;
-    p.grid_bytes = host ? 2 * vis_align(HW * 8) : 0;
-    for (;; b /= 2) {
-        if (b < 1) return WASS_ERR_NO_MEMORY;
-        p.zc_bytes = vis_align((size_t)b * HW * 8);
-        p.stage_bytes = host ? vis_align((size_t)b * HW * 4) : 0;
-        p.mask_bytes = host ? vis_align((size_t)b * HW) : 0;
-        p.ang_bytes = host ? vis_align((size_t)b * HW * 4) : 0;
-        p.total = p.head_bytes + p.grid_bytes + p.zc_bytes + p.stage_bytes + p.mask_bytes + p.ang_bytes;
-        if (p.total <= VIS_SCRATCH_CAP) break;
-    }
-    p.batch = b;
-    return WASS_OK;
+    p.head_bytes = align256((size_t)count * 8) + align256((size_t)count * 4) + 256;
+    p.grid_bytes = host ? 2 * align256(HW * 8) : 0;
+    p.batch = fit_batch(batch, VIS_DEFAULT_BATCH, VIS_MAX_BATCH, count, VIS_SCRATCH_CAP, [&](int b) {
+        p.zc_bytes = align256((size_t)b * HW * 8);
+        p.stage_bytes = host ? align256((size_t)b * HW * 4) : 0;
+        p.mask_bytes = host ? align256((size_t)b * HW) : 0;
+        p.ang_bytes = host ? align256((size_t)b * HW * 4) : 0;
+        return p.total = p.head_bytes + p.grid_bytes + p.zc_bytes + p.stage_bytes + p.mask_bytes + p.ang_bytes;
+    });
+    return p.batch ? WASS_OK : WASS_ERR_NO_MEMORY;
 }
 
 static int vis_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy, int count, int H, int W, const double* XX, const double* YY,
@@ -274,19 +235,18 @@ static int vis_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy
     g.limit = angle_limit;
     g.scale = (float)datascale;
     const size_t HW = (size_t)H * W;
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the visibility scratch failed", p.total);
-    char* q = mem;
-    unsigned long long* keys = (unsigned long long*)q;      q += vis_align((size_t)count * 8);
-    unsigned* counts = (unsigned*)q;                        q += vis_align((size_t)count * 4);
-    unsigned long long* notup = (unsigned long long*)q;     q += 256;
-    double* dXX = (double*)q;                               q += p.grid_bytes / 2;
-    double* dYY = (double*)q;                               q += p.grid_bytes / 2;
-    double* Zc = (double*)q;                                q += p.zc_bytes;
-    float* stage = (float*)q;                               q += p.stage_bytes;
-    unsigned char* dmask = (unsigned char*)q;               q += p.mask_bytes;
-    float* dang = (float*)q;
-    hipError_t e = hipMemsetAsync(mem, 0, p.head_bytes, s);
+    Arena mem;
+    if ((rc = mem.reserve(c, p.total, "the visibility scratch"))) return rc;
+    unsigned long long* keys = mem.take<unsigned long long>((size_t)count * 8);
+    unsigned* counts = mem.take<unsigned>((size_t)count * 4);
+    unsigned long long* notup = mem.take<unsigned long long>(256);
+    double* dXX = mem.take<double>(p.grid_bytes / 2);
+    double* dYY = mem.take<double>(p.grid_bytes / 2);
+    double* Zc = mem.take<double>(p.zc_bytes);
+    float* stage = mem.take<float>(p.stage_bytes);
+    unsigned char* dmask = mem.take<unsigned char>(p.mask_bytes);
+    float* dang = mem.take<float>(p.ang_bytes);
+    hipError_t e = hipMemsetAsync(keys, 0, p.head_bytes, s);   // the head: keys, counts and the not-upward count
     if (e == hipSuccess && host) {
         e = hipMemcpyAsync(dXX, XX, HW * 8, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(dYY, YY, HW * 8, hipMemcpyHostToDevice, s);
@@ -304,8 +264,7 @@ static int vis_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy
         unsigned char* m = mask + (size_t)t0 * HW;
         float* a = angles + (size_t)t0 * HW;
         if (host) {
-            for (int t = 0; t < nb && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(stage + t * HW, (size_t)W * 4, zin + t * st, sy * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, s);
+            e = upload_rows(stage, zin, 4, nb, 0, H, W, st, sy, s);
             if (e != hipSuccess) break;
             zin = stage; zst = (long long)HW; zsy = W; m = dmask; a = dang;
         }
@@ -318,9 +277,7 @@ static int vis_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy
             if (e == hipSuccess) e = hipMemcpyAsync(angles + (size_t)t0 * HW, dang, (size_t)nb * HW * 4, hipMemcpyDeviceToHost, s);
         }
     }
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "visibility map: %s", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);                            // the scratch is freed below
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "visibility map: %s", hipGetErrorString(e));
+    rc = finish(c, WASS_OK, e, s, "visibility map");
     if (!rc) {
         std::vector<unsigned> n((size_t)count);
         unsigned long long up = 0;
@@ -332,7 +289,6 @@ static int vis_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy
             if (not_upward) *not_upward = up;
         }
     }
-    (void)hipFree(mem);
     return rc;
 }
 
@@ -345,24 +301,23 @@ static int occ_run(wass_ctx* c, bool host, const double* ZZ, const double* rays,
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
     const size_t HW = (size_t)H * W;
-    const size_t total = 256 + (host ? vis_align(HW * 8) + vis_align(HW * 24) + vis_align(HW) : 0);
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the occlusion scratch failed", total);
-    unsigned long long* key = (unsigned long long*)mem;
+    Arena mem;
+    int rc = mem.reserve(c, 256 + (host ? align256(HW * 8) + align256(HW * 24) + align256(HW) : 0), "the occlusion scratch");
+    if (rc) return rc;
+    unsigned long long* key = mem.take<unsigned long long>(256);
     unsigned long long* notup = key + 1;
     const double* dZ = ZZ;
     const double* dR = rays;
     unsigned char* dM = mask;
-    hipError_t e = hipMemsetAsync(mem, 0, 256, s);
+    hipError_t e = hipMemsetAsync(key, 0, 256, s);
     if (host) {
-        double* z = (double*)(mem + 256);
-        double* r = (double*)(mem + 256 + vis_align(HW * 8));
-        dM = (unsigned char*)(mem + 256 + vis_align(HW * 8) + vis_align(HW * 24));
+        double* z = mem.take<double>(HW * 8);
+        double* r = mem.take<double>(HW * 24);
+        dM = mem.take<unsigned char>(HW);
         if (e == hipSuccess) e = hipMemcpyAsync(z, ZZ, HW * 8, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(r, rays, HW * 24, hipMemcpyHostToDevice, s);
         dZ = z; dR = r;
     }
-    int rc = WASS_OK;
     if (e == hipSuccess) {
         const dim3 block(VIS_BX, VIS_BY), grid((W + VIS_BX - 1) / VIS_BX, (H + VIS_BY - 1) / VIS_BY);
         hipLaunchKernelGGL(k_occ_prepass, grid, block, 0, s, dZ, dR, H, W, key, notup);
@@ -370,14 +325,11 @@ static int occ_run(wass_ctx* c, bool host, const double* ZZ, const double* rays,
         e = hipGetLastError();
         if (e == hipSuccess && host) e = hipMemcpyAsync(mask, dM, HW, hipMemcpyDeviceToHost, s);
     }
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "occlusion mask: %s", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "occlusion mask: %s", hipGetErrorString(e));
+    rc = finish(c, WASS_OK, e, s, "occlusion mask");
     if (!rc && not_upward) {
         e = hipMemcpy(not_upward, notup, 8, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "occlusion mask: %s", hipGetErrorString(e));
     }
-    (void)hipFree(mem);
     return rc;
 }
 

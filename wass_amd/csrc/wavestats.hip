@@ -17,7 +17,10 @@
 // 2 * (count / 2) doubles per series.  Rows go in slabs so that it, and the staging of a host cube and of its results, stay under
 // WS_SCRATCH_CAP; a series never crosses a slab, so the result does not depend on the slab height.  No atomics but the
 // histogram's integer ones.
+// Host side: ws_plan keeps the byte formula; the slab rule, the scratch, the staging of a host slab and the end of the call are
+// cube.h's.
 #include "common.h"
+#include "cube.h"
 
 #include <math.h>
 
@@ -159,7 +162,7 @@ __global__ void __launch_bounds__(256) k_ws_scan(const float* __restrict__ x, lo
 
 // H_k > 0 in a series of finite samples (a wave's span begins at or above zero and ends below), so its bits, taken as an
 // unsigned integer, order like its value
-__device__ __forceinline__ unsigned long long ws_key(double h) { return (unsigned long long)__double_as_longlong(h); }
+__device__ __forceinline__ unsigned long long ws_bits(double h) { return (unsigned long long)__double_as_longlong(h); }
 
 __global__ void __launch_bounds__(256) k_ws_select(unsigned nser, const int* __restrict__ ncr, const double* __restrict__ wh,
                                                    const double* __restrict__ wt, double* __restrict__ fields, size_t fpitch,
@@ -190,7 +193,7 @@ __global__ void __launch_bounds__(256) k_ws_select(unsigned nser, const int* __r
 #pragma unroll
             for (int d = 0; d < 16; ++d) cnt[d][tid] = 0;
             for (unsigned k = 0; k < nw; ++k) {
-                const unsigned long long key = ws_key(hs[(size_t)k * nser]);
+                const unsigned long long key = ws_bits(hs[(size_t)k * nser]);
                 if (shift == 60 || (key >> (shift + 4)) == (cut >> (shift + 4))) ++cnt[(unsigned)(key >> shift) & 15u][tid];
             }
             int d = 15;
@@ -205,7 +208,7 @@ __global__ void __launch_bounds__(256) k_ws_select(unsigned nser, const int* __r
         double sh = 0.0, st = 0.0;
         for (unsigned k = 0; k < nw; ++k) {
             const double h = hs[(size_t)k * nser];
-            const unsigned long long key = ws_key(h);
+            const unsigned long long key = ws_bits(h);
             bool take = key > cut;
             if (key == cut && want) { take = true; --want; }
             if (take) {
@@ -237,30 +240,22 @@ struct WsPlan {
     size_t wave_bytes = 0, stage_bytes = 0, field_bytes = 0, ncr_bytes = 0, hist_bytes = 0, total = 0;
 };
 
-static size_t ws_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // 0, or why the problem cannot be planned.  The device form needs the waves alone: its results go where the caller says.
-static int ws_plan(int count, int H, int W, int slab_rows, bool host, int hist_bins, WsPlan& p)
+static int ws_plan(int count, int H, int W, int slab, bool host, int hist_bins, WsPlan& p)
 {
-    if (count < 1 || H < 1 || W < 1 || slab_rows < 0 || hist_bins < 0) return WASS_ERR_INVALID_ARG;
+    if (count < 1 || H < 1 || W < 1 || slab < 0 || hist_bins < 0) return WASS_ERR_INVALID_ARG;
     const size_t nslot = (size_t)count / 2;
     const size_t per_row = (2 * nslot * 8 + (host ? (size_t)count * 4 + WS_NF * 8 + 4 : 0)) * (size_t)W;
-    const size_t fixed = 2048 + (host ? ws_align((size_t)hist_bins * 8) : 0);   // 2048: what aligning the parts may add
+    const size_t fixed = 2048 + (host ? align256((size_t)hist_bins * 8) : 0);   // 2048: what aligning the parts may add
     if (fixed >= WS_SCRATCH_CAP) return WASS_ERR_NO_MEMORY;
-    size_t rows = per_row ? (WS_SCRATCH_CAP - fixed) / per_row : (size_t)H;
-    if (rows < 1) return WASS_ERR_NO_MEMORY;
-    const size_t most = 0x7fffff00u / (size_t)W;         // the series of a slab are indexed with 32 bits
-    if (rows > most) rows = most;
-    if (rows > (size_t)H) rows = (size_t)H;
-    if (slab_rows > 0 && rows > (size_t)slab_rows) rows = (size_t)slab_rows;
-    if (rows < 1) return WASS_ERR_UNSUPPORTED;
-    const size_t nser = rows * (size_t)W;
-    p.rows = (int)rows;
-    p.wave_bytes = ws_align(2 * nslot * nser * 8);
-    p.stage_bytes = host ? ws_align((size_t)count * nser * 4) : 0;
-    p.field_bytes = host ? ws_align((size_t)WS_NF * nser * 8) : 0;
-    p.ncr_bytes = host ? ws_align(nser * 4) : 0;
-    p.hist_bytes = host ? ws_align((size_t)hist_bins * 8) : 0;
+    const int rc = slab_rows(WS_SCRATCH_CAP - fixed, per_row, H, W, slab, &p.rows);
+    if (rc) return rc;
+    const size_t nser = (size_t)p.rows * (size_t)W;
+    p.wave_bytes = align256(2 * nslot * nser * 8);
+    p.stage_bytes = host ? align256((size_t)count * nser * 4) : 0;
+    p.field_bytes = host ? align256((size_t)WS_NF * nser * 8) : 0;
+    p.ncr_bytes = host ? align256(nser * 4) : 0;
+    p.hist_bytes = host ? align256((size_t)hist_bins * 8) : 0;
     p.total = p.wave_bytes + p.stage_bytes + p.field_bytes + p.ncr_bytes + p.hist_bytes;
     if (p.total == 0) p.total = 256;                     // count = 1 on the device: no waves, nothing staged
     return WASS_OK;
@@ -303,14 +298,14 @@ static int ws_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy,
     if (sy < (size_t)W || (count > 1 && st < (size_t)W)) return set_err(c, WASS_ERR_INVALID_ARG, "bad strides");
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, p.total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the wave statistics failed", p.total);
-    const size_t nslot = (size_t)count / 2, HW = (size_t)H * W, rowb = (size_t)W * 4;
-    double* wh = (double*)mem;
-    float* stage = (float*)(mem + p.wave_bytes);
-    double* sfields = (double*)(mem + p.wave_bytes + p.stage_bytes);
-    int* sncr = (int*)(mem + p.wave_bytes + p.stage_bytes + p.field_bytes);
-    unsigned long long* dhist = host ? (unsigned long long*)(mem + p.wave_bytes + p.stage_bytes + p.field_bytes + p.ncr_bytes) : hist;
+    Arena mem;
+    if ((rc = mem.reserve(c, p.total, "the wave statistics"))) return rc;
+    const size_t nslot = (size_t)count / 2, HW = (size_t)H * W;
+    double* wh = mem.take<double>(p.wave_bytes);
+    float* stage = mem.take<float>(p.stage_bytes);
+    double* sfields = mem.take<double>(p.field_bytes);
+    int* sncr = mem.take<int>(p.ncr_bytes);
+    unsigned long long* dhist = host ? mem.take<unsigned long long>(p.hist_bytes) : hist;
     hipError_t e = hipSuccess;
     if (hist_bins > 0) e = hipMemsetAsync(dhist, 0, (size_t)hist_bins * 8, s);
     for (int r0 = 0; r0 < H && e == hipSuccess; r0 += p.rows) {
@@ -319,8 +314,7 @@ static int ws_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy,
         const unsigned nser = (unsigned)plane;
         double* wt = wh + nslot * plane;
         if (host) {
-            for (int t = 0; t < count && e == hipSuccess; ++t)
-                e = hipMemcpy2DAsync(stage + t * plane, rowb, in + t * st + (size_t)r0 * sy, sy * 4, rowb, rows, hipMemcpyHostToDevice, s);
+            e = upload_rows(stage, in, 4, count, r0, rows, W, st, sy, s);
             if (e != hipSuccess) break;
             ws_launch(s, stage, (long long)plane, W, W, nser, count, datascale, dt, crossing == WASS_WS_DOWN, demean != 0, sfields, plane, sncr, wh, wt,
                       dhist, hist_bins, hist_width);
@@ -335,12 +329,7 @@ static int ws_run(wass_ctx* c, bool host, const float* in, size_t st, size_t sy,
         }
     }
     if (host && hist_bins > 0 && e == hipSuccess) e = hipMemcpyAsync(hist, dhist, (size_t)hist_bins * 8, hipMemcpyDeviceToHost, s);
-    rc = WASS_OK;
-    if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "wave statistics: %s", hipGetErrorString(e));
-    e = hipStreamSynchronize(s);                         // the scratch is freed below
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "wave statistics: %s", hipGetErrorString(e));
-    (void)hipFree(mem);
-    return rc;
+    return finish(c, WASS_OK, e, s, "wave statistics");
 }
 
 }  // namespace wass

@@ -339,14 +339,21 @@ def sosfilt_zi(sos) -> np.ndarray:
     return zi
 
 
+def _scratch_bytes(name: str, args, shown: str):
+    """(bytes, frames per launch or rows per slab) as the library's pure wass_<name>_scratch_bytes plans them; its refusal is a
+    ValueError that shows the call"""
+    from . import _lib
+    b, n = C.c_size_t(), C.c_int()
+    rc = getattr(_lib.load(), f"wass_{name}_scratch_bytes")(*args, C.byref(b), C.byref(n))
+    if rc:
+        raise ValueError(f"wass_{name}_scratch_bytes({shown}): error {rc}")
+    return b.value, n.value
+
+
 def sosfiltfilt_scratch_bytes(count: int, H: int, W: int, padlen: int, slab_rows: int = 0, host: bool = True):
     """(bytes of device scratch, rows per slab) of one sosfiltfilt call; no GPU needed."""
-    from . import _lib
-    b, r = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_sosfiltfilt_scratch_bytes(int(count), int(H), int(W), int(padlen), int(slab_rows), int(bool(host)), C.byref(b), C.byref(r))
-    if rc:
-        raise ValueError(f"wass_sosfiltfilt_scratch_bytes({count}, {H}, {W}, padlen {padlen}): error {rc}")
-    return b.value, r.value
+    return _scratch_bytes("sosfiltfilt", (int(count), int(H), int(W), int(padlen), int(slab_rows), int(bool(host))),
+                          f"{count}, {H}, {W}, padlen {padlen}")
 
 
 def _is_device(a) -> bool:
@@ -360,6 +367,54 @@ def _host_f32_rows(a) -> np.ndarray:
             or a.strides[0] <= 0 or a.strides[1] <= 0:
         a = np.ascontiguousarray(a, np.float32)
     return a
+
+
+def _ptr_strides(a):
+    """(pointer, stride_t, stride_y in elements) of a cube on either side"""
+    if _is_device(a):
+        return a.data_ptr(), a.stride(0), a.stride(1)
+    return a.ctypes.data, a.strides[0] // a.itemsize, a.strides[1] // a.itemsize
+
+
+def _cube_io(data, outs, what, dtypes=("float32",), shape=None, dense=False, alias=True):
+    """A float32 cube and the outputs of an operator on it, all on one side: (data, outs, suffix, a).  `data` comes back as the
+    library takes it, converted or copied only where its dtype or strides demand it.  outs[k] is the caller's, checked, or a new
+    one where the caller gave None: of dtypes[k] and `shape` (default: the cube's); contiguous if `dense`, else with a contiguous
+    last axis and positive whole strides (_ptr_strides gives them); with alias=False it must not share memory with the cube.
+    suffix is "_dev" for device tensors, whose current stream is synchronised here (the library runs on streams of its own), and
+    "" for host arrays.  a = (pointer, stride_t, stride_y, count, H, W) of the cube."""
+    if len(data.shape) != 3:
+        raise ValueError("data must be count x H x W")
+    count, H, W = (int(v) for v in data.shape)
+    shape = (count, H, W) if shape is None else tuple(shape)
+    dev = _is_device(data)
+    if dev:
+        import torch
+        lib, side = torch, "device tensor"
+        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
+            data = data.to(torch.float32).contiguous()
+    else:
+        lib, side = np, "host array"
+        data = _host_f32_rows(data)
+    outs = list(outs)
+    for k, (o, name) in enumerate(zip(outs, dtypes)):
+        dt = getattr(lib, name)
+        if o is None:
+            outs[k] = torch.empty(shape, dtype=dt, device=data.device) if dev else np.empty(shape, dt)
+            continue
+        if dev:
+            ok = _is_device(o) and tuple(o.shape) == shape and o.dtype == dt and (alias or o.data_ptr() != data.data_ptr()) \
+                and (o.is_contiguous() if dense else o.stride(2) == 1 and o.stride(0) > 0 and o.stride(1) > 0)
+        else:
+            ok = isinstance(o, np.ndarray) and o.shape == shape and o.dtype == dt and (alias or not np.shares_memory(o, data)) \
+                and (o.flags.c_contiguous if dense else o.strides[2] == o.itemsize and min(o.strides) > 0
+                     and not (o.strides[0] % o.itemsize or o.strides[1] % o.itemsize))
+        if not ok:
+            raise ValueError(f"{what}: an output must be {'a' if alias else 'another'} {name} {side} of shape {shape}, "
+                             + ("contiguous" if dense else "with a contiguous last axis"))
+    if dev:
+        torch.cuda.current_stream(data.device).synchronize()
+    return data, outs, "_dev" if dev else "", (*_ptr_strides(data), count, H, W)
 
 
 def sosfiltfilt(sos, data, remove_mean: bool = False, ctx: Context | None = None, out=None, slab_rows: int = 0):
@@ -381,27 +436,10 @@ def sosfiltfilt(sos, data, remove_mean: bool = False, ctx: Context | None = None
     if ctx is None:
         ctx = Context(0)
     args = (sos.ctypes.data, sos.shape[0], zi.ctypes.data, padlen, int(bool(remove_mean)), int(slab_rows))
-    if _is_device(data):
-        import torch
-        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
-            data = data.to(torch.float32).contiguous()
-        if out is None:
-            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
-        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or out.stride(2) != 1:
-            raise ValueError("out must be a float32 device tensor of the input's shape with a contiguous last axis")
-        torch.cuda.current_stream(data.device).synchronize()
-        ctx._check(ctx._lib.wass_sosfiltfilt_dev(ctx._h, data.data_ptr(), data.stride(0), data.stride(1), count, H, W, *args,
-                                                 out.data_ptr(), out.stride(0), out.stride(1)))
+    data, (out,), suffix, a = _cube_io(data, (out,), "sosfiltfilt")
+    ctx._check(getattr(ctx._lib, "wass_sosfiltfilt" + suffix)(ctx._h, *a, *args, *_ptr_strides(out)))
+    if suffix:
         ctx.synchronize()
-        return out
-    src = _host_f32_rows(data)
-    if out is None:
-        out = np.empty((count, H, W), np.float32)
-    elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or out.strides[2] != 4 \
-            or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0:
-        raise ValueError("out must be a float32 host array of the input's shape with a contiguous last axis")
-    ctx._check(ctx._lib.wass_sosfiltfilt(ctx._h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W, *args,
-                                         out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4))
     return out
 
 
@@ -464,29 +502,11 @@ class Spatial2DButterworth:
             raise ValueError(f"frames of shape {tuple(frames.shape)}, expected n x {self.rows} x {self.cols}")
         n = int(frames.shape[0])
         h, ctx = self._handle(), self._ctx
-        if _is_device(frames):
-            import torch
-            if frames.dtype != torch.float32 or frames.stride(2) != 1 or frames.stride(0) <= 0 or frames.stride(1) <= 0:
-                frames = frames.to(torch.float32).contiguous()
-            if out is None:
-                out = torch.empty((n, self.rows, self.cols), dtype=torch.float32, device=frames.device)
-            elif not _is_device(out) or tuple(out.shape) != tuple(frames.shape) or out.dtype != torch.float32 or out.stride(2) != 1:
-                raise ValueError("out must be a float32 device tensor of the input's shape with a contiguous last axis")
-            if n:
-                torch.cuda.current_stream(frames.device).synchronize()
-                ctx._check(ctx._lib.wass_spatial_filter_apply_dev(h, frames.data_ptr(), frames.stride(0), frames.stride(1), n,
-                                                                  out.data_ptr(), out.stride(0), out.stride(1)))
-                ctx.synchronize()
-            return out
-        src = _host_f32_rows(frames)
-        if out is None:
-            out = np.empty((n, self.rows, self.cols), np.float32)
-        elif not isinstance(out, np.ndarray) or out.shape != src.shape or out.dtype != np.float32 or out.strides[2] != 4 \
-                or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0:
-            raise ValueError("out must be a float32 host array of the input's shape with a contiguous last axis")
+        frames, (out,), suffix, a = _cube_io(frames, (out,), "apply_batch")
         if n:
-            ctx._check(ctx._lib.wass_spatial_filter_apply(h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, n,
-                                                          out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4))
+            ctx._check(getattr(ctx._lib, "wass_spatial_filter_apply" + suffix)(h, *a[:3], n, *_ptr_strides(out)))
+            if suffix:
+                ctx.synchronize()
         return out
 
     def apply(self, surface):
@@ -552,12 +572,7 @@ def compute_slope_and_normals(XX, YY, ZZ):
 
 def visibility_scratch_bytes(count: int, H: int, W: int, batch: int = 8, host: bool = True):
     """(bytes of device scratch, frames per launch) of one visibility_map call; no GPU needed."""
-    from . import _lib
-    b, n = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_visibility_scratch_bytes(int(count), int(H), int(W), int(batch), int(bool(host)), C.byref(b), C.byref(n))
-    if rc:
-        raise ValueError(f"wass_visibility_scratch_bytes({count}, {H}, {W}, batch {batch}): error {rc}")
-    return b.value, n.value
+    return _scratch_bytes("visibility", (int(count), int(H), int(W), int(batch), int(bool(host))), f"{count}, {H}, {W}, batch {batch}")
 
 
 def _check_grid(XX, YY, H: int, W: int):
@@ -601,32 +616,13 @@ def visibility_map(data, XX, YY, cam_to_grid, datascale: float = 1e-3, angle_lim
     counts = np.zeros(count, np.uint64)
     up = C.c_uint64()
     tail = (origin.ctypes.data, float(datascale), limit, int(batch))
+    grid = [XX, YY]
     if _is_device(data):
         import torch
-        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
-            data = data.to(torch.float32).contiguous()
-        outs = []
-        for o, dt in ((out_occlusion, torch.uint8), (out_angles, torch.float32)):
-            if o is None:
-                o = torch.empty((count, H, W), dtype=dt, device=data.device)
-            elif not _is_device(o) or tuple(o.shape) != (count, H, W) or o.dtype != dt or not o.is_contiguous():
-                raise ValueError("the outputs must be contiguous device tensors of the input's shape, uint8 and float32")
-            outs.append(o)
-        dXX, dYY = torch.from_numpy(XX).to(data.device), torch.from_numpy(YY).to(data.device)
-        torch.cuda.current_stream(data.device).synchronize()
-        ctx._check(ctx._lib.wass_visibility_dev(ctx._h, data.data_ptr(), data.stride(0), data.stride(1), count, H, W, dXX.data_ptr(),
-                                                dYY.data_ptr(), *tail, outs[0].data_ptr(), outs[1].data_ptr(), counts.ctypes.data, C.byref(up)))
-    else:
-        src = _host_f32_rows(data)
-        outs = []
-        for o, dt in ((out_occlusion, np.uint8), (out_angles, np.float32)):
-            if o is None:
-                o = np.empty((count, H, W), dt)
-            elif not isinstance(o, np.ndarray) or o.shape != (count, H, W) or o.dtype != dt or not o.flags.c_contiguous:
-                raise ValueError("the outputs must be contiguous host arrays of the input's shape, uint8 and float32")
-            outs.append(o)
-        ctx._check(ctx._lib.wass_visibility(ctx._h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W, XX.ctypes.data,
-                                            YY.ctypes.data, *tail, outs[0].ctypes.data, outs[1].ctypes.data, counts.ctypes.data, C.byref(up)))
+        grid = [torch.from_numpy(g).to(data.device) for g in grid]      # before _cube_io: it waits for the caller's stream
+    data, outs, suffix, a = _cube_io(data, (out_occlusion, out_angles), "visibility_map", ("uint8", "float32"), dense=True)
+    gp, op = ([_ptr_strides(v)[0] for v in vs] for vs in (grid, outs))
+    ctx._check(getattr(ctx._lib, "wass_visibility" + suffix)(ctx._h, *a, *gp, *tail, *op, counts.ctypes.data, C.byref(up)))
     if up.value:
         raise ValueError(f"rays must go upward: {up.value} cells lie at or above the camera")
     return outs[0], outs[1], 100.0 * counts.astype(np.float64) / float(H * W)
@@ -731,12 +727,8 @@ def workspace_images(wassdir: str, cam: int, count: int):
 
 def radiance_scratch_bytes(count: int, H: int, W: int, Ih: int, Iw: int, batch: int = 8, host: bool = True):
     """(bytes of device scratch, frames per launch) of one radiance call; no GPU needed."""
-    from . import _lib
-    b, n = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_radiance_scratch_bytes(int(count), int(H), int(W), int(Ih), int(Iw), int(batch), int(bool(host)), C.byref(b), C.byref(n))
-    if rc:
-        raise ValueError(f"wass_radiance_scratch_bytes({count}, {H}, {W}, pictures {Ih} x {Iw}, batch {batch}): error {rc}")
-    return b.value, n.value
+    return _scratch_bytes("radiance", (int(count), int(H), int(W), int(Ih), int(Iw), int(batch), int(bool(host))),
+                          f"{count}, {H}, {W}, pictures {Ih} x {Iw}, batch {batch}")
 
 
 def _radiance_chunk(ctx, imgs, data, XX, YY, dgrid, pcam, datascale, batch, out, levels=0):
@@ -802,22 +794,11 @@ def _radiance_frames(images, data, XX, YY, Pplane, datascale, levels, ctx, out, 
         _check_picture(images.shape[1:])
     if ctx is None:
         ctx = Context(0)
+    data, (out,), suffix, _ = _cube_io(data, (out,), "radiance", shape=oshape, dense=True)
     dgrid = None
-    if _is_device(data):
+    if suffix:
         import torch
-        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
-            data = data.to(torch.float32).contiguous()
-        if out is None:
-            out = torch.empty(oshape, dtype=torch.float32, device=data.device)
-        elif not _is_device(out) or tuple(out.shape) != oshape or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 device tensor of the result's shape")
-        dgrid = (torch.from_numpy(XX).to(data.device), torch.from_numpy(YY).to(data.device))
-    else:
-        data = _host_f32_rows(data)
-        if out is None:
-            out = np.empty(oshape, np.float32)
-        elif not isinstance(out, np.ndarray) or out.shape != oshape or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous float32 host array of the result's shape")
+        dgrid = (torch.from_numpy(XX).to(data.device), torch.from_numpy(YY).to(data.device))    # _radiance_chunk waits for them
     if whole:
         pcam = radiance_pcam(Pplane, int(images.shape[2]), int(images.shape[1]))
         _radiance_chunk(ctx, images, data, XX, YY, dgrid, pcam, datascale, batch, out, levels)
@@ -858,13 +839,8 @@ def pyr_up_scratch_bytes(count: int, H: int, W: int, levels: int = 1, dtype=np.f
     launch and every term rounded up to 256 bytes: the levels below the last, sum over l = 1 .. levels - 1 of b 4^l H W e, and from
     the host also the input b H W e and the result b 4^levels H W e.  b is `batch` (pyr_up itself uses 8), at most count, halved
     until the sum is at most 16 GiB."""
-    from . import _lib
-    b, n = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_pyrup_scratch_bytes(int(count), int(H), int(W), int(levels), int(np.dtype(dtype).itemsize), int(batch), int(bool(host)),
-                                              C.byref(b), C.byref(n))
-    if rc:
-        raise ValueError(f"wass_pyrup_scratch_bytes({count}, {H}, {W}, levels {levels}, {np.dtype(dtype)}, batch {batch}): error {rc}")
-    return b.value, n.value
+    return _scratch_bytes("pyrup", (int(count), int(H), int(W), int(levels), int(np.dtype(dtype).itemsize), int(batch), int(bool(host))),
+                          f"{count}, {H}, {W}, levels {levels}, {np.dtype(dtype)}, batch {batch}")
 
 
 def _device_span(t):
@@ -951,13 +927,8 @@ def radiance_upscaled_scratch_bytes(count: int, H: int, W: int, Ih: int, Iw: int
     levels = int(upscalefactor) - 1
     if levels == 0:
         return radiance_scratch_bytes(count, H, W, Ih, Iw, batch, host)
-    from . import _lib
-    b, n = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_radiance_up_scratch_bytes(int(count), int(H), int(W), int(Ih), int(Iw), levels, int(batch), int(bool(host)), C.byref(b),
-                                                    C.byref(n))
-    if rc:
-        raise ValueError(f"wass_radiance_up_scratch_bytes({count}, {H}, {W}, pictures {Ih} x {Iw}, levels {levels}, batch {batch}): error {rc}")
-    return b.value, n.value
+    return _scratch_bytes("radiance_up", (int(count), int(H), int(W), int(Ih), int(Iw), levels, int(batch), int(bool(host))),
+                          f"{count}, {H}, {W}, pictures {Ih} x {Iw}, levels {levels}, batch {batch}")
 
 
 def radiance_upscaled(images, data, XX, YY, Pplane, upscalefactor: int = 2, datascale: float = 1e-3, ctx: Context | None = None, out=None,
@@ -974,12 +945,8 @@ def radiance_upscaled(images, data, XX, YY, Pplane, upscalefactor: int = 2, data
 
 def bgimage_scratch_bytes(count: int, H: int, W: int, filtersize: int = 2000, slab_rows: int = 0, host: bool = True):
     """(bytes of device scratch, rows per slab) of one bgimage call; no GPU needed."""
-    from . import _lib
-    b, r = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_bgimage_scratch_bytes(int(count), int(H), int(W), int(filtersize), int(slab_rows), int(bool(host)), C.byref(b), C.byref(r))
-    if rc:
-        raise ValueError(f"wass_bgimage_scratch_bytes({count}, {H}, {W}, size {filtersize}): error {rc}")
-    return b.value, r.value
+    return _scratch_bytes("bgimage", (int(count), int(H), int(W), int(filtersize), int(slab_rows), int(bool(host))),
+                          f"{count}, {H}, {W}, size {filtersize}")
 
 
 def bgimage(data, filtersize: int = 2000, ctx: Context | None = None, out=None, slab_rows: int = 0):
@@ -996,28 +963,10 @@ def bgimage(data, filtersize: int = 2000, ctx: Context | None = None, out=None, 
         raise ValueError("filtersize must be at least 1")
     if ctx is None:
         ctx = Context(0)
-    if _is_device(data):
-        import torch
-        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
-            data = data.to(torch.float32).contiguous()
-        if out is None:
-            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
-        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or out.stride(2) != 1 \
-                or out.data_ptr() == data.data_ptr():
-            raise ValueError("out must be another float32 device tensor of the input's shape with a contiguous last axis")
-        torch.cuda.current_stream(data.device).synchronize()
-        ctx._check(ctx._lib.wass_bgimage_dev(ctx._h, data.data_ptr(), data.stride(0), data.stride(1), count, H, W, int(filtersize), int(slab_rows),
-                                             out.data_ptr(), out.stride(0), out.stride(1)))
+    data, (out,), suffix, a = _cube_io(data, (out,), "bgimage", alias=False)
+    ctx._check(getattr(ctx._lib, "wass_bgimage" + suffix)(ctx._h, *a, int(filtersize), int(slab_rows), *_ptr_strides(out)))
+    if suffix:
         ctx.synchronize()
-        return out
-    src = _host_f32_rows(data)
-    if out is None:
-        out = np.empty((count, H, W), np.float32)
-    elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or out.strides[2] != 4 \
-            or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0 or np.shares_memory(out, src):
-        raise ValueError("out must be another float32 host array of the input's shape with a contiguous last axis")
-    ctx._check(ctx._lib.wass_bgimage(ctx._h, src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W, int(filtersize), int(slab_rows),
-                                     out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4))
     return out
 
 
@@ -1026,12 +975,7 @@ VATS_BINS = 30
 
 def radiance_threshold_scratch_bytes(count: int, H: int, W: int, batch: int = 8, host: bool = True):
     """(bytes of device scratch, frames per launch) of one pass of radiance_threshold; no GPU needed."""
-    from . import _lib
-    b, n = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_radiance_threshold_scratch_bytes(int(count), int(H), int(W), int(batch), int(bool(host)), C.byref(b), C.byref(n))
-    if rc:
-        raise ValueError(f"wass_radiance_threshold_scratch_bytes({count}, {H}, {W}, batch {batch}): error {rc}")
-    return b.value, n.value
+    return _scratch_bytes("radiance_threshold", (int(count), int(H), int(W), int(batch), int(bool(host))), f"{count}, {H}, {W}, batch {batch}")
 
 
 def vats_threshold(counts, bin_edges):
@@ -1178,13 +1122,8 @@ def _pol_outputs(outputs) -> int:
 def polarimetric_scratch_bytes(count: int, H: int, W: int, Ih: int, Iw: int, batch: int = 8, host: bool = True,
                                outputs=("S", "occlusion")):
     """(bytes of device scratch, frames per launch) of one polarimetric_setup call; no GPU needed."""
-    from . import _lib
-    b, n = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_polarimetric_scratch_bytes(int(count), int(H), int(W), int(Ih), int(Iw), int(batch), int(bool(host)),
-                                                     _pol_outputs(outputs), C.byref(b), C.byref(n))
-    if rc:
-        raise ValueError(f"wass_polarimetric_scratch_bytes({count}, {H}, {W}, pictures {Ih} x {Iw}, batch {batch}): error {rc}")
-    return b.value, n.value
+    return _scratch_bytes("polarimetric", (int(count), int(H), int(W), int(Ih), int(Iw), int(batch), int(bool(host)), _pol_outputs(outputs)),
+                          f"{count}, {H}, {W}, pictures {Ih} x {Iw}, batch {batch}")
 
 
 @dataclass
@@ -1248,18 +1187,15 @@ def polarimetric_setup(stokes, data, XX, YY, Pplane, cam_to_grid, K, datascale: 
     Kinv = np.linalg.inv(K)
     if ctx is None:
         ctx = Context(0)
-    dev = _is_device(data)
+    data, _, dev, _ = _cube_io(data, (), "polarimetric_setup")
     if dev:
         import torch
-        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
-            data = data.to(torch.float32).contiguous()
         new = lambda shape, dt: torch.empty(shape, dtype=getattr(torch, dt), device=data.device)
         acc = torch.zeros(8 * H * W, dtype=torch.float64, device=data.device)
         grid = (torch.tensor(XX).to(data.device), torch.tensor(YY).to(data.device))      # a copy: the caller's may be read-only
         ptr = lambda a: a.data_ptr()
         entry = ctx._lib.wass_polarimetric_dev
     else:
-        data = _host_f32_rows(data)
         new = lambda shape, dt: np.empty(shape, getattr(np, dt))
         acc = np.zeros(8 * H * W, np.float64)
         grid = (XX, YY)
@@ -1347,34 +1283,6 @@ def polarimetric_setup(stokes, data, XX, YY, Pplane, cam_to_grid, K, datascale: 
                               valid=acc[7 * HW:].reshape(H, W), occluded_percent=100.0 * counts.astype(np.float64) / float(HW), **per_frame)
 
 
-def _cube_io(data, out, what):
-    """(data, out, suffix, pointers and strides) of a float32 cube and its result, on one side"""
-    if len(data.shape) != 3:
-        raise ValueError("data must be count x H x W")
-    count, H, W = (int(v) for v in data.shape)
-    if count < 1 or H < 1 or W < 1:
-        raise ValueError("empty cube")
-    if _is_device(data):
-        import torch
-        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
-            data = data.to(torch.float32).contiguous()
-        if out is None:
-            out = torch.empty((count, H, W), dtype=torch.float32, device=data.device)
-        elif not _is_device(out) or tuple(out.shape) != (count, H, W) or out.dtype != torch.float32 or out.stride(2) != 1 \
-                or out.stride(0) <= 0 or out.stride(1) <= 0:
-            raise ValueError(f"{what}: out must be a float32 device tensor of the input's shape with a contiguous last axis")
-        torch.cuda.current_stream(data.device).synchronize()
-        return data, out, "_dev", (data.data_ptr(), data.stride(0), data.stride(1), count, H, W), (out.data_ptr(), out.stride(0), out.stride(1))
-    src = _host_f32_rows(data)
-    if out is None:
-        out = np.empty((count, H, W), np.float32)
-    elif not isinstance(out, np.ndarray) or out.shape != (count, H, W) or out.dtype != np.float32 or out.strides[2] != 4 \
-            or out.strides[0] % 4 or out.strides[1] % 4 or min(out.strides) <= 0:
-        raise ValueError(f"{what}: out must be a float32 host array of the input's shape with a contiguous last axis")
-    return src, out, "", (src.ctypes.data, src.strides[0] // 4, src.strides[1] // 4, count, H, W), \
-        (out.ctypes.data, out.strides[0] // 4, out.strides[1] // 4)
-
-
 def clip_cube(data, minval: float, maxval: float, out=None, ctx: Context | None = None):
     """wasspost clip as a function: (np.clip(data, float32(minval), float32(maxval)) in float32 with NaN kept, vmin, vmax), vmin
     and vmax the smallest and largest value of the result that is not NaN (NaN if there is none).  A host array or memmap gives
@@ -1382,11 +1290,13 @@ def clip_cube(data, minval: float, maxval: float, out=None, ctx: Context | None 
     lo, hi = np.float32(minval), np.float32(maxval)
     if np.isnan(lo) or np.isnan(hi):
         raise ValueError("minval and maxval must be numbers")
-    data, out, suffix, a, b = _cube_io(data, out, "clip_cube")
+    if min(data.shape, default=0) < 1:
+        raise ValueError("empty cube")
+    data, (out,), suffix, a = _cube_io(data, (out,), "clip_cube")
     if ctx is None:
         ctx = Context(0)
     vmin, vmax = C.c_float(), C.c_float()
-    ctx._check(getattr(ctx._lib, "wass_clip_cube" + suffix)(ctx._h, *a, float(lo), float(hi), *b, C.byref(vmin), C.byref(vmax)))
+    ctx._check(getattr(ctx._lib, "wass_clip_cube" + suffix)(ctx._h, *a, float(lo), float(hi), *_ptr_strides(out), C.byref(vmin), C.byref(vmax)))
     return out, np.float32(vmin.value), np.float32(vmax.value)
 
 
@@ -1394,10 +1304,12 @@ def zeromean(data, out=None, ctx: Context | None = None):
     """wasspost zeromean as a function: float32(double(data) - mean), the mean of every cell over time an fp64 sum in frame order
     divided by the number of frames.  A cell that is NaN in any frame is NaN in all.  A host array or memmap gives a host
     array, a device tensor a device tensor; `out` may be `data`."""
-    data, out, suffix, a, b = _cube_io(data, out, "zeromean")
+    if min(data.shape, default=0) < 1:
+        raise ValueError("empty cube")
+    data, (out,), suffix, a = _cube_io(data, (out,), "zeromean")
     if ctx is None:
         ctx = Context(0)
-    ctx._check(getattr(ctx._lib, "wass_zeromean" + suffix)(ctx._h, *a, *b))
+    ctx._check(getattr(ctx._lib, "wass_zeromean" + suffix)(ctx._h, *a, *_ptr_strides(out)))
     if suffix:
         ctx.synchronize()
     return out
@@ -1437,14 +1349,8 @@ def wave_statistics_scratch_bytes(count: int, H: int, W: int, dt: float = 1.0, d
     """(bytes of device scratch, rows per slab) of one wave_statistics call; no GPU needed.  Per slab of `rows` rows:
     2 * (count // 2) * rows * W * 8 bytes for the waves and, for a host cube, count * rows * W * 4 for the cube, 13 * rows * W * 8
     and rows * W * 4 for the results and hist_bins * 8, each part rounded up to 256 bytes."""
-    from . import _lib
     count, H, W, dt, datascale, cr, hist_bins, hist_width, slab_rows = _wave_args(count, H, W, dt, datascale, crossing, hist_bins, hist_width, slab_rows)
-    b, r = C.c_size_t(), C.c_int()
-    rc = _lib.load().wass_wavestats_scratch_bytes(count, H, W, dt, datascale, cr, hist_bins, hist_width, slab_rows, int(bool(host)),
-                                                  C.byref(b), C.byref(r))
-    if rc:
-        raise ValueError(f"wass_wavestats_scratch_bytes({count}, {H}, {W}): error {rc}")
-    return b.value, r.value
+    return _scratch_bytes("wavestats", (count, H, W, dt, datascale, cr, hist_bins, hist_width, slab_rows, int(bool(host))), f"{count}, {H}, {W}")
 
 
 @dataclass
@@ -1521,31 +1427,27 @@ def wave_statistics(data, dt: float, datascale: float = 1.0, crossing: str = "up
     nf = len(WAVE_FIELDS)
     hist = np.zeros(hist_bins, np.uint64) if hist_bins else None
     args = (count, H, W, dt, datascale, cr, int(bool(demean)), hist_bins, hist_width, slab_rows)
-    if _is_device(data):
+    data, _, dev, a = _cube_io(data, (), "wave_statistics")
+    if dev:
         import torch
-        if data.dtype != torch.float32 or data.stride(2) != 1 or data.stride(0) <= 0 or data.stride(1) <= 0:
-            data = data.to(torch.float32).contiguous()
         d_fields = torch.empty((nf, H, W), dtype=torch.float64, device=data.device)
         d_ncross = torch.empty((H, W), dtype=torch.int32, device=data.device)
         d_hist = torch.empty(hist_bins, dtype=torch.int64, device=data.device) if hist_bins else None    # the call zeroes it
-        torch.cuda.current_stream(data.device).synchronize()
-        ctx._check(ctx._lib.wass_wavestats_dev(ctx._h, data.data_ptr(), *_wave_strides(data.stride(0), data.stride(1), count, H, W), *args,
+        ctx._check(ctx._lib.wass_wavestats_dev(ctx._h, a[0], *_wave_strides(a[1], a[2], count, H, W), *args,
                                                d_fields.data_ptr(), d_ncross.data_ptr(), d_hist.data_ptr() if hist_bins else None))
         fields, n_cross = d_fields.cpu().numpy(), d_ncross.cpu().numpy()
         if hist_bins:
             hist = d_hist.cpu().numpy().view(np.uint64)
     else:
-        src = _host_f32_rows(data)
         fields, n_cross = np.empty((nf, H, W), np.float64), np.empty((H, W), np.int32)
-        ctx._check(ctx._lib.wass_wavestats(ctx._h, src.ctypes.data, *_wave_strides(src.strides[0] // 4, src.strides[1] // 4, count, H, W), *args,
+        ctx._check(ctx._lib.wass_wavestats(ctx._h, a[0], *_wave_strides(a[1], a[2], count, H, W), *args,
                                            fields.ctypes.data, n_cross.ctypes.data, hist.ctypes.data if hist_bins else None))
     m2, m3, m4, h_sqmean = (fields[WAVE_FIELDS.index(n)] for n in ("m2", "m3", "m4", "h_sqmean"))
     with np.errstate(invalid="ignore", divide="ignore"):
         sigma = np.sqrt(m2)
         derived = {"n_waves": np.where(n_cross < 0, n_cross, np.maximum(n_cross - 1, 0)).astype(np.int32), "sigma": sigma, "hs_m0": 4.0 * sigma,
                    "skewness": m3 / (m2 * sigma), "kurtosis": m4 / (m2 * m2), "h_rms": np.sqrt(h_sqmean)}
-    if _is_device(data):
-        import torch
+    if dev:
         maps = {n: d_fields[k] for k, n in enumerate(WAVE_FIELDS)}
         maps["n_cross"] = d_ncross
         maps.update({n: torch.from_numpy(np.ascontiguousarray(v)).to(data.device) for n, v in derived.items()})
