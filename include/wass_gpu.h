@@ -218,6 +218,11 @@ int wass_biggest_component_by_gradient_dev(wass_ctx* ctx, float* d_disp, int w, 
  * component extraction on this context (cc_threshold > 0 in wass_disparity_postprocess_ex or the call above), w x h bytes to
  * the host: what the reference paints into disparity_large_gradient.jpg (:958-960) */
 int wass_large_gradient_mask(wass_ctx* ctx, int w, int h, uint8_t* mask_out);
+/* cv::filterSpeckles(img, new_val, max_size, max_diff) alone, in place on a device int16 map of w x h (the filter that
+ * wass_sgm_disparity applies when speckle_win > 0; test hook / building block): 4-connected regions of pixels != new_val
+ * whose neighbours differ by at most max_diff; a region of at most max_size pixels becomes new_val.  new_val is an int16
+ * value, max_size and max_diff are >= 0.  Asynchronous on the stream of the clean-up calls. */
+int wass_filter_speckles_dev(wass_ctx* ctx, int16_t* d_img, int w, int h, int new_val, int max_size, int max_diff);
 
 /* ------------------------------------------------------------------------
  * Triangulation, rows a10-a13.  Replaces triangulate(StereoMatchEnv&)

@@ -344,6 +344,7 @@ SYMBOLS = {
     "wass_disparity_postprocess_ex": (_i, [_vp, _vp, _i, _i, C.POINTER(SgmParams), _i, _i, _i, _i, _i, _i, _vp]),
     "wass_disparity_postprocess_ex_dev": (_i, [_vp, _vp, _i, _i, C.POINTER(SgmParams), _i, _i, _i, _i, _i, _i, _vp]),
     "wass_biggest_component_by_gradient_dev": (_i, [_vp, _vp, _i, _i, _i]),
+    "wass_filter_speckles_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
     "wass_upload_async": (_i, [_vp, _vp, _vp, _sz]),
     "wass_burned_area_mask_dev": (_i, [_vp, _vp, _sz, _vp]),
     "wass_camera_mask_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),

@@ -286,6 +286,14 @@ extern "C" int wass_biggest_component_by_gradient_dev(wass_ctx* c, float* d_disp
     return biggest_component_dev(c, d_disp, w, h, threshold, (uint8_t*)c->tmp_mask.p, c->ts());
 }
 
+extern "C" int wass_filter_speckles_dev(wass_ctx* c, int16_t* d_img, int w, int h, int new_val, int max_size, int max_diff)
+{
+    if (!c || !d_img || w <= 0 || h <= 0 || max_size < 0 || max_diff < 0 || new_val < -32768 || new_val > 32767)
+        return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
+    WASS_HIP(c, hipSetDevice(c->device));
+    return speckle_filter_dev(c, d_img, w, h, new_val, max_size, max_diff, c->ts());
+}
+
 // disparity_large_gradient.jpg (wass_stereo.cpp:957-960): the mask the last component extraction of this context used
 extern "C" int wass_large_gradient_mask(wass_ctx* c, int w, int h, uint8_t* mask_out)
 {

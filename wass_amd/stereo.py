@@ -218,6 +218,15 @@ class Context:
                                                              dilate_steps, erode_steps, median_wsize, d_out.data_ptr()))
         return d_out
 
+    def filter_speckles_dev(self, d_img, new_val: int, max_size: int, max_diff: int):
+        """cv::filterSpeckles in place on a contiguous 2-D int16 CUDA tensor (wass_filter_speckles_dev; asynchronous)."""
+        import torch
+        if d_img.dtype != torch.int16 or not d_img.is_cuda or d_img.dim() != 2 or not d_img.is_contiguous():
+            raise ValueError("d_img: expected a contiguous 2-D int16 CUDA tensor")
+        h, w = d_img.shape
+        self._check(self._lib.wass_filter_speckles_dev(self._h, d_img.data_ptr(), w, h, int(new_val), int(max_size), int(max_diff)))
+        return d_img
+
     def frame_result(self):
         """Wait for the frame enqueued by Mesh.finish_frame_async and return its wass_frame_result."""
         res = _lib.FrameResult()
