@@ -398,3 +398,12 @@ def load() -> C.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def scratch_bytes(name: str, args, refusal: str) -> int:
+    """What the pure planner wass_<name>_scratch_bytes(*args, &bytes) answers (no GPU needed); where it refuses, a ValueError with
+    the caller's text."""
+    b = C.c_size_t()
+    if getattr(load(), f"wass_{name}_scratch_bytes")(*args, C.byref(b)) != 0:
+        raise ValueError(refusal)
+    return b.value

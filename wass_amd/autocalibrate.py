@@ -124,10 +124,7 @@ def cam_rotation(cam) -> np.ndarray:
 def wass_ac_scratch_bytes(n: int) -> int:
     """device memory the context keeps for a bundle adjustment of n points (no GPU needed)"""
     from . import _lib
-    b = C.c_size_t()
-    if _lib.load().wass_ac_scratch_bytes(int(n), C.byref(b)) != 0:
-        raise ValueError(f"n = {n}: 1 .. {MAX_N} points")
-    return b.value
+    return _lib.scratch_bytes("ac", (int(n),), f"n = {n}: 1 .. {MAX_N} points")
 
 
 # --------------------------------------------------------------------------------------------------------------------- kernels

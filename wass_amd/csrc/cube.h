@@ -2,6 +2,8 @@
 // wavestats; prepare_pol takes the keys): the host scaffolding of a call that allocates its scratch, runs and frees it, and the
 // ordered-key maxima of their kernels.  Plain functions and one RAII struct; every operator keeps its own plan and byte formula.
 // A call makes ONE hipMalloc and one hipFree by design: the scratch of a cube is gigabytes and is not kept in the context.
+// The handles of spectrum.hip (wass_spec3d, wass_spatial_filter) hold an Arena for their lifetime and stage through the same
+// functions; vref.hip takes align256.
 #pragma once
 
 #include "common.h"
@@ -12,7 +14,9 @@ namespace wass {
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // One hipMalloc of `total` bytes, handed out in 256-aligned pieces in the order asked, freed when the struct goes out of scope.
-// A total of 0 makes no call at all, and every piece of it is a pointer nobody may follow.
+// A total of 0 makes no call at all, and every piece of it is a pointer nobody may follow.  An Arena that has reserved nothing
+// measures: take() hands out nullptr and still counts, so the function that carves a layout, run on a fresh Arena, leaves the
+// layout's size in `used`.
 struct Arena {
     char* mem = nullptr;
     size_t used = 0;
@@ -27,7 +31,7 @@ struct Arena {
     }
     template <class T> T* take(size_t bytes)
     {
-        T* p = (T*)(mem + used);
+        T* p = mem ? (T*)(mem + used) : nullptr;
         used += align256(bytes);
         return p;
     }
@@ -84,13 +88,15 @@ inline hipError_t upload_rows(void* dev, const void* host, size_t elem, int coun
     return e;
 }
 
-inline hipError_t download_rows(void* host, const void* dev, size_t elem, int count, int r0, int rows, int W, size_t st, size_t sy, hipStream_t s)
+// The way back; with kind = hipMemcpyDeviceToDevice `host` is a cube on the device.
+inline hipError_t download_rows(void* host, const void* dev, size_t elem, int count, int r0, int rows, int W, size_t st, size_t sy, hipStream_t s,
+                                hipMemcpyKind kind = hipMemcpyDeviceToHost)
 {
     const size_t rowb = (size_t)W * elem, plane = (size_t)rows * rowb;
     hipError_t e = hipSuccess;
     for (int t = 0; t < count && e == hipSuccess; ++t)
         e = hipMemcpy2DAsync((char*)host + ((size_t)t * st + (size_t)r0 * sy) * elem, sy * elem, (const char*)dev + (size_t)t * plane, rowb, rowb, rows,
-                             hipMemcpyDeviceToHost, s);
+                             kind, s);
     return e;
 }
 

@@ -19,7 +19,7 @@
 // Scratch of one handle, in units of one real f32 copy of the window (nt * ny * nx * 4 bytes): 1 for the prepared segment, 1 for
 // the host-pointer staging, about 2 for the two complex half-spectra the stages alternate between, 2 for the fp64 Welch sum:
 // about 6, i.e. 1.1 GB at 100 x 684 x 684 and 3.4 GB at 300 x 684 x 684.  SPEC_SCRATCH_CAP bounds it.
-#include "common.h"
+#include "cube.h"
 
 #include <math.h>
 #include <new>
@@ -311,36 +311,44 @@ static int launch_dft(wass_ctx* c, hipStream_t s, const DftArgs& a, bool cplx, b
     return WASS_OK;
 }
 
+// p + n, or nullptr for a piece of an Arena that only measures
+template <class T> static T* piece_at(T* p, size_t n) { return p ? p + n : nullptr; }
+
 struct Twiddle {
     float* c = nullptr;
     float* s = nullptr;
-    int Kp = 0, Mp = 0;
-    static size_t bytes(int n, int nm) { return (size_t)2 * sp_round_up(n, SP_TK) * sp_round_up(nm, SP_TM) * 4; }
+    int n = 0, nm = 0, Kp = 0, Mp = 0;
 };
 
-// carve one twiddle pair out of mem (bytes(n, nm) of it) and fill it
-static int make_twiddle(wass_ctx* c, hipStream_t s, char*& mem, int n, int nm, Twiddle& t)
+// one twiddle pair for a transform of length n with nm outputs, taken from the arena: 2 * Kp * Mp floats (a multiple of 256 bytes)
+static Twiddle make_twiddle(Arena& a, int n, int nm)
 {
+    Twiddle t;
+    t.n = n;
+    t.nm = nm;
     t.Kp = sp_round_up(n, SP_TK);
     t.Mp = sp_round_up(nm, SP_TM);
-    t.c = (float*)mem;
-    t.s = t.c + (size_t)t.Kp * t.Mp;
-    mem += Twiddle::bytes(n, nm);
-    hipLaunchKernelGGL(k_dft_twiddle, dim3((t.Mp + 255) / 256, t.Kp), dim3(256), 0, s, t.c, t.s, n, nm, t.Mp);
+    t.c = a.take<float>((size_t)2 * t.Kp * t.Mp * 4);
+    t.s = piece_at(t.c, (size_t)t.Kp * t.Mp);
+    return t;
+}
+
+static int fill_twiddle(wass_ctx* c, hipStream_t s, const Twiddle& t)
+{
+    hipLaunchKernelGGL(k_dft_twiddle, dim3((t.Mp + 255) / 256, t.Kp), dim3(256), 0, s, t.c, t.s, t.n, t.nm, t.Mp);
     WASS_HIP(c, hipGetLastError());
     return WASS_OK;
 }
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace wass
 
 using namespace wass;
 
 struct wass_spec3d {
-    wass_ctx* c = nullptr;
-    int nt = 0, ny = 0, nx = 0, nxh = 0;
-    char* mem = nullptr;           // one allocation, carved below
+    wass_spec3d(wass_ctx* c_, int nt_, int ny_, int nx_) : c(c_), nt(nt_), ny(ny_), nx(nx_), nxh(nx_ / 2 + 1) {}
+    wass_ctx* c;
+    int nt, ny, nx, nxh;
+    Arena arena;                   // one allocation, carved by carve()
     float* raw = nullptr;          // staging of a host segment, [nt][ny][nx]
     float* prep = nullptr;         // the prepared segment
     float* a_re = nullptr; float* a_im = nullptr;   // [nt][ny][nxh]: x stage out, t stage out
@@ -356,29 +364,31 @@ struct wass_spec3d {
 
 namespace {
 
-struct Spec3dLayout {
-    size_t win, half, off_raw, off_prep, off_a, off_b, off_S, off_w, off_cell, off_part, off_flag, off_tw, total;
-};
-
-Spec3dLayout spec3d_layout(int nt, int ny, int nx)
+// The handle's pieces, in the order of its allocation.  Run on an Arena that has reserved nothing it measures: a.used is what
+// the handle needs.
+void carve(wass_spec3d& h, Arena& a)
 {
-    Spec3dLayout L;
-    const int nxh = nx / 2 + 1;
-    L.win = (size_t)nt * ny * nx;
-    L.half = (size_t)nt * ny * nxh;
-    size_t o = 0;
-    L.off_raw = o;  o += align256(L.win * 4);
-    L.off_prep = o; o += align256(L.win * 4);
-    L.off_a = o;    o += align256(2 * L.half * 4);
-    L.off_b = o;    o += align256(2 * L.half * 4);
-    L.off_S = o;    o += align256(L.win * 8);
-    L.off_w = o;    o += align256((size_t)(nt + ny + nx) * 8);
-    L.off_cell = o; o += align256((size_t)ny * nx * 4);
-    L.off_part = o; o += align256((((size_t)ny * nx + 255) / 256 + 1) * 8);
-    L.off_flag = o; o += 256;
-    L.off_tw = o;   o += Twiddle::bytes(nx, nxh) + Twiddle::bytes(ny, ny) + Twiddle::bytes(nt, nt);
-    L.total = o;
-    return L;
+    const size_t cells = (size_t)h.ny * h.nx, win = (size_t)h.nt * cells, half = (size_t)h.nt * h.ny * h.nxh;
+    h.npart = (int)((cells + 255) / 256);
+    h.raw = a.take<float>(win * 4);
+    h.prep = a.take<float>(win * 4);
+    h.a_re = a.take<float>(2 * half * 4); h.a_im = piece_at(h.a_re, half);
+    h.b_re = a.take<float>(2 * half * 4); h.b_im = piece_at(h.b_re, half);
+    h.S = a.take<double>(win * 8);
+    h.wt = a.take<double>((size_t)(h.nt + h.ny + h.nx) * 8); h.wy = piece_at(h.wt, h.nt); h.wx = piece_at(h.wy, h.ny);
+    h.cellmean = a.take<float>(cells * 4);
+    h.part = a.take<double>(((size_t)h.npart + 1) * 8); h.mean = piece_at(h.part, h.npart);
+    h.flag = a.take<int>(256);
+    h.tx = make_twiddle(a, h.nx, h.nxh);
+    h.ty = make_twiddle(a, h.ny, h.ny);
+    h.tt = make_twiddle(a, h.nt, h.nt);
+}
+
+size_t spec3d_bytes(int nt, int ny, int nx)
+{
+    wass_spec3d h(nullptr, nt, ny, nx);
+    carve(h, h.arena);
+    return h.arena.used;
 }
 
 bool spec3d_dims_ok(int nt, int ny, int nx)
@@ -426,7 +436,7 @@ int spec3d_run(wass_spec3d* h, const float* d_seg, size_t stride_t, size_t strid
 extern "C" int wass_spec3d_scratch_bytes(int nt, int ny, int nx, size_t* bytes)
 {
     if (!bytes || !spec3d_dims_ok(nt, ny, nx)) return WASS_ERR_INVALID_ARG;
-    *bytes = spec3d_layout(nt, ny, nx).total;
+    *bytes = spec3d_bytes(nt, ny, nx);
     return WASS_OK;
 }
 
@@ -434,8 +444,7 @@ extern "C" void wass_spec3d_destroy(wass_spec3d* h)
 {
     if (!h) return;
     if (h->c) (void)hipSetDevice(h->c->device);
-    if (h->mem) (void)hipFree(h->mem);
-    delete h;
+    delete h;                      // the arena frees the scratch
 }
 
 extern "C" int wass_spec3d_create(wass_ctx* c, int nt, int ny, int nx, const double* win_t, const double* win_y, const double* win_x,
@@ -444,44 +453,30 @@ extern "C" int wass_spec3d_create(wass_ctx* c, int nt, int ny, int nx, const dou
     if (!c || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (!spec3d_dims_ok(nt, ny, nx)) return set_err(c, WASS_ERR_INVALID_ARG, "bad window size %d x %d x %d (each axis 1 .. %d)", nt, ny, nx, SPEC_MAX_AXIS);
-    const Spec3dLayout L = spec3d_layout(nt, ny, nx);
+    const size_t total = spec3d_bytes(nt, ny, nx);
     if ((size_t)ny * (nx / 2 + 1) > 0x7fffffffu || (size_t)nt * ny > 0x7fffffffu) return set_err(c, WASS_ERR_UNSUPPORTED, "window too large");
-    if (L.total > SPEC_SCRATCH_CAP)
-        return set_err(c, WASS_ERR_NO_MEMORY, "a %d x %d x %d window needs %zu bytes of scratch, the cap is %zu", nt, ny, nx, L.total, SPEC_SCRATCH_CAP);
+    if (total > SPEC_SCRATCH_CAP)
+        return set_err(c, WASS_ERR_NO_MEMORY, "a %d x %d x %d window needs %zu bytes of scratch, the cap is %zu", nt, ny, nx, total, SPEC_SCRATCH_CAP);
     WASS_HIP(c, hipSetDevice(c->device));
-    wass_spec3d* h = new (std::nothrow) wass_spec3d;
+    wass_spec3d* h = new (std::nothrow) wass_spec3d(c, nt, ny, nx);
     if (!h) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
-    h->c = c; h->nt = nt; h->ny = ny; h->nx = nx; h->nxh = nx / 2 + 1;
-    hipError_t e = hipMalloc((void**)&h->mem, L.total);
-    if (e != hipSuccess) {
-        h->mem = nullptr;
+    int rc = h->arena.reserve(c, total, "the spectrum scratch");
+    if (rc) {
         wass_spec3d_destroy(h);
-        return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the spectrum scratch: %s", L.total, hipGetErrorString(e));
+        return rc;
     }
-    h->raw = (float*)(h->mem + L.off_raw);
-    h->prep = (float*)(h->mem + L.off_prep);
-    h->a_re = (float*)(h->mem + L.off_a); h->a_im = h->a_re + L.half;
-    h->b_re = (float*)(h->mem + L.off_b); h->b_im = h->b_re + L.half;
-    h->S = (double*)(h->mem + L.off_S);
-    h->wt = (double*)(h->mem + L.off_w); h->wy = h->wt + nt; h->wx = h->wy + ny;
-    h->cellmean = (float*)(h->mem + L.off_cell);
-    h->part = (double*)(h->mem + L.off_part);
-    h->npart = (int)(((size_t)ny * nx + 255) / 256);
-    h->mean = h->part + h->npart;
-    h->flag = (int*)(h->mem + L.off_flag);
+    carve(*h, h->arena);
     hipStream_t s = c->ts();
     std::vector<double> w((size_t)nt + ny + nx);
     if (win_t) memcpy(&w[0], win_t, (size_t)nt * 8); else hann_symmetric(nt, &w[0]);
     if (win_y) memcpy(&w[nt], win_y, (size_t)ny * 8); else hann_symmetric(ny, &w[nt]);
     if (win_x) memcpy(&w[(size_t)nt + ny], win_x, (size_t)nx * 8); else hann_symmetric(nx, &w[(size_t)nt + ny]);
-    int rc = WASS_OK;
-    char* tw = h->mem + L.off_tw;
     if (hipMemcpyAsync(h->wt, w.data(), w.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(h->S, 0, L.win * 8, s) != hipSuccess || hipMemsetAsync(h->flag, 0, 256, s) != hipSuccess)
+        hipMemsetAsync(h->S, 0, (size_t)nt * ny * nx * 8, s) != hipSuccess || hipMemsetAsync(h->flag, 0, 256, s) != hipSuccess)
         rc = set_err(c, WASS_ERR_DEVICE, "spectrum set-up failed");
-    if (!rc) rc = make_twiddle(c, s, tw, nx, h->nxh, h->tx);
-    if (!rc) rc = make_twiddle(c, s, tw, ny, ny, h->ty);
-    if (!rc) rc = make_twiddle(c, s, tw, nt, nt, h->tt);
+    if (!rc) rc = fill_twiddle(c, s, h->tx);
+    if (!rc) rc = fill_twiddle(c, s, h->ty);
+    if (!rc) rc = fill_twiddle(c, s, h->tt);
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "spectrum set-up failed");   // w leaves scope
     if (rc) {
         wass_spec3d_destroy(h);
@@ -507,10 +502,8 @@ extern "C" int wass_spec3d_push(wass_spec3d* h, const float* seg, size_t stride_
     if (!seg || stride_y < (size_t)h->nx || stride_t < (size_t)h->nx) return set_err(c, WASS_ERR_INVALID_ARG, "bad segment pointer or strides");
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    const size_t slab = (size_t)h->ny * h->nx, row = (size_t)h->nx * 4;
-    for (int t = 0; t < h->nt; ++t)
-        WASS_HIP(c, hipMemcpy2DAsync(h->raw + t * slab, row, seg + t * stride_t, stride_y * 4, row, h->ny, hipMemcpyHostToDevice, s));
-    return spec3d_run(h, h->raw, slab, h->nx, datascale);
+    WASS_HIP(c, upload_rows(h->raw, seg, 4, h->nt, 0, h->ny, h->nx, stride_t, stride_y, s));
+    return spec3d_run(h, h->raw, (size_t)h->ny * h->nx, h->nx, datascale);
 }
 
 extern "C" int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* n_segments, int* had_all_nan_cell)
@@ -547,26 +540,28 @@ extern "C" int wass_spec1d_welch(wass_ctx* c, const float* series, int n_series,
     if (nseg < 1 || nseg > 65535) return set_err(c, WASS_ERR_INVALID_ARG, "no segment fits");
     const size_t ncol = (size_t)n_series * nseg;
     if (ncol > 0x7fffffffu) return set_err(c, WASS_ERR_UNSUPPORTED, "too many segments");
-    size_t o = 0;
-    const size_t off_x = o;   o += align256((size_t)n_series * n_samples * 4);
-    const size_t off_m = o;   o += align256((size_t)n_series * 8);
-    const size_t off_w = o;   o += align256((size_t)nps * 8);
-    const size_t off_B = o;   o += align256((size_t)nps * ncol * 4);
-    const size_t off_X = o;   o += align256((size_t)2 * nf * ncol * 4);
-    const size_t off_o = o;   o += align256((size_t)nf * 8);
-    const size_t off_tw = o;  o += Twiddle::bytes(nps, nf);
-    if (o > SPEC_SCRATCH_CAP) return set_err(c, WASS_ERR_NO_MEMORY, "the Welch estimate needs %zu bytes of scratch, the cap is %zu", o, SPEC_SCRATCH_CAP);
+    float *d_x, *d_B, *d_Xre, *d_Xim;
+    double *d_m, *d_w, *d_o;
+    Twiddle tw;
+    auto carve = [&](Arena& a) {
+        d_x = a.take<float>((size_t)n_series * n_samples * 4);
+        d_m = a.take<double>((size_t)n_series * 8);
+        d_w = a.take<double>((size_t)nps * 8);
+        d_B = a.take<float>((size_t)nps * ncol * 4);
+        d_Xre = a.take<float>((size_t)2 * nf * ncol * 4); d_Xim = piece_at(d_Xre, (size_t)nf * ncol);
+        d_o = a.take<double>((size_t)nf * 8);
+        tw = make_twiddle(a, nps, nf);
+    };
+    Arena measure, arena;
+    carve(measure);
+    const size_t total = measure.used;
+    if (total > SPEC_SCRATCH_CAP)
+        return set_err(c, WASS_ERR_NO_MEMORY, "the Welch estimate needs %zu bytes of scratch, the cap is %zu", total, SPEC_SCRATCH_CAP);
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, o) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the Welch scratch failed", o);
-    float* d_x = (float*)(mem + off_x);
-    double* d_m = (double*)(mem + off_m);
-    double* d_w = (double*)(mem + off_w);
-    float* d_B = (float*)(mem + off_B);
-    float* d_Xre = (float*)(mem + off_X);
-    float* d_Xim = d_Xre + (size_t)nf * ncol;
-    double* d_o = (double*)(mem + off_o);
+    int rc = arena.reserve(c, total, "the Welch scratch");
+    if (rc) return rc;
+    carve(arena);
     // periodic Hann (scipy's get_window('hann', n)): 0.5 - 0.5 cos(2 pi i / n)
     std::vector<double> w(nps);
     double sw2 = 0.0;
@@ -575,13 +570,10 @@ extern "C" int wass_spec1d_welch(wass_ctx* c, const float* series, int n_series,
         sw2 += w[i] * w[i];
     }
     const double dens = 1.0 / (fs * sw2) / (double)nseg;             // density scaling, mean over the segments
-    int rc = WASS_OK;
-    Twiddle tw;
-    char* twm = mem + off_tw;
     hipError_t e = hipMemcpyAsync(d_x, series, (size_t)n_series * n_samples * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_w, w.data(), (size_t)nps * 8, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "upload of the series: %s", hipGetErrorString(e));
-    if (!rc) rc = make_twiddle(c, s, twm, nps, nf, tw);
+    if (!rc) rc = fill_twiddle(c, s, tw);
     if (!rc) {
         const float sc = (float)scale;
         hipLaunchKernelGGL(k_w1_mean, dim3(n_series), dim3(256), 0, s, (const float*)d_x, n_samples, sc, d_m);
@@ -594,12 +586,8 @@ extern "C" int wass_spec1d_welch(wass_ctx* c, const float* series, int n_series,
         hipLaunchKernelGGL(k_w1_power, dim3(nf), dim3(256), 0, s, (const float*)d_Xre, (const float*)d_Xim, ncol, dens, nps, d_o);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(S, d_o, (size_t)nf * 8, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "Welch estimate: %s", hipGetErrorString(e));
     }
-    e = hipStreamSynchronize(s);
-    if (!rc && e != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "Welch estimate: %s", hipGetErrorString(e));
-    (void)hipFree(mem);
-    return rc;
+    return finish(c, rc, e, s, "Welch estimate");
 }
 
 // ---- the spatial Butterworth low-pass (postproc/wasspost/spectra.py:176-202, wasspost spatial_lowpass) -------------------------
@@ -628,10 +616,11 @@ __global__ void __launch_bounds__(256) k_spat_mul(float* __restrict__ re, float*
 }  // namespace wass
 
 struct wass_spatial_filter {
-    wass_ctx* c = nullptr;
-    int rows = 0, cols = 0, ch = 0, batch = 0;
-    char* mem = nullptr;
-    float* io = nullptr;            // [batch][rows][cols]: staged input of the host entry, then the result
+    wass_spatial_filter(wass_ctx* c_, int rows_, int cols_, int batch_) : c(c_), rows(rows_), cols(cols_), ch(cols_ / 2 + 1), batch(batch_) {}
+    wass_ctx* c;
+    int rows, cols, ch, batch;
+    Arena arena;
+    float* io = nullptr;           // [batch][rows][cols]: staged input of the host entry, then the result
     float* dump = nullptr;          // the last stage's imaginary part
     float* a_re = nullptr; float* a_im = nullptr;   // [batch][rows][ch]
     float* b_re = nullptr; float* b_im = nullptr;
@@ -641,30 +630,29 @@ struct wass_spatial_filter {
 
 namespace {
 
-struct SpatLayout {
-    size_t frame, half, off_io, off_dump, off_a, off_b, off_H, off_tw, total;
-};
-
 bool spat_dims_ok(int rows, int cols, int batch)
 {
     return rows >= 1 && cols >= 1 && rows <= SPEC_MAX_AXIS && cols <= SPEC_MAX_AXIS && batch >= 1 && batch <= 65535;
 }
 
-SpatLayout spat_layout(int rows, int cols, int batch)
+// The handle's pieces, in the order of its allocation; on an Arena that has reserved nothing it measures, like the spectrum's.
+void carve(wass_spatial_filter& h, Arena& a)
 {
-    SpatLayout L;
-    const int ch = cols / 2 + 1;
-    L.frame = (size_t)rows * cols;
-    L.half = (size_t)rows * ch;
-    size_t o = 0;
-    L.off_io = o;   o += align256(L.frame * batch * 4);
-    L.off_dump = o; o += align256(L.frame * batch * 4);
-    L.off_a = o;    o += align256(2 * L.half * batch * 4);
-    L.off_b = o;    o += align256(2 * L.half * batch * 4);
-    L.off_H = o;    o += align256(L.half * 8);
-    L.off_tw = o;   o += Twiddle::bytes(cols, cols) + Twiddle::bytes(rows, rows);
-    L.total = o;
-    return L;
+    const size_t frames = (size_t)h.rows * h.cols * h.batch, half = (size_t)h.rows * h.ch, halves = half * h.batch;
+    h.io = a.take<float>(frames * 4);
+    h.dump = a.take<float>(frames * 4);
+    h.a_re = a.take<float>(2 * halves * 4); h.a_im = piece_at(h.a_re, halves);
+    h.b_re = a.take<float>(2 * halves * 4); h.b_im = piece_at(h.b_re, halves);
+    h.Hw = a.take<double>(half * 8);
+    h.tx = make_twiddle(a, h.cols, h.cols);
+    h.ty = make_twiddle(a, h.rows, h.rows);
+}
+
+size_t spat_bytes(int rows, int cols, int batch)
+{
+    wass_spatial_filter h(nullptr, rows, cols, batch);
+    carve(h, h.arena);
+    return h.arena.used;
 }
 
 // nb frames at d_in (element strides st, sy) -> h->io, [nb][rows][cols]
@@ -696,21 +684,19 @@ int spat_apply(wass_spatial_filter* h, bool host, const float* in, size_t st, si
         return set_err(c, WASS_ERR_INVALID_ARG, "bad frame pointer, count or strides");
     WASS_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->ts();
-    const size_t frame = (size_t)h->rows * h->cols, rowb = (size_t)h->cols * 4;
-    const hipMemcpyKind up = hipMemcpyHostToDevice, down = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const int R = h->rows, Cn = h->cols;
     for (int f0 = 0; f0 < n; f0 += h->batch) {
         const int nb = n - f0 < h->batch ? n - f0 : h->batch;
+        const float* frames = in + (size_t)f0 * st;
         int rc;
         if (host) {
-            for (int b = 0; b < nb; ++b)
-                WASS_HIP(c, hipMemcpy2DAsync(h->io + b * frame, rowb, in + (f0 + b) * st, sy * 4, rowb, h->rows, up, s));
-            rc = spat_run(h, h->io, (long long)frame, h->cols, nb);
+            WASS_HIP(c, upload_rows(h->io, frames, 4, nb, 0, R, Cn, st, sy, s));
+            rc = spat_run(h, h->io, (long long)R * Cn, Cn, nb);
         } else {
-            rc = spat_run(h, in + (size_t)f0 * st, (long long)st, (long long)sy, nb);
+            rc = spat_run(h, frames, (long long)st, (long long)sy, nb);
         }
         if (rc) return rc;
-        for (int b = 0; b < nb; ++b)
-            WASS_HIP(c, hipMemcpy2DAsync(out + (f0 + b) * ost, osy * 4, h->io + b * frame, rowb, rowb, h->rows, down, s));
+        WASS_HIP(c, download_rows(out + (size_t)f0 * ost, h->io, 4, nb, 0, R, Cn, ost, osy, s, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
     }
     if (host) WASS_HIP(c, hipStreamSynchronize(s));
     return WASS_OK;
@@ -721,7 +707,7 @@ int spat_apply(wass_spatial_filter* h, bool host, const float* in, size_t st, si
 extern "C" int wass_spatial_filter_scratch_bytes(int rows, int cols, int batch, size_t* bytes)
 {
     if (!bytes || !spat_dims_ok(rows, cols, batch)) return WASS_ERR_INVALID_ARG;
-    *bytes = spat_layout(rows, cols, batch).total;
+    *bytes = spat_bytes(rows, cols, batch);
     return WASS_OK;
 }
 
@@ -729,11 +715,8 @@ extern "C" void wass_spatial_filter_destroy(wass_spatial_filter* h)
 {
     if (!h) return;
     if (h->c) (void)hipSetDevice(h->c->device);
-    if (h->mem) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(h->mem);
-    }
-    delete h;
+    if (h->arena.mem) (void)hipDeviceSynchronize();     // the device form of apply returns with its copies in flight
+    delete h;                                           // the arena frees the scratch
 }
 
 extern "C" int wass_spatial_filter_create(wass_ctx* c, int rows, int cols, const double* H, int batch, wass_spatial_filter** out)
@@ -744,27 +727,22 @@ extern "C" int wass_spatial_filter_create(wass_ctx* c, int rows, int cols, const
     if (!spat_dims_ok(rows, cols, batch))
         return set_err(c, WASS_ERR_INVALID_ARG, "bad frame size %d x %d (each axis 1 .. %d) or batch %d", rows, cols, SPEC_MAX_AXIS, batch);
     // no more frames per batch than the cap allows
-    while (batch > 1 && spat_layout(rows, cols, batch).total > SPEC_SCRATCH_CAP) batch /= 2;
-    const SpatLayout L = spat_layout(rows, cols, batch);
-    if (L.total > SPEC_SCRATCH_CAP)
-        return set_err(c, WASS_ERR_NO_MEMORY, "a %d x %d frame needs %zu bytes of scratch, the cap is %zu", rows, cols, L.total, SPEC_SCRATCH_CAP);
+    while (batch > 1 && spat_bytes(rows, cols, batch) > SPEC_SCRATCH_CAP) batch /= 2;
+    const size_t total = spat_bytes(rows, cols, batch);
+    if (total > SPEC_SCRATCH_CAP)
+        return set_err(c, WASS_ERR_NO_MEMORY, "a %d x %d frame needs %zu bytes of scratch, the cap is %zu", rows, cols, total, SPEC_SCRATCH_CAP);
     WASS_HIP(c, hipSetDevice(c->device));
-    wass_spatial_filter* h = new (std::nothrow) wass_spatial_filter;
+    wass_spatial_filter* h = new (std::nothrow) wass_spatial_filter(c, rows, cols, batch);
     if (!h) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
-    h->c = c; h->rows = rows; h->cols = cols; h->ch = cols / 2 + 1; h->batch = batch;
-    hipError_t e = hipMalloc((void**)&h->mem, L.total);
-    if (e != hipSuccess) {
-        h->mem = nullptr;
+    int rc = h->arena.reserve(c, total, "the spatial filter's scratch");
+    if (rc) {
         wass_spatial_filter_destroy(h);
-        return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for the spatial filter's scratch: %s", L.total, hipGetErrorString(e));
+        return rc;
     }
-    h->io = (float*)(h->mem + L.off_io);
-    h->dump = (float*)(h->mem + L.off_dump);
-    h->a_re = (float*)(h->mem + L.off_a); h->a_im = h->a_re + L.half * batch;
-    h->b_re = (float*)(h->mem + L.off_b); h->b_im = h->b_re + L.half * batch;
-    h->Hw = (double*)(h->mem + L.off_H);
+    carve(*h, h->arena);
     const int ch = h->ch;
-    std::vector<double> hw(L.half);
+    const size_t half = (size_t)rows * ch;
+    std::vector<double> hw(half);
     const double inv = 1.0 / ((double)rows * (double)cols);
     for (int ky = 0; ky < rows; ++ky)
         for (int kx = 0; kx < ch; ++kx) {
@@ -772,11 +750,9 @@ extern "C" int wass_spatial_filter_create(wass_ctx* c, int rows, int cols, const
             hw[(size_t)ky * ch + kx] = H[(size_t)ky * cols + kx] * (alone ? 1.0 : 2.0) * inv;
         }
     hipStream_t s = c->ts();
-    int rc = WASS_OK;
-    char* tw = h->mem + L.off_tw;
-    if (hipMemcpyAsync(h->Hw, hw.data(), L.half * 8, hipMemcpyHostToDevice, s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "spatial filter set-up failed");
-    if (!rc) rc = make_twiddle(c, s, tw, cols, cols, h->tx);
-    if (!rc) rc = make_twiddle(c, s, tw, rows, rows, h->ty);
+    if (hipMemcpyAsync(h->Hw, hw.data(), half * 8, hipMemcpyHostToDevice, s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "spatial filter set-up failed");
+    if (!rc) rc = fill_twiddle(c, s, h->tx);
+    if (!rc) rc = fill_twiddle(c, s, h->ty);
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "spatial filter set-up failed");   // hw leaves scope
     if (rc) {
         wass_spatial_filter_destroy(h);

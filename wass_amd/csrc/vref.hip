@@ -59,7 +59,7 @@
 //   k_vref_down      per coarse node: cv.resize's INTER_LINEAR rule (refinement.downsample_linear) from host tables s, s + 1, f:
 //                    row = S[s] * (1 - f) + S[s + 1] * f in float32, the two rows combined by the same rule; m = v = 0
 //   k_vref_finish    per fine node: Z = resize(Zc) * mask, out = mask ? (float)(-(double)Z * baseline) : NaN
-#include "common.h"
+#include "cube.h"
 
 #include <math.h>
 
@@ -400,8 +400,6 @@ __global__ void __launch_bounds__(256) k_vref_finish(const float* __restrict__ Z
     out[o] = mk != 0.0f ? (float)(-(double)z * baseline) : __builtin_nanf("");
 }
 
-static inline size_t vr_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // One allocation: what every frame shares, then nb frames of `frame` bytes each.  The f_ offsets count from a frame's start.
 struct VrefLayout {
     size_t N, Nc, off_x, off_y, off_flag, off_tab, shared;
@@ -426,13 +424,13 @@ static VrefLayout vref_layout(int nb, int ny, int nx, int ih0, int iw0, int ih1,
     L.bx = (nx + VR_TW - 1) / VR_TW;
     L.by = (ny + VR_TH - 1) / VR_TH;
     L.nblocks = L.bx * L.by;
-    const size_t plane = vr_align(L.N * 4), coarse = vr_align(L.Nc * 4);
+    const size_t plane = align256(L.N * 4), coarse = align256(L.Nc * 4);
     size_t o = 0;
     L.off_x = o; o += plane;
     L.off_y = o; o += plane;
     L.off_flag = o; o += 256;
     // resize: lo, hi, t per fine index, r0, r1 per coarse index; down-sampling: s, s1, f per coarse index
-    L.off_tab = o; o += vr_align((size_t)(ny + nx) * 12 + (size_t)(ny / 2 + nx / 2) * 20);
+    L.off_tab = o; o += align256((size_t)(ny + nx) * 12 + (size_t)(ny / 2 + nx / 2) * 20);
     L.shared = o;
     o = 0;
     L.f_mask = o; o += plane;
@@ -441,12 +439,12 @@ static VrefLayout vref_layout(int nb, int ny, int nx, int ih0, int iw0, int ih1,
     L.f_zdy = o; o += plane;
     L.f_gd = o; o += plane;
     L.f_gz = o; o += plane;
-    L.f_I0 = o; o += vr_align((size_t)ih0 * iw0 * 4);
-    L.f_I1 = o; o += vr_align((size_t)ih1 * iw1 * 4);
+    L.f_I0 = o; o += align256((size_t)ih0 * iw0 * 4);
+    L.f_I1 = o; o += align256((size_t)ih1 * iw1 * 4);
     L.f_zc = o; o += coarse;
     L.f_m = o; o += coarse;
     L.f_v = o; o += coarse;
-    L.f_partial = o; o += vr_align((size_t)L.nblocks * 16);
+    L.f_partial = o; o += align256((size_t)L.nblocks * 16);
     L.frame = o;
     L.total = L.shared + (size_t)nb * L.frame;
     return L;

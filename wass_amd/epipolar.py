@@ -150,10 +150,7 @@ def _upload(pairs, dev):
 def scratch_bytes(batch: int, rounds: int = ROUNDS) -> int:
     """device memory the context keeps for find_essential over `batch` pairs of `rounds` samples (no GPU needed)"""
     from . import _lib
-    b = C.c_size_t()
-    if _lib.load().wass_epi_scratch_bytes(int(batch), int(rounds), C.byref(b)) != 0:
-        raise ValueError(f"batch = {batch}, rounds = {rounds}: 1 .. 65535 pairs of 1 .. {MAX_ROUNDS} samples")
-    return b.value
+    return _lib.scratch_bytes("epi", (int(batch), int(rounds)), f"batch = {batch}, rounds = {rounds}: 1 .. 65535 pairs of 1 .. {MAX_ROUNDS} samples")
 
 
 # --------------------------------------------------------------------------------------------------------------------- kernels

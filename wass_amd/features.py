@@ -255,10 +255,8 @@ def kaze_scratch_bytes(h: int, w: int, options: KazeOptions | None = None) -> in
     list found) and, with keep=True, three more planes for Lxx, Lxy, Lyy are not in the figure."""
     o = _check_options(options)
     _check_size(int(h), int(w), kaze_levels(o))
-    b = C.c_size_t()
-    if _lib.load().wass_kaze_scratch_bytes(int(h), int(w), o.n_octaves * o.n_sublevels, C.byref(b)) != 0:
-        raise ValueError(f"image: {h} x {w} with {o.n_octaves * o.n_sublevels} levels")
-    return b.value
+    levels = o.n_octaves * o.n_sublevels
+    return _lib.scratch_bytes("kaze", (int(h), int(w), levels), f"image: {h} x {w} with {levels} levels")
 
 
 # -------------------------------------------------------------------------------------------------------------------- pyramid

@@ -142,10 +142,7 @@ def _ints(v):
 
 def scratch_bytes(batch: int, n_max: int) -> int:
     """device memory one round over `batch` problems of at most n_max candidates takes (no GPU needed)"""
-    b = C.c_size_t()
-    if _lib.load().wass_match_scratch_bytes(int(batch), int(n_max), C.byref(b)) != 0:
-        raise ValueError(f"batch = {batch}, n_max = {n_max}: 1 .. 65535 problems of 1 .. {MAX_N} candidates")
-    return b.value
+    return _lib.scratch_bytes("match", (int(batch), int(n_max)), f"batch = {batch}, n_max = {n_max}: 1 .. 65535 problems of 1 .. {MAX_N} candidates")
 
 
 # ------------------------------------------------------------------------------------------------------------------ candidates

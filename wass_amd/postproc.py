@@ -13,7 +13,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .stereo import Context
+from .stereo import Context, _Handle, _is_device
 
 
 def _hann(n: int, sym: bool = True) -> np.ndarray:
@@ -88,7 +88,7 @@ def spectrum3d_plan(shape, du: float, dt: float) -> Spectrum3DPlan:
     return Spectrum3DPlan(nt, shift, starts, r0, c0, ny, nx, kx, ky, f, win_t, win_y, win_x, scale)
 
 
-class Spectrum3D:
+class Spectrum3D(_Handle):
     """wass_spec3d: one Welch accumulation of nt x ny x nx segments."""
 
     def __init__(self, ctx: Context, nt: int, ny: int, nx: int, win_t=None, win_y=None, win_x=None):
@@ -102,22 +102,8 @@ class Spectrum3D:
                                                C.byref(h)))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.ctx._lib.wass_spec3d_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    def _destroy(self, h):
+        self.ctx._lib.wass_spec3d_destroy(h)
 
     def push(self, seg: np.ndarray, datascale: float = 1.0):
         """seg: an nt x ny x nx float32 view of host memory whose last axis is contiguous (a slice of the cube: no copy)."""
@@ -356,10 +342,6 @@ def sosfiltfilt_scratch_bytes(count: int, H: int, W: int, padlen: int, slab_rows
                           f"{count}, {H}, {W}, padlen {padlen}")
 
 
-def _is_device(a) -> bool:
-    return hasattr(a, "data_ptr")
-
-
 def _host_f32_rows(a) -> np.ndarray:
     """a count x H x W float32 host array whose last axis is contiguous and whose other strides are whole, positive elements (a
     slice or a memmap passes as it is)."""
@@ -456,7 +438,7 @@ def butterworth_filter(data, dt: float, cutoff: float = 1.0, type: str = "lowpas
     return sosfiltfilt(sos, data, remove_mean=(type == "highpass" and not fast), ctx=ctx, out=out, slab_rows=slab_rows)
 
 
-class Spatial2DButterworth:
+class Spatial2DButterworth(_Handle):
     """The reference's class (spectra.py:176-202) on the GPU.  It is called there with W, H = XX.shape, so W is the number of ROWS
     of a surface and H the number of columns; butterworth_filter is the fftshifted transfer function [rows, cols], float64."""
 
@@ -484,16 +466,8 @@ class Spatial2DButterworth:
             self._h = h
         return self._h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._ctx._lib.wass_spatial_filter_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, h):
+        self._ctx._lib.wass_spatial_filter_destroy(h)
 
     def apply_batch(self, frames, out=None):
         """frames: n x rows x cols float32, host or device; the filtered frames, float32, on the same side.  A frame that holds a NaN

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .stereo import Context
+from .stereo import Context, _is_device
 
 # bit k of the C entry's `outputs` is PREP_OUTPUTS[k]
 PREP_OUTPUTS = ("stokes", "dolp", "aolp", "channels", "image_f32", "aolp_f32")
@@ -44,10 +44,6 @@ def _prep_outputs(outputs) -> int:
         if name not in PREP_OUTPUTS:
             raise ValueError(f"unknown output {name!r}: choose among {PREP_OUTPUTS}")
     return sum(1 << k for k, name in enumerate(PREP_OUTPUTS) if name in outputs)
-
-
-def _is_device(a) -> bool:
-    return type(a).__module__.split(".")[0] == "torch"
 
 
 def polarimetric_prepare(image, K, dist, hdr: bool = False, outputs=("stokes",), clahe=None, ctx: Context | None = None) -> PolarimetricFrame:

@@ -29,7 +29,7 @@ import dataclasses
 
 import numpy as np
 
-from .stereo import Context
+from .stereo import Context, _Handle, _is_device
 
 ADAM_BETA_1, ADAM_BETA_2 = 0.9, 0.999       # Keras's defaults, compiled into the library
 
@@ -71,8 +71,46 @@ def downsample_linear(Z, hc: int, wc: int) -> np.ndarray:
     return np.ascontiguousarray(rows[ys] * (one - fy)[:, np.newaxis] + rows[ys1] * fy[:, np.newaxis])
 
 
-def _is_device(a) -> bool:
-    return hasattr(a, "data_ptr")
+# ---- what VariationalRefinement and SequenceRefiner share: tensors on the context's device `dev`, and the set-up both copy there
+def _to_dev(a, dtype, dev):
+    import torch
+    if _is_device(a):
+        if a.device != dev:
+            raise ValueError(f"a tensor on {a.device}, the context is on {dev}")
+        return a.to(dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(dev).to(dtype).contiguous()
+
+
+def _new(dev, *shape):
+    import torch
+    t = torch.empty(shape, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    return t
+
+
+def _matrices(mats, names, flat: bool):
+    """Rp2c, Tp2c, P0cam, P1cam as flat fp64 arrays.  A refusal calls them by `names` and gives their size as one number (flat) or
+    as rows x columns."""
+    out = []
+    for name, m, shp in zip(names, mats, ((3, 3), (3,), (3, 4), (3, 4))):
+        a = np.ascontiguousarray(np.asarray(m, np.float64))
+        size = int(np.prod(shp))
+        if a.size != size or not np.isfinite(a).all():
+            raise ValueError(f"{name}: {size if flat else ' x '.join(map(str, shp))} finite values expected")
+        out.append(a.reshape(-1))
+    return out
+
+
+def _kernels() -> np.ndarray:
+    """the two 7 x 7 derivative-of-Gaussian kernels of the smoothness term, float32 [2, 7, 7]"""
+    dsx, dsy = derivative_of_gaussian_win(7, sigma=0.8)
+    return np.ascontiguousarray(np.stack([dsx, dsy]).astype(np.float32))
+
+
+def _scaled_grid(XX, YY, baseline, dev):
+    """XX / baseline, YY / baseline on the device with the reference's casts: fp64 quotients, then float32"""
+    import torch
+    return tuple((_to_dev(a, torch.float64, dev) / baseline).to(torch.float32).contiguous() for a in (XX, YY))
 
 
 @dataclasses.dataclass
@@ -83,7 +121,7 @@ class AdamState:
     step: int = 0
 
 
-class VariationalRefinement:
+class VariationalRefinement(_Handle):
     def __init__(self, I0, I1, Rp2c, Tp2c, P0cam, P1cam, XX, YY, baseline, mask, ctx: Context | None = None):
         shape = tuple(int(v) for v in XX.shape)
         if len(shape) != 2 or tuple(YY.shape) != shape or tuple(mask.shape) != shape:
@@ -96,27 +134,17 @@ class VariationalRefinement:
         baseline = float(baseline)
         if not np.isfinite(baseline) or baseline == 0:
             raise ValueError("baseline must be finite and not 0")
-        mats = []
-        for name, m, shp in (("Rp2c", Rp2c, (3, 3)), ("Tp2c", Tp2c, (3,)), ("P0cam", P0cam, (3, 4)), ("P1cam", P1cam, (3, 4))):
-            a = np.ascontiguousarray(np.asarray(m, np.float64))
-            if a.size != int(np.prod(shp)) or not np.isfinite(a).all():
-                raise ValueError(f"{name}: {' x '.join(map(str, shp))} finite values expected")
-            mats.append(a.reshape(-1))
+        mats = _matrices((Rp2c, Tp2c, P0cam, P1cam), ("Rp2c", "Tp2c", "P0cam", "P1cam"), flat=False)
         self.shape = shape
         self.coarse_shape = (shape[0] // 2, shape[1] // 2)
         self.losses = np.zeros((0, 4))
         self.state = None                                        # the AdamState the last optimize() ended with
-        self._h = None
         self._ctx = ctx if ctx is not None else Context(0)
         import torch
         self._dev = torch.device("cuda", self._ctx.device_id)
-        # the reference's casts: fp64 quotients, then float32
-        xb = self._to_dev(XX, torch.float64) / baseline
-        yb = self._to_dev(YY, torch.float64) / baseline
-        planes = [xb.to(torch.float32).contiguous(), yb.to(torch.float32).contiguous(), self._to_dev(mask, torch.float32),
-                  self._to_dev(I0, torch.float32), self._to_dev(I1, torch.float32)]
-        dsx, dsy = derivative_of_gaussian_win(7, sigma=0.8)
-        kernels = np.ascontiguousarray(np.stack([dsx, dsy]).astype(np.float32))
+        planes = [*_scaled_grid(XX, YY, baseline, self._dev), _to_dev(mask, torch.float32, self._dev),
+                  _to_dev(I0, torch.float32, self._dev), _to_dev(I1, torch.float32, self._dev)]
+        kernels = _kernels()
         torch.cuda.synchronize(self._dev)
         h = C.c_void_p()
         dp = C.POINTER(C.c_double)
@@ -127,15 +155,10 @@ class VariationalRefinement:
             planes[3].data_ptr(), int(ih0), int(iw0), planes[4].data_ptr(), int(ih1), int(iw1), kernels.ctypes.data, C.byref(h)))
         self._h = h                                              # the library has copied everything it keeps
 
-    # ---- plumbing
-    def _to_dev(self, a, dtype):
-        import torch
-        if _is_device(a):
-            if a.device != self._dev:
-                raise ValueError(f"a tensor on {a.device}, the context is on {self._dev}")
-            return a.to(dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(self._dev).to(dtype).contiguous()
+    def _destroy(self, h):
+        self._ctx._lib.wass_vref_destroy(h)
 
+    # ---- plumbing
     def _plane(self, Z, shape, name):
         """Z as a contiguous float32 device tensor of `shape`, finite; and whether the caller's was a device tensor"""
         import torch
@@ -144,45 +167,22 @@ class VariationalRefinement:
         dev = _is_device(Z)
         if not dev and not np.isfinite(np.asarray(Z)).all():
             raise ValueError(f"{name} holds a value that is not finite")
-        d = self._to_dev(Z, torch.float32)
+        d = _to_dev(Z, torch.float32, self._dev)
         if dev and not bool(torch.isfinite(d).all()):
             raise ValueError(f"{name} holds a value that is not finite")
         torch.cuda.synchronize(self._dev)
         return d, dev
 
-    def _new(self, *shape):
-        import torch
-        t = torch.empty(shape, dtype=torch.float32, device=self._dev)
-        torch.cuda.synchronize(self._dev)
-        return t
-
     @staticmethod
     def _back(t, dev):
         return t if dev else t.cpu().numpy()
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._ctx._lib.wass_vref_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ---- the reference's methods
     def sample_images(self, Z):
         """(I0_samp, I1_samp, cam0_p2, cam1_p2): the masked samples, Ny x Nx, and the pixel coordinates, (Ny * Nx) x 2 as (x, y)."""
         import torch
         d, dev = self._plane(Z, self.shape, "Z")
-        i0, i1, uv = self._new(*self.shape), self._new(*self.shape), self._new(4, *self.shape)
+        i0, i1, uv = _new(self._dev, *self.shape), _new(self._dev, *self.shape), _new(self._dev, 4, *self.shape)
         self._ctx._check(self._ctx._lib.wass_vref_sample(self._h, d.data_ptr(), i0.data_ptr(), i1.data_ptr(), uv.data_ptr()))
         p0 = torch.stack([uv[0].reshape(-1), uv[1].reshape(-1)], dim=1)
         p1 = torch.stack([uv[2].reshape(-1), uv[3].reshape(-1)], dim=1)
@@ -191,7 +191,7 @@ class VariationalRefinement:
     def compute_Z_gradient(self, Z):
         """(Z_dx, Z_dy): Z correlated with the two 7 x 7 derivative-of-Gaussian kernels (sigma 0.8), zero padding."""
         d, dev = self._plane(Z, self.shape, "Z")
-        zdx, zdy = self._new(*self.shape), self._new(*self.shape)
+        zdx, zdy = _new(self._dev, *self.shape), _new(self._dev, *self.shape)
         self._ctx._check(self._ctx._lib.wass_vref_zgrad(self._h, d.data_ptr(), zdx.data_ptr(), zdy.data_ptr()))
         return self._back(zdx, dev), self._back(zdy, dev)
 
@@ -206,8 +206,8 @@ class VariationalRefinement:
         """The gradient of data_loss + alpha * smoothness_loss of resize(Zc) with respect to the coarse field Zc; with full=True
         also with respect to the full-resolution surface: (gC, gZ)."""
         d, dev = self._plane(Zc, self.coarse_shape, "Zc")
-        gc = self._new(*self.coarse_shape)
-        gz = self._new(*self.shape) if full else None
+        gc = _new(self._dev, *self.coarse_shape)
+        gz = _new(self._dev, *self.shape) if full else None
         self._ctx._check(self._ctx._lib.wass_vref_gradient(self._h, d.data_ptr(), float(alpha), gc.data_ptr(), gz.data_ptr() if full else None))
         return (self._back(gc, dev), self._back(gz, dev)) if full else self._back(gc, dev)
 
@@ -216,7 +216,7 @@ class VariationalRefinement:
         with the flipped kernels) and gC the adjoint of the resize applied to gZ."""
         planes = [self._plane(a, self.shape, n) for a, n in ((Zdx, "Zdx"), (Zdy, "Zdy"), (gd, "gd"))]
         dev = planes[0][1]
-        gc, gz = self._new(*self.coarse_shape), self._new(*self.shape)
+        gc, gz = _new(self._dev, *self.coarse_shape), _new(self._dev, *self.shape)
         self._ctx._check(self._ctx._lib.wass_vref_adjoint(self._h, planes[0][0].data_ptr(), planes[1][0].data_ptr(), planes[2][0].data_ptr(),
                                                           float(alpha), gc.data_ptr(), gz.data_ptr()))
         return self._back(gc, dev), self._back(gz, dev)
@@ -235,7 +235,7 @@ class VariationalRefinement:
             m, v, step = torch.zeros_like(d), torch.zeros_like(d), 0
         else:
             m, v, step = self._plane(state.m, self.coarse_shape, "state.m")[0].clone(), self._plane(state.v, self.coarse_shape, "state.v")[0].clone(), int(state.step)
-        z = self._new(*self.shape)
+        z = _new(self._dev, *self.shape)
         torch.cuda.synchronize(self._dev)
         every = int(report_every)
         cap = 2 + ((iters + every - 1) // every if every > 0 else 0)
@@ -312,7 +312,7 @@ def _plane_to_camera(gridsetup):
     return baseline, Rp2c, Tp2c
 
 
-class SequenceRefiner:
+class SequenceRefiner(_Handle):
     """The handle of a sequence's refinement: XX / b, YY / b, the cameras, the kernels and the axis tables are copied to the device
     once, with room for `batch` frames.  gridsetup: setup_grid's mapping (Rpl, Tpl, P0cam, P1cam, XX, YY, CAM_BASELINE);
     image_shapes: ((ih0, iw0), (ih1, iw1)).  refine() may be called any number of times, with 1 .. batch frames each."""
@@ -331,20 +331,12 @@ class SequenceRefiner:
         self.batch = int(batch)
         if self.batch < 1:
             raise ValueError("batch must be at least 1")
-        mats = []
-        for name, m, size in (("Rpl", Rp2c, 9), ("Tpl", Tp2c, 3), ("P0cam", gridsetup["P0cam"], 12), ("P1cam", gridsetup["P1cam"], 12)):
-            a = np.ascontiguousarray(np.asarray(m, np.float64))
-            if a.size != size or not np.isfinite(a).all():
-                raise ValueError(f"{name}: {size} finite values expected")
-            mats.append(a.reshape(-1))
+        mats = _matrices((Rp2c, Tp2c, gridsetup["P0cam"], gridsetup["P1cam"]), ("Rpl", "Tpl", "P0cam", "P1cam"), flat=True)
         self.losses = []                                         # per frame of the last refine(): rows [steps, data, smoothness, energy]
-        self._h = None
         self._ctx = ctx if ctx is not None else Context(0)
         self._dev = torch.device("cuda", self._ctx.device_id)
-        xb = (self._to_dev(XX, torch.float64) / self.baseline).to(torch.float32).contiguous()     # fp64 quotients, then float32
-        yb = (self._to_dev(YY, torch.float64) / self.baseline).to(torch.float32).contiguous()
-        dsx, dsy = derivative_of_gaussian_win(7, sigma=0.8)
-        kernels = np.ascontiguousarray(np.stack([dsx, dsy]).astype(np.float32))
+        xb, yb = _scaled_grid(XX, YY, self.baseline, self._dev)
+        kernels = _kernels()
         torch.cuda.synchronize(self._dev)
         h = C.c_void_p()
         dp = C.POINTER(C.c_double)
@@ -355,30 +347,8 @@ class SequenceRefiner:
         self._h = h
         self._n = 0
 
-    def _to_dev(self, a, dtype):
-        import torch
-        if _is_device(a):
-            if a.device != self._dev:
-                raise ValueError(f"a tensor on {a.device}, the context is on {self._dev}")
-            return a.to(dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(self._dev).to(dtype).contiguous()
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._ctx._lib.wass_vref_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    def _destroy(self, h):
+        self._ctx._lib.wass_vref_batch_destroy(h)
 
     def _call(self, rc, first_frame=0):
         """a refusal that names a frame becomes a ValueError with the frame's index in the caller's sequence"""
@@ -404,10 +374,10 @@ class SequenceRefiner:
         for name, I, shp in (("I0", I0, self.image_shapes[0]), ("I1", I1, self.image_shapes[1])):
             if tuple(int(v) for v in I.shape) != (n,) + shp:
                 raise ValueError(f"{name} of shape {tuple(I.shape)}, expected {(n,) + shp}")
-        keep = [self._to_dev(Zi, torch.float32), self._to_dev(I0, torch.float32), self._to_dev(I1, torch.float32)]
+        keep = [_to_dev(Zi, torch.float32, self._dev), _to_dev(I0, torch.float32, self._dev), _to_dev(I1, torch.float32, self._dev)]
         d_mask = None
         if mask is not None:
-            d_mask = self._to_dev(mask, torch.float32)
+            d_mask = _to_dev(mask, torch.float32, self._dev)
             if tuple(d_mask.shape) == self.shape:
                 d_mask = d_mask.expand(n, *self.shape).contiguous()
             if tuple(d_mask.shape) != (n,) + self.shape:
@@ -418,19 +388,13 @@ class SequenceRefiner:
                                                        keep[1].data_ptr(), keep[2].data_ptr(), self.baseline), first_frame)
         self._n = n
 
-    def _new(self, *shape):
-        import torch
-        t = torch.empty(shape, dtype=torch.float32, device=self._dev)
-        torch.cuda.synchronize(self._dev)
-        return t
-
     def set_state(self, Zc, m=None, v=None, step=0):
         """the coarse fields (n x Hc x Wc) and the optimiser's state of the loaded frames; m, v default to zeros"""
         import torch
         shape = (self._n,) + self.coarse_shape
         t = []
         for name, a in (("Zc", Zc), ("m", m), ("v", v)):
-            d = torch.zeros(shape, dtype=torch.float32, device=self._dev) if a is None else self._to_dev(a, torch.float32)
+            d = torch.zeros(shape, dtype=torch.float32, device=self._dev) if a is None else _to_dev(a, torch.float32, self._dev)
             if tuple(d.shape) != shape:
                 raise ValueError(f"{name} of shape {tuple(d.shape)}, expected {shape}")
             t.append(d)
@@ -439,7 +403,7 @@ class SequenceRefiner:
 
     def get_state(self):
         """(Zc, m, v, step) of the loaded frames: device tensors n x Hc x Wc"""
-        t = [self._new(self._n, *self.coarse_shape) for _ in range(3)]
+        t = [_new(self._dev, self._n, *self.coarse_shape) for _ in range(3)]
         st = C.c_int64(0)
         self._call(self._ctx._lib.wass_vref_batch_get_state(self._h, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), C.byref(st)))
         return t[0], t[1], t[2], int(st.value)
@@ -462,10 +426,10 @@ class SequenceRefiner:
         import torch
         shape = (self._n,) + self.shape
         if out is None:
-            out = self._new(*shape)
+            out = _new(self._dev, *shape)
         elif not _is_device(out) or tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError(f"out: a contiguous float32 device tensor of shape {shape} expected")
-        z = self._new(*shape) if with_plane else None
+        z = _new(self._dev, *shape) if with_plane else None
         torch.cuda.synchronize(self._dev)
         self._call(self._ctx._lib.wass_vref_batch_result(self._h, out.data_ptr(), z.data_ptr() if with_plane else None))
         return (out, z) if with_plane else out
@@ -502,7 +466,7 @@ def refine_sequence(Zi, I0, I1, gridsetup, mask=None, options: RefineOptions | N
     nb = max(1, min(int(o.batch), n))
     losses = []
     with SequenceRefiner(gridsetup, (tuple(I0.shape[1:]), tuple(I1.shape[1:])), nb, ctx) as sr:
-        d_mask = None if mask is None or per_frame_mask else sr._to_dev(mask, torch.float32)
+        d_mask = None if mask is None or per_frame_mask else _to_dev(mask, torch.float32, sr._dev)
         for i0 in range(0, n, nb):
             k = slice(i0, min(n, i0 + nb))
             part = (lambda a: a[k] if _is_device(a) else np.ascontiguousarray(a[k]))

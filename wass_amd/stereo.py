@@ -24,21 +24,22 @@ def dense_input_size(w: int, h: int, dense_scale: float):
     return ws.value, hs.value
 
 
-class Context:
-    """One GPU, one stream, its scratch HBM (wass_ctx)."""
+def _is_device(a) -> bool:
+    """a device tensor, not a host array"""
+    return hasattr(a, "data_ptr")
 
-    def __init__(self, device_id: int = 0):
-        self._lib = _lib.load()
-        h = C.c_void_p()
-        rc = self._lib.wass_ctx_create(device_id, C.byref(h))
-        if rc != 0:
-            raise WassError(rc, "wass_ctx_create failed (no usable GPU?)")
-        self._h = h
-        self.device_id = device_id
+
+class _Handle:
+    """An object of the library behind _h, given back once: by close(), at the end of a `with` block, or when the Python object
+    goes.  A subclass says in _destroy(h) which entry takes it back."""
+    _h = None
+
+    def _destroy(self, h):
+        raise NotImplementedError
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.wass_ctx_destroy(self._h)
+        if self._h:
+            self._destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -50,8 +51,24 @@ class Context:
     def __enter__(self):
         return self
 
-    def __exit__(self, *a):
+    def __exit__(self, *exc):
         self.close()
+
+
+class Context(_Handle):
+    """One GPU, one stream, its scratch HBM (wass_ctx)."""
+
+    def __init__(self, device_id: int = 0):
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        rc = self._lib.wass_ctx_create(device_id, C.byref(h))
+        if rc != 0:
+            raise WassError(rc, "wass_ctx_create failed (no usable GPU?)")
+        self._h = h
+        self.device_id = device_id
+
+    def _destroy(self, h):
+        self._lib.wass_ctx_destroy(h)
 
     def _check(self, rc: int, allow=()):
         if rc != 0 and rc not in allow:
@@ -582,7 +599,7 @@ def quantiles_launch_shape():
     return a.value, b.value
 
 
-class GridSequence:
+class GridSequence(_Handle):
     """What the reference's grid() keeps across the frames of a sequence (wass_grid_seq): per-frame nanmean / nanmin / nanmax, the
     per-point fp64 sum, the millimetre slices, and at the end zmin / zmax / zmean, the per-point mean and the zero-mean pass."""
 
@@ -593,16 +610,8 @@ class GridSequence:
         self._h = h
         self.n_frames = 0
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.ctx._lib.wass_grid_seq_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, h):
+        self.ctx._lib.wass_grid_seq_destroy(h)
 
     def push_dev(self, d_zi, d_z_mm=None):
         """d_zi: float32 device tensor n x height x width (metres), frames in sequence order; d_z_mm (same shape, optional)
@@ -628,7 +637,7 @@ class GridSequence:
         self.ctx._check(self.ctx._lib.wass_grid_seq_zero_mean_dev(self._h, d_z_mm.data_ptr(), n))
 
 
-class Mesh:
+class Mesh(_Handle):
     """Device-resident organised point cloud (wass_mesh) -- the PovMesh of the reference."""
 
     def __init__(self, ctx: Context, handle):
@@ -637,16 +646,8 @@ class Mesh:
         ctx._lib.wass_mesh_size(handle, C.byref(w), C.byref(h))
         self.width, self.height = w.value, h.value
 
-    def close(self):
-        if self._h:
-            self.ctx._lib.wass_mesh_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self, h):
+        self.ctx._lib.wass_mesh_destroy(h)
 
     def download(self):
         n = self.width * self.height
