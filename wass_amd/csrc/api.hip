@@ -33,10 +33,9 @@ int ensure(wass_ctx* c, Buf& b, size_t bytes)
     return WASS_OK;
 }
 
-static void release(Buf& b)
+Buf::~Buf()
 {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
+    if (p) (void)hipFree(p);
 }
 
 // derived parameters
@@ -158,10 +157,6 @@ void wass_ctx_destroy(wass_ctx* c)
     coll_release(c);
     mesh_pool_ctx_alive(c, false);
     mesh_pool_purge(c);
-    for (Buf* b : { &c->bt1, &c->bt2, &c->hsum, &c->C, &c->S, &c->ckpt, &c->sel_d16, &c->sel_key, &c->raw,
-                    &c->flags, &c->tmp_in0, &c->tmp_in1, &c->tmp_out, &c->tmp_mask, &c->fA, &c->fB, &c->fC, &c->fD, &c->fE, &c->uf, &c->rs_r, &c->rs_l, &c->raw2, &c->grid, &c->dct, &c->dct_io, &c->scratch, &c->counters, &c->tri_cnt, &c->inl, &c->inl2, &c->clahe_lut, &c->prep_pol, &c->qsel, &c->ccmask, &c->und_cache[0].xy, &c->und_cache[1].xy, &c->dstate, &c->rect_tab, &c->lanczos_tab, &c->bilinear_tab, &c->rect_mx, &c->rect_my, &c->xyzc, &c->limits, &c->jpeg_scratch, &c->jpeg_huff,
-                    &c->jpeg_out, &c->jpeg_info, &c->jpeg_part, &c->match, &c->match_io, &c->epi, &c->ac })
-        release(*b);
     for (auto& e : c->ev_dbg) if (e) (void)hipEventDestroy(e);
     for (auto& k : c->kev) { if (k.a) (void)hipEventDestroy(k.a); if (k.b) (void)hipEventDestroy(k.b); }
     if (c->h_dbg_info) (void)hipHostFree(c->h_dbg_info);
@@ -184,7 +179,7 @@ void wass_ctx_destroy(wass_ctx* c)
     if (c->ev_pack) (void)hipEventDestroy(c->ev_pack);
     for (auto& u : c->uploads) if (u.ev) (void)hipEventDestroy(u.ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                // frees every Buf: the device is selected and no stream has work left
 }
 
 const char* wass_last_error(const wass_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -490,7 +485,6 @@ int wass_sgm_selftest(wass_ctx* c, int w, int h, int num_disp, int ndirs, uint64
     unsigned long long hc = ~0ull;
     if (e == hipSuccess && rc == WASS_OK) e = hipMemcpyAsync(&hc, d_count, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(s2.p);
     if (rc != WASS_OK) return rc;
     if (e != hipSuccess) return set_err(c, WASS_ERR_DEVICE, "self-test: %s", hipGetErrorString(e));
     *mismatches = hc;

@@ -335,33 +335,28 @@ struct AcPlan {
     int* d_counts = nullptr;
 };
 
-static size_t ac_up(size_t v) { return (v + 255) & ~(size_t)255; }
 static size_t ac_blocks(int n) { return ((size_t)n + AC_WG - 1) / AC_WG; }
 
-static size_t ac_ctx_bytes(int n)
+// the layout of c->ac for n points: the counts, then six arrays of doubles
+static void ac_carve(AcPlan& pl, int n, Carve& a)
 {
     const size_t N = (size_t)n, d = sizeof(double);
-    return 256 + ac_up(AC_PART * d) + ac_up(ac_blocks(n) * AC_PART * d) + ac_up(AC_LIN * N * d) + ac_up(6 * N * d) + 2 * ac_up(3 * N * d);
+    pl.n = n; pl.nb = (int)ac_blocks(n);
+    pl.d_counts = a.take<int>(256);
+    pl.d_rec = a.take<double>(AC_PART * d);
+    pl.d_part = a.take<double>(pl.nb * AC_PART * d);
+    pl.d_lin = a.take<double>(AC_LIN * N * d);
+    pl.d_vinv = a.take<double>(6 * N * d);
+    pl.d_db = a.take<double>(3 * N * d);
+    pl.d_ptsn = a.take<double>(3 * N * d);
 }
+
+static size_t ac_ctx_bytes(int n) { AcPlan pl; return measure([&](Carve& a) { ac_carve(pl, n, a); }); }
 
 static int ac_plan(wass_ctx* c, int n, AcPlan* pl)
 {
     if (n < 1 || n > WASS_AC_MAX_N) return set_err(c, WASS_ERR_INVALID_ARG, "n = %d: 1 .. %d points", n, WASS_AC_MAX_N);
-    int rc = ensure(c, c->ac, ac_ctx_bytes(n));
-    if (rc) return rc;
-    const size_t N = (size_t)n, d = sizeof(double);
-    char* base = (char*)c->ac.p;
-    pl->n = n;
-    pl->nb = (int)ac_blocks(n);
-    pl->d_counts = (int*)base;
-    size_t off = 256;
-    pl->d_rec = (double*)(base + off); off += ac_up(AC_PART * d);
-    pl->d_part = (double*)(base + off); off += ac_up(ac_blocks(n) * AC_PART * d);
-    pl->d_lin = (double*)(base + off); off += ac_up(AC_LIN * N * d);
-    pl->d_vinv = (double*)(base + off); off += ac_up(6 * N * d);
-    pl->d_db = (double*)(base + off); off += ac_up(3 * N * d);
-    pl->d_ptsn = (double*)(base + off);
-    return WASS_OK;
+    return carve_buf(c, c->ac, [&](Carve& a) { ac_carve(*pl, n, a); });
 }
 
 // the partial results of the last kernel to one record on the host; returns after a synchronisation

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/wass_gpu.h"
+#include "scratch.h"
 
 namespace wass {
 
@@ -96,11 +97,6 @@ struct SgmDims {
 // pitch (in u16) of one mirrored image-2 plane; the slack absorbs reads of padded disparity slots past the row
 constexpr int BT2_FRONT = 128;    // u16 elements of slack in front of the first plane (group loads may start a few elements early)
 static inline int bt2_pitch(int Wp) { return (Wp + 1024 + 63) & ~63; }
-
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
 
 }  // namespace wass
 
@@ -247,7 +243,6 @@ struct wass_mesh {
 namespace wass {
 
 int set_err(wass_ctx* c, int code, const char* fmt, ...);
-int ensure(wass_ctx* c, Buf& b, size_t bytes);
 
 #define WASS_HIP(ctx, call)                                                                 \
     do {                                                                                    \

@@ -3,7 +3,7 @@
 // ordered-key maxima of their kernels.  Plain functions and one RAII struct; every operator keeps its own plan and byte formula.
 // A call makes ONE hipMalloc and one hipFree by design: the scratch of a cube is gigabytes and is not kept in the context.
 // The handles of spectrum.hip (wass_spec3d, wass_spatial_filter) hold an Arena for their lifetime and stage through the same
-// functions; vref.hip takes align256.
+// functions.  The piece-by-piece hand-out itself (Carve, align256) is scratch.h's, which the context's pool shares.
 #pragma once
 
 #include "common.h"
@@ -11,15 +11,9 @@
 namespace wass {
 
 // ---------------------------------------------------------------- host side
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// One hipMalloc of `total` bytes, handed out in 256-aligned pieces in the order asked, freed when the struct goes out of scope.
-// A total of 0 makes no call at all, and every piece of it is a pointer nobody may follow.  An Arena that has reserved nothing
-// measures: take() hands out nullptr and still counts, so the function that carves a layout, run on a fresh Arena, leaves the
-// layout's size in `used`.
-struct Arena {
-    char* mem = nullptr;
-    size_t used = 0;
+// A Carve over ONE hipMalloc of `total` bytes, freed when the struct goes out of scope.  A total of 0 makes no call at all, and
+// every piece of it is a pointer nobody may follow.  An Arena that has reserved nothing measures, as every Carve without memory.
+struct Arena : Carve {
     Arena() = default;
     Arena(const Arena&) = delete;
     Arena& operator=(const Arena&) = delete;
@@ -28,12 +22,6 @@ struct Arena {
     {
         if (total && hipMalloc((void**)&mem, total) != hipSuccess) return set_err(c, WASS_ERR_NO_MEMORY, "hipMalloc(%zu) for %s failed", total, what);
         return WASS_OK;
-    }
-    template <class T> T* take(size_t bytes)
-    {
-        T* p = mem ? (T*)(mem + used) : nullptr;
-        used += align256(bytes);
-        return p;
     }
 };
 

@@ -657,14 +657,21 @@ struct EpiPlan {
     std::vector<int> dims;                                   // the upload's source: lives until the call's last synchronisation
 };
 
-static size_t epi_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static size_t epi_ctx_bytes(int batch, int rounds)
+// the layout of c->epi for a batch and its rounds (rounds == 0: the flag, the sizes, the best and its model alone)
+static void epi_carve(EpiPlan& pl, int batch, int rounds, Carve& a)
 {
     const size_t b = (size_t)batch, k = (size_t)rounds * EPI_SOL;
-    return 256 + epi_up(2 * b * sizeof(int)) + epi_up(b * sizeof(EpiBest)) + epi_up(b * 9 * sizeof(double)) + epi_up(b * rounds * sizeof(int)) +
-           epi_up(b * k * sizeof(int)) + epi_up(b * k * 9 * sizeof(double));
+    pl.batch = batch;
+    pl.d_flag = a.take<int>(256);
+    pl.d_dims = a.take<int>(2 * b * sizeof(int));
+    pl.d_best = a.take<EpiBest>(b * sizeof(EpiBest));
+    pl.d_Ebest = a.take<double>(b * 9 * sizeof(double));
+    pl.d_nsol = a.take<int>(b * rounds * sizeof(int));
+    pl.d_counts = a.take<int>(b * k * sizeof(int));
+    pl.d_E = a.take<double>(b * k * 9 * sizeof(double));
 }
+
+static size_t epi_ctx_bytes(int batch, int rounds) { EpiPlan pl; return measure([&](Carve& a) { epi_carve(pl, batch, rounds, a); }); }
 
 // checks the sizes of a batch, lays the context's scratch out (rounds == 0: the sizes and the flag alone) and enqueues the upload
 static int epi_plan(wass_ctx* c, const int* m, const double* t, int batch, int rounds, size_t pt_stride, size_t out_stride, bool outputs, EpiPlan* pl,
@@ -680,20 +687,10 @@ static int epi_plan(wass_ctx* c, const int* m, const double* t, int batch, int r
     }
     if (batch > 1 && pt_stride < 2 * (size_t)mmax) return set_err(c, WASS_ERR_INVALID_ARG, "pt_stride is shorter than the largest pair (%d matches)", mmax);
     if (outputs && batch > 1 && out_stride < (size_t)mmax) return set_err(c, WASS_ERR_INVALID_ARG, "out_stride is shorter than the largest pair (%d matches)", mmax);
-    int rc = ensure(c, c->epi, epi_ctx_bytes(batch, rounds));
+    int rc = carve_buf(c, c->epi, [&](Carve& a) { epi_carve(*pl, batch, rounds, a); });
     if (rc) return rc;
-    char* base = (char*)c->epi.p;
-    const size_t b = (size_t)batch, k = (size_t)rounds * EPI_SOL;
-    pl->batch = batch;
+    const size_t b = (size_t)batch;
     pl->mmax = mmax;
-    pl->d_flag = (int*)base;
-    size_t off = 256;
-    pl->d_dims = (int*)(base + off); off += epi_up(2 * b * sizeof(int));
-    pl->d_best = (EpiBest*)(base + off); off += epi_up(b * sizeof(EpiBest));
-    pl->d_Ebest = (double*)(base + off); off += epi_up(b * 9 * sizeof(double));
-    pl->d_nsol = (int*)(base + off); off += epi_up(b * rounds * sizeof(int));
-    pl->d_counts = (int*)(base + off); off += epi_up(b * k * sizeof(int));
-    pl->d_E = (double*)(base + off);
     pl->dims.assign(2 * b, 0);
     for (int p = 0; p < batch; ++p) {
         const float thr = t ? (float)(t[p] * t[p]) : 0.0f;

@@ -197,21 +197,21 @@ static int grid_bin(wass_ctx* c, const wass_mesh* m, const wass_grid_setup* gs, 
     if (ng > 0x7FFFFFF0ull) return set_err(c, WASS_ERR_UNSUPPORTED, "grid too large");
     const bool median = cell_statistic == WASS_GRID_CELL_MEDIAN;
     int rc;
-    // [sum i64 | zi f64 | cellval f64 | out f32 | cnt u32 | off u32 | fill u32 | dil u8 | mask u8]  (+ per point: pz f64, vals f64, pcell u32)
-    const size_t bytes = ng * (8 + 8 + 8 + 4 + 4 + 4 + 4 + 1 + 1) + (median ? n * (8 + 8 + 4) : 0) + 256;
-    if ((rc = ensure(c, c->grid, bytes))) return rc;
-    long long* sum = (long long*)c->grid.p;
-    double* zi = (double*)(sum + ng);
-    double* cellval = zi + ng;
-    double* pz = cellval + ng;                               // median mode only
-    double* vals = pz + (median ? n : 0);
-    float* out = (float*)(vals + (median ? n : 0));
-    unsigned int* cnt = (unsigned int*)(out + ng);
-    unsigned int* off = cnt + ng;
-    unsigned int* fill = off + ng;
-    unsigned int* pcell = fill + ng;                         // median mode only
-    uint8_t* dil = (uint8_t*)(pcell + (median ? n : 0));
-    uint8_t* mask = dil + ng;
+    // Per cell, and per point in median mode only.  Every kernel stops at its array's last cell or point (the 5 x 5 windows skip
+    // what lies outside the grid, and the cells' segments of vals add up to at most n), so no piece needs room behind it.
+    long long* sum;
+    double *zi, *cellval, *pz = nullptr, *vals = nullptr;
+    float* out;
+    unsigned int *cnt, *off, *fill, *pcell = nullptr;
+    uint8_t *dil, *mask;
+    if ((rc = carve_buf(c, c->grid, [&](Carve& a) {
+            sum = a.take<long long>(ng * 8); zi = a.take<double>(ng * 8); cellval = a.take<double>(ng * 8);
+            out = a.take<float>(ng * 4);
+            cnt = a.take<unsigned int>(ng * 4); off = a.take<unsigned int>(ng * 4); fill = a.take<unsigned int>(ng * 4);
+            dil = a.take<uint8_t>(ng); mask = a.take<uint8_t>(ng);
+            if (median) { pz = a.take<double>(n * 8); vals = a.take<double>(n * 8); pcell = a.take<unsigned int>(n * 4); }
+        })))
+        return rc;
     memcpy(g.R, gs->R, sizeof g.R); memcpy(g.T, gs->T, sizeof g.T);
     g.baseline = gs->baseline; g.xmin = gs->xmin; g.ymin = gs->ymin;
     g.xext = gs->xmax - gs->xmin; g.yext = gs->ymax - gs->ymin; g.wm1 = gs->width - 1; g.hm1 = gs->height - 1;

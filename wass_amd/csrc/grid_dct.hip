@@ -393,20 +393,32 @@ static void dct_shape(int W, int H, int nf, DctPlan& p)
     p.nloss = ((nct + 3) / 4) * nrb;
 }
 
-// floats one frame takes in c->dct
-static size_t dct_frame_floats(const DctPlan& p)
+// The layout of c->dct for nb frames of the shape in p: the doubles, the two bases and g, which the frames share, then nb frames
+// back to back in every other array.  Every kernel indexes a frame's arrays by the padded sizes they are taken with here (tiles
+// of 16 inside Hp, Wp and nfp; ntile and nloss are the grids of k_dct_step and k_dct_recon): nothing reaches past a piece.
+static void dct_carve(DctPlan& p, int nb, Carve& a)
 {
-    const size_t nfp2 = (size_t)p.nfp * p.nfp, hw = (size_t)p.Hp * p.Wp;
-    return 2 * hw + 3 * nfp2 + (size_t)p.nfp * p.Wp + (size_t)p.nchunk * p.Hp * p.nfp + p.ntile + 3;
+    const size_t n = (size_t)nb, nfp2 = (size_t)p.nfp * p.nfp * 4, hw = (size_t)p.Hp * p.Wp * 4;
+    p.nb = nb;
+    p.lossp = a.take<double>(n * p.nloss * 8); p.res = a.take<double>(n * 4 * 8);
+    p.Ay = a.take<float>((size_t)p.nfp * p.Hp * 4); p.Ax = a.take<float>((size_t)p.nfp * p.Wp * 4); p.g = a.take<float>(nfp2);
+    p.zp = a.take<float>(n * hw); p.out = a.take<float>(n * hw);
+    p.x = a.take<float>(n * nfp2); p.prev = a.take<float>(n * nfp2); p.step = a.take<float>(n * nfp2);
+    p.T = a.take<float>(n * p.nfp * p.Wp * 4);
+    p.Up = a.take<float>(n * p.nchunk * p.Hp * p.nfp * 4);
+    p.tmax = a.take<float>(n * p.ntile * 4);
+    p.scal = a.take<float>(n * 4); p.cnt = a.take<int>(n * 4); p.act = a.take<int>(n * 4);
 }
 
 // Frames one set of launches takes: the scratch of a sub-batch stays below 1 GiB (a 1024 x 1024, Nf 150 frame takes 14 MB) and
-// blockIdx.z below its limit.  Results do not depend on it.
+// blockIdx.z below its limit.  A frame alone takes no less than its share of a batch, so nb frames fit where nb * per do.
+// Results do not depend on it.
 static int dct_sub_batch(int W, int H, int nf, int n_frames)
 {
     DctPlan p;
     dct_shape(W, H, nf, p);
-    const size_t per = dct_frame_floats(p) * 4 + (size_t)(p.nloss + 4) * 8;
+    const auto bytes = [&](int nb) { return measure([&](Carve& a) { dct_carve(p, nb, a); }); };
+    const size_t per = bytes(1) - bytes(0);                  // without a frame the shared arrays are all there is
     size_t nb = ((size_t)1 << 30) / per;
     if (nb > 1024) nb = 1024;
     if (nb < 1) nb = 1;
@@ -416,31 +428,7 @@ static int dct_sub_batch(int W, int H, int nf, int n_frames)
 static int dct_plan(wass_ctx* c, int W, int H, int nf, int nb, DctPlan& p)
 {
     dct_shape(W, H, nf, p);
-    p.nb = nb;
-    const size_t nfp2 = (size_t)p.nfp * p.nfp, hw = (size_t)p.Hp * p.Wp;
-    const size_t fl = (size_t)p.nfp * p.Hp + (size_t)p.nfp * p.Wp + nfp2 + nb * dct_frame_floats(p) + 16;
-    const size_t nd = ((size_t)nb * (p.nloss + 4) + 3) & ~(size_t)3;    // doubles in front: keeps the float arrays 32-byte aligned
-    const size_t bytes = fl * 4 + nd * 8 + 64;
-    int rc;
-    if ((rc = ensure(c, c->dct, bytes))) return rc;
-    double* d = (double*)c->dct.p;
-    p.lossp = d; p.res = d + (size_t)nb * p.nloss; d += nd;
-    float* f = (float*)d;
-    p.Ay = f; f += (size_t)p.nfp * p.Hp;
-    p.Ax = f; f += (size_t)p.nfp * p.Wp;
-    p.g = f; f += nfp2;
-    p.zp = f; f += nb * hw;
-    p.out = f; f += nb * hw;
-    p.x = f; f += nb * nfp2;
-    p.prev = f; f += nb * nfp2;
-    p.step = f; f += nb * nfp2;
-    p.T = f; f += (size_t)nb * p.nfp * p.Wp;
-    p.Up = f; f += (size_t)nb * p.nchunk * p.Hp * p.nfp;
-    p.tmax = f; f += (size_t)nb * p.ntile;
-    p.scal = f; f += nb;
-    p.cnt = (int*)f; f += nb;
-    p.act = (int*)f;
-    return WASS_OK;
+    return carve_buf(c, c->dct, [&](Carve& a) { dct_carve(p, nb, a); });
 }
 
 // bases and the padded cell maps; ndata[f] = the number of cells with data of frame f (one synchronisation)
@@ -599,30 +587,19 @@ static int dct_solve(wass_ctx* c, const float* d_zz, int W, int H, const wass_dc
     return WASS_OK;
 }
 
-// host staging of one call: [zz | out | x0 | coeffs | mask]
+// host staging of a call of n frames: zz, out, x0 and coeffs per frame, one mask
 struct DctIo {
     float *zz, *out, *x0, *coeffs;
     uint8_t* mask;
 };
-static int dct_io(wass_ctx* c, int W, int H, int nf, DctIo& io)
+static int dct_io(wass_ctx* c, int n, int W, int H, int nf, DctIo& io)
 {
     const size_t hw = (size_t)W * H, n2 = (size_t)nf * nf;
-    int rc;
-    if ((rc = ensure(c, c->dct_io, (2 * hw + 2 * n2) * 4 + hw + 64))) return rc;
-    io.zz = (float*)c->dct_io.p; io.out = io.zz + hw; io.x0 = io.out + hw; io.coeffs = io.x0 + n2;
-    io.mask = (uint8_t*)(io.coeffs + n2);
-    return WASS_OK;
-}
-
-// host staging of a batch call: [zz | out | x0 | coeffs] per frame, one mask
-static int dct_io_batch(wass_ctx* c, int n, int W, int H, int nf, DctIo& io)
-{
-    const size_t hw = (size_t)W * H, n2 = (size_t)nf * nf;
-    int rc;
-    if ((rc = ensure(c, c->dct_io, (size_t)n * (2 * hw + 2 * n2) * 4 + hw + 64))) return rc;
-    io.zz = (float*)c->dct_io.p; io.out = io.zz + n * hw; io.x0 = io.out + n * hw; io.coeffs = io.x0 + n * n2;
-    io.mask = (uint8_t*)(io.coeffs + n * n2);
-    return WASS_OK;
+    return carve_buf(c, c->dct_io, [&](Carve& a) {
+        io.zz = a.take<float>(n * hw * 4); io.out = a.take<float>(n * hw * 4);
+        io.x0 = a.take<float>(n * n2 * 4); io.coeffs = a.take<float>(n * n2 * 4);
+        io.mask = a.take<uint8_t>(hw);
+    });
 }
 
 }  // namespace wass
@@ -646,7 +623,7 @@ extern "C" int wass_grid_dct_batch(wass_ctx* c, const float* zz, int n_frames, i
     if ((rc = dct_check_args(c, width, height, opts->nfreqs))) return rc;
     WASS_HIP(c, hipSetDevice(c->device));
     DctIo io;
-    if ((rc = dct_io_batch(c, n_frames, width, height, opts->nfreqs, io))) return rc;
+    if ((rc = dct_io(c, n_frames, width, height, opts->nfreqs, io))) return rc;
     hipStream_t s = c->ts();
     const size_t hw = (size_t)width * height, n2 = (size_t)opts->nfreqs * opts->nfreqs;
     WASS_HIP(c, hipMemcpyAsync(io.zz, zz, n_frames * hw * 4, hipMemcpyHostToDevice, s));
@@ -690,7 +667,7 @@ extern "C" int wass_grid_dct(wass_ctx* c, const float* zz, int width, int height
     if ((rc = dct_check_args(c, width, height, opts->nfreqs))) return rc;
     WASS_HIP(c, hipSetDevice(c->device));
     DctIo io;
-    if ((rc = dct_io(c, width, height, opts->nfreqs, io))) return rc;
+    if ((rc = dct_io(c, 1, width, height, opts->nfreqs, io))) return rc;
     hipStream_t s = c->ts();
     const size_t hw = (size_t)width * height, n2 = (size_t)opts->nfreqs * opts->nfreqs;
     WASS_HIP(c, hipMemcpyAsync(io.zz, zz, hw * 4, hipMemcpyHostToDevice, s));
@@ -713,7 +690,7 @@ extern "C" int wass_mesh_grid_dct(wass_ctx* c, const wass_mesh* m, const wass_gr
     if ((rc = dct_check_args(c, gs->width, gs->height, opts->nfreqs))) return rc;
     WASS_HIP(c, hipSetDevice(c->device));
     DctIo io;
-    if ((rc = dct_io(c, gs->width, gs->height, opts->nfreqs, io))) return rc;
+    if ((rc = dct_io(c, 1, gs->width, gs->height, opts->nfreqs, io))) return rc;
     if ((rc = grid_cells_dev(c, m, gs, cell_statistic, io.zz))) return rc;
     hipStream_t s = c->ts();
     const size_t hw = (size_t)gs->width * gs->height, n2 = (size_t)opts->nfreqs * opts->nfreqs;
@@ -737,7 +714,7 @@ extern "C" int wass_grid_dct_eval(wass_ctx* c, const float* zz, int width, int h
     if ((rc = dct_check_args(c, width, height, nfreqs))) return rc;
     WASS_HIP(c, hipSetDevice(c->device));
     DctIo io;
-    if ((rc = dct_io(c, width, height, nfreqs, io))) return rc;
+    if ((rc = dct_io(c, 1, width, height, nfreqs, io))) return rc;
     hipStream_t s = c->ts();
     const size_t hw = (size_t)width * height, n2 = (size_t)nfreqs * nfreqs;
     WASS_HIP(c, hipMemcpyAsync(io.zz, zz, hw * 4, hipMemcpyHostToDevice, s));

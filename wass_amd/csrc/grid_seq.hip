@@ -199,8 +199,7 @@ extern "C" void wass_grid_seq_destroy(wass_grid_seq* q)
     if (!q) return;
     if (q->c) (void)hipSetDevice(q->c->device);
     if (q->acc) (void)hipFree(q->acc);
-    if (q->part.p) (void)hipFree(q->part.p);
-    delete q;
+    delete q;                                                // frees q->part: every call that used it has synchronised before it returned
 }
 
 extern "C" int wass_grid_seq_create(wass_ctx* c, int width, int height, wass_grid_seq** out)

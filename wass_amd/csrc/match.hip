@@ -399,10 +399,20 @@ struct MatchPlan {
     double* d_ax = nullptr;
 };
 
-static size_t match_ctx_bytes(int batch, int nmax)
+// The layout of c->match for a batch whose largest problem has nmax candidates.  Every kernel indexes d_rec and d_ax by
+// (problem * nmax + candidate) with candidate < n[problem] <= nmax: nothing is read or written past a piece, and none has slack.
+static void match_carve(MatchPlan& pl, int batch, int nmax, Carve& a)
 {
-    return 256 + (size_t)batch * 16 + (size_t)batch * sizeof(MatchRes) + (size_t)batch * nmax * (MATCH_REC + 1) * sizeof(double) + 64;
+    const size_t cells = (size_t)batch * nmax;
+    pl.batch = batch; pl.nmax = nmax;
+    pl.d_flag = a.take<int>(256);
+    pl.d_dims = a.take<int>((size_t)batch * 4 * sizeof(int));
+    pl.d_res = a.take<MatchRes>((size_t)batch * sizeof(MatchRes));
+    pl.d_rec = a.take<double>(cells * MATCH_REC * sizeof(double));
+    pl.d_ax = a.take<double>(cells * sizeof(double));
 }
+
+static size_t match_ctx_bytes(int batch, int nmax) { MatchPlan pl; return measure([&](Carve& a) { match_carve(pl, batch, nmax, a); }); }
 
 // checks the sizes of a batch, lays the context's scratch out and uploads the sizes
 static int match_plan(wass_ctx* c, const int* n, const int* na, const int* nb, int batch, MatchPlan* pl, hipStream_t s)
@@ -415,18 +425,8 @@ static int match_plan(wass_ctx* c, const int* n, const int* na, const int* nb, i
         if ((na && na[p] < 1) || (nb && nb[p] < 1)) return set_err(c, WASS_ERR_INVALID_ARG, "problem %d has an empty feature set", p);
         nmax = n[p] > nmax ? n[p] : nmax;
     }
-    int rc = ensure(c, c->match, match_ctx_bytes(batch, nmax));
+    int rc = carve_buf(c, c->match, [&](Carve& a) { match_carve(*pl, batch, nmax, a); });
     if (rc) return rc;
-    char* base = (char*)c->match.p;
-    pl->batch = batch;
-    pl->nmax = nmax;
-    pl->d_flag = (int*)base;
-    pl->d_dims = (int*)(base + 256);
-    pl->d_res = (MatchRes*)(base + 256 + (size_t)batch * 16);
-    size_t off = 256 + (size_t)batch * 16 + (size_t)batch * sizeof(MatchRes);
-    off = (off + 63) & ~(size_t)63;
-    pl->d_rec = (double*)(base + off);
-    pl->d_ax = pl->d_rec + (size_t)batch * nmax * MATCH_REC;
     std::vector<int> dims((size_t)batch * 4, 0);
     for (int p = 0; p < batch; ++p) {
         dims[4 * p] = n[p];
@@ -533,16 +533,18 @@ int wass_match_knn(wass_ctx* c, const float* desc_a, int na, const float* desc_b
     WASS_HIP(c, hipSetDevice(c->device));
     const int kk = k < nb ? k : nb;
     const size_t ba = (size_t)na * d * 4, bb = (size_t)nb * d * 4, bo = (size_t)na * kk * 4;
-    const size_t oa = 0, ob = (ba + 255) & ~(size_t)255, oi = ob + ((bb + 255) & ~(size_t)255), od = oi + ((bo + 255) & ~(size_t)255);
-    if ((rc = ensure(c, c->match_io, od + bo))) return rc;
-    char* base = (char*)c->match_io.p;
-    hipStream_t s = c->ts();
-    WASS_HIP(c, hipMemcpyAsync(base + oa, desc_a, ba, hipMemcpyHostToDevice, s));
-    WASS_HIP(c, hipMemcpyAsync(base + ob, desc_b, bb, hipMemcpyHostToDevice, s));
-    if ((rc = wass_match_knn_dev(c, (const float*)(base + oa), na, (const float*)(base + ob), nb, d, k, (int32_t*)(base + oi), (float*)(base + od))))
+    float *d_a, *d_b, *d_dist;
+    int32_t* d_idx;
+    if ((rc = carve_buf(c, c->match_io, [&](Carve& a) {
+            d_a = a.take<float>(ba); d_b = a.take<float>(bb); d_idx = a.take<int32_t>(bo); d_dist = a.take<float>(bo);
+        })))
         return rc;
-    WASS_HIP(c, hipMemcpyAsync(idx, base + oi, bo, hipMemcpyDeviceToHost, s));
-    WASS_HIP(c, hipMemcpyAsync(dist, base + od, bo, hipMemcpyDeviceToHost, s));
+    hipStream_t s = c->ts();
+    WASS_HIP(c, hipMemcpyAsync(d_a, desc_a, ba, hipMemcpyHostToDevice, s));
+    WASS_HIP(c, hipMemcpyAsync(d_b, desc_b, bb, hipMemcpyHostToDevice, s));
+    if ((rc = wass_match_knn_dev(c, d_a, na, d_b, nb, d, k, d_idx, d_dist))) return rc;
+    WASS_HIP(c, hipMemcpyAsync(idx, d_idx, bo, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemcpyAsync(dist, d_dist, bo, hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipStreamSynchronize(s));
     return WASS_OK;
 }
@@ -571,18 +573,19 @@ int wass_match_payoff(wass_ctx* c, const float* fa, int na, const float* fb, int
     if (na < 1 || nb < 1) return set_err(c, WASS_ERR_INVALID_ARG, "an empty feature set");
     WASS_HIP(c, hipSetDevice(c->device));
     const size_t ba = (size_t)na * 16, bb = (size_t)nb * 16, bc = (size_t)n * 8, bA = (size_t)n * n * 8;
-    const size_t ob = (ba + 255) & ~(size_t)255, oc = ob + ((bb + 255) & ~(size_t)255), oA = oc + ((bc + 255) & ~(size_t)255);
-    int rc = ensure(c, c->match_io, oA + bA);
+    float *d_fa, *d_fb;
+    int32_t* d_cand;
+    double* d_A;
+    int rc = carve_buf(c, c->match_io, [&](Carve& a) {
+        d_fa = a.take<float>(ba); d_fb = a.take<float>(bb); d_cand = a.take<int32_t>(bc); d_A = a.take<double>(bA);
+    });
     if (rc) return rc;
-    char* base = (char*)c->match_io.p;
     hipStream_t s = c->ts();
-    WASS_HIP(c, hipMemcpyAsync(base, fa, ba, hipMemcpyHostToDevice, s));
-    WASS_HIP(c, hipMemcpyAsync(base + ob, fb, bb, hipMemcpyHostToDevice, s));
-    WASS_HIP(c, hipMemcpyAsync(base + oc, cand, bc, hipMemcpyHostToDevice, s));
-    if ((rc = wass_match_payoff_dev(c, (const float*)base, 0, (const float*)(base + ob), 0, (const int32_t*)(base + oc), 0, &n, &na, &nb, 1, lambda,
-                                    (double*)(base + oA), 0)))
-        return rc;
-    WASS_HIP(c, hipMemcpyAsync(A, base + oA, bA, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemcpyAsync(d_fa, fa, ba, hipMemcpyHostToDevice, s));
+    WASS_HIP(c, hipMemcpyAsync(d_fb, fb, bb, hipMemcpyHostToDevice, s));
+    WASS_HIP(c, hipMemcpyAsync(d_cand, cand, bc, hipMemcpyHostToDevice, s));
+    if ((rc = wass_match_payoff_dev(c, d_fa, 0, d_fb, 0, d_cand, 0, &n, &na, &nb, 1, lambda, d_A, 0))) return rc;
+    WASS_HIP(c, hipMemcpyAsync(A, d_A, bA, hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipStreamSynchronize(s));
     return WASS_OK;
 }
@@ -612,18 +615,17 @@ int wass_match_iidyn(wass_ctx* c, const double* A, int n, double* x, int uniform
     if (n < 1 || n > WASS_MATCH_MAX_N) return set_err(c, WASS_ERR_INVALID_ARG, "%d candidates: 1 .. %d", n, WASS_MATCH_MAX_N);
     WASS_HIP(c, hipSetDevice(c->device));
     const size_t bA = (size_t)n * n * 8, bx = (size_t)n * 8;
-    const size_t ox = (bA + 255) & ~(size_t)255, og = ox + ((bx + 255) & ~(size_t)255);
-    int rc = ensure(c, c->match_io, og + (size_t)n);
+    double *d_A, *d_x;
+    uint8_t* d_group;
+    int rc = carve_buf(c, c->match_io, [&](Carve& a) { d_A = a.take<double>(bA); d_x = a.take<double>(bx); d_group = a.take<uint8_t>((size_t)n); });
     if (rc) return rc;
-    char* base = (char*)c->match_io.p;
     hipStream_t s = c->ts();
-    WASS_HIP(c, hipMemcpyAsync(base, A, bA, hipMemcpyHostToDevice, s));
-    if (!uniform_start) WASS_HIP(c, hipMemcpyAsync(base + ox, x, bx, hipMemcpyHostToDevice, s));
-    if ((rc = wass_match_iidyn_dev(c, (const double*)base, 0, (double*)(base + ox), 0, uniform_start, &n, 1, toll, max_iters, pop_threshold, steps, err,
-                                   (uint8_t*)(base + og), 0, group_size)))
+    WASS_HIP(c, hipMemcpyAsync(d_A, A, bA, hipMemcpyHostToDevice, s));
+    if (!uniform_start) WASS_HIP(c, hipMemcpyAsync(d_x, x, bx, hipMemcpyHostToDevice, s));
+    if ((rc = wass_match_iidyn_dev(c, d_A, 0, d_x, 0, uniform_start, &n, 1, toll, max_iters, pop_threshold, steps, err, d_group, 0, group_size)))
         return rc;
-    WASS_HIP(c, hipMemcpyAsync(x, base + ox, bx, hipMemcpyDeviceToHost, s));
-    WASS_HIP(c, hipMemcpyAsync(group, base + og, (size_t)n, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemcpyAsync(x, d_x, bx, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemcpyAsync(group, d_group, (size_t)n, hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipStreamSynchronize(s));
     return WASS_OK;
 }

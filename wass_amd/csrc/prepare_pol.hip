@@ -17,7 +17,7 @@
 //
 // OpenCV is absent here: written from knowledge of OpenCV 4.5.5 (resize.cpp, imgwarp.cpp, undistort.dispatch.cpp), PARITY UNPINNED.
 #include "common.h"
-#include "cube.h"          // align256, order_key, order_unkey, wave_max
+#include "cube.h"          // order_key, order_unkey, wave_max
 #include "undistort_map.h"
 
 #include <cmath>
@@ -280,10 +280,13 @@ static int prep_dev(wass_ctx* c, const uint8_t* d_mosaic, int cols, int rows, si
     const double* dxy = nullptr;
     if ((rc = undistort_tables(c, K, W, H, &dxy))) return rc;
     const dim3 block(PP_BX, PP_BY), grid((W + PP_BX - 1) / PP_BX, (H + PP_BY - 1) / PP_BY);
-    const size_t nblocks = (size_t)grid.x * grid.y, part_bytes = align256(nblocks * PP_NKEY * sizeof(unsigned));
-    if ((rc = ensure(c, c->prep_pol, part_bytes + 256))) return rc;
-    unsigned* part = (unsigned*)c->prep_pol.p;
-    float* d_ranges = (float*)((char*)c->prep_pol.p + part_bytes);
+    const size_t nblocks = (size_t)grid.x * grid.y;
+    unsigned* part;
+    float* d_ranges;
+    if ((rc = carve_buf(c, c->prep_pol, [&](Carve& a) {
+            part = a.take<unsigned>(nblocks * PP_NKEY * sizeof(unsigned)); d_ranges = a.take<float>(PP_NKEY * sizeof(float));
+        })))
+        return rc;
     const int b = prm->outputs;
     PrepOut o;
     o.S = (b & WASS_PREP_STOKES) ? out->S : nullptr;
@@ -333,30 +336,27 @@ extern "C" int wass_prepare_pol(wass_ctx* c, const uint8_t* mosaic, int cols, in
     WASS_HIP(c, hipSetDevice(c->device));
     const int W = cols / 2 * 2, H = rows / 2 * 2, b = params->outputs;
     const size_t HW = (size_t)W * H;
-    // the staged results, in the order of the members; only what was asked for
-    const size_t sz[7] = { (b & WASS_PREP_STOKES) ? align256(HW * 12) : 0, align256(HW), (b & WASS_PREP_DOLP) ? align256(HW) : 0,
-                           (b & WASS_PREP_AOLP) ? align256(HW) : 0, (b & WASS_PREP_CHANNELS) ? align256(HW * 4) : 0,
-                           (b & WASS_PREP_IMAGE_F32) ? align256(HW * 4) : 0, (b & WASS_PREP_AOLP_F32) ? align256(HW * 4) : 0 };
-    size_t off[8] = { 0 };
-    for (int k = 0; k < 7; ++k) off[k + 1] = off[k] + sz[k];
-    if ((rc = ensure(c, c->tmp_in0, HW)) || (rc = ensure(c, c->tmp_out, off[7]))) return rc;
-    char* base = (char*)c->tmp_out.p;
+    // the staged results, in the order of the members; what was not asked for is not taken and stays null
     wass_pol_prep_out d = {};
-    d.S = sz[0] ? (float*)(base + off[0]) : nullptr;
-    d.image = (uint8_t*)(base + off[1]);
-    d.dolp = sz[2] ? (uint8_t*)(base + off[2]) : nullptr;
-    d.aolp = sz[3] ? (uint8_t*)(base + off[3]) : nullptr;
-    d.channels = sz[4] ? (uint8_t*)(base + off[4]) : nullptr;
-    d.image_f32 = sz[5] ? (float*)(base + off[5]) : nullptr;
-    d.aolp_f32 = sz[6] ? (float*)(base + off[6]) : nullptr;
+    if ((rc = ensure(c, c->tmp_in0, HW)) || (rc = carve_buf(c, c->tmp_out, [&](Carve& a) {
+            if (b & WASS_PREP_STOKES) d.S = a.take<float>(HW * 12);
+            d.image = a.take<uint8_t>(HW);
+            if (b & WASS_PREP_DOLP) d.dolp = a.take<uint8_t>(HW);
+            if (b & WASS_PREP_AOLP) d.aolp = a.take<uint8_t>(HW);
+            if (b & WASS_PREP_CHANNELS) d.channels = a.take<uint8_t>(HW * 4);
+            if (b & WASS_PREP_IMAGE_F32) d.image_f32 = a.take<float>(HW * 4);
+            if (b & WASS_PREP_AOLP_F32) d.aolp_f32 = a.take<float>(HW * 4);
+        })))
+        return rc;
     hipStream_t s = c->stream;
     // the odd last row and column are dropped here
     WASS_HIP(c, hipMemcpy2DAsync(c->tmp_in0.p, (size_t)W, mosaic, stride, (size_t)W, (size_t)H, hipMemcpyHostToDevice, s));
     if ((rc = prep_dev(c, (const uint8_t*)c->tmp_in0.p, W, H, (size_t)W, K, dist, n_dist, params, &d))) return rc;
     void* const dst[7] = { out->S, out->image, out->dolp, out->aolp, out->channels, out->image_f32, out->aolp_f32 };
+    const void* const src[7] = { d.S, d.image, d.dolp, d.aolp, d.channels, d.image_f32, d.aolp_f32 };
     const size_t bytes[7] = { HW * 12, HW, HW, HW, HW * 4, HW * 4, HW * 4 };
     for (int k = 0; k < 7; ++k)
-        if (sz[k]) WASS_HIP(c, hipMemcpyAsync(dst[k], base + off[k], bytes[k], hipMemcpyDeviceToHost, s));
+        if (src[k]) WASS_HIP(c, hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipStreamSynchronize(s));
     memcpy(out->ranges, d.ranges, sizeof d.ranges);
     return WASS_OK;
