@@ -33,7 +33,7 @@ def _sum(v, how):
 
 
 def _fold64(w):
-    """the butterfly over a wave: lanes l and l ^ 32, then ^ 16 ... (axis -1 has 64 entries)"""
+    """the butterfly over a wave: lanes l and l ^ 32, then ^ 16 ... (axis -1 has 64 entries); wave_all of wass_amd/csrc/reduce.h"""
     m = 32
     while m >= 1:
         w = w[..., :m] + w[..., m:2 * m]
@@ -43,7 +43,7 @@ def _fold64(w):
 
 def _tree_sum(v):
     """the kernel's tree: 1024 threads, thread t sums elements t, t + 1024, ... in order, a butterfly over each wave of 64, the
-    sixteen waves in order; a problem of at most 64 elements is summed in order, like the reference"""
+    sixteen waves in order; a problem of at most 64 elements is summed in order, like the reference (orders: wass_amd/csrc/reduce.h)"""
     if v.size <= 64:
         return np.cumsum(v)[-1]
     pad = np.zeros(8192)

@@ -59,19 +59,9 @@ static void ac_cam(const double* p, AcCam* c)
         for (int k = 0; k < 3; ++k) c->Rj[3 * r + k] = (Rl[3 * r] * c->R0[k] + Rl[3 * r + 1] * c->R0[3 + k]) + Rl[3 * r + 2] * c->R0[6 + k];
 }
 
-__device__ __forceinline__ double ac_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_down(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double ac_wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-    return v;
-}
+// sum and maximum of a wave in lane 0
+__device__ __forceinline__ double ac_sum(double v) { return wave_fold(v, [](double a, double b) { return a + b; }); }
+__device__ __forceinline__ double ac_max(double v) { return wave_fold(v, [](double a, double b) { return fmax(a, b); }); }
 
 // the projection of one point by one camera: X = Rj M + t, iz = 1 / X2, (px, py) = (X0 iz, X1 iz)
 __device__ __forceinline__ void ac_project(const AcCam& c, double m0, double m1, double m2, double& iz, double& px, double& py)
@@ -193,12 +183,12 @@ __global__ void __launch_bounds__(AC_WG) k_ac_linearize(AcCams cams, const doubl
         for (int a = 0; a < 6; ++a)
 #pragma unroll
             for (int b = 0; b <= a; ++b, ++s) {
-                const double r = ac_wave_sum(in ? ax[a] * ax[b] + ay[a] * ay[b] : 0.0);
+                const double r = ac_sum(in ? ax[a] * ax[b] + ay[a] * ay[b] : 0.0);
                 if (threadIdx.x == 0) out[21 * q + s] = r;
             }
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
-            const double r = ac_wave_sum(in ? ax[a] * ex + ay[a] * ey : 0.0);
+            const double r = ac_sum(in ? ax[a] * ex + ay[a] * ey : 0.0);
             if (threadIdx.x == 0) out[42 + 6 * q + a] = r;
         }
     }
@@ -208,9 +198,9 @@ __global__ void __launch_bounds__(AC_WG) k_ac_linearize(AcCams cams, const doubl
 #pragma unroll
         for (int k = 0; k < 3; ++k) lin[(size_t)(10 + k) * n + i] = eb[k];
     }
-    const double se = ac_wave_sum(in ? err : 0.0);
-    const double mg = ac_wave_max(in ? fmax(fmax(fabs(eb[0]), fabs(eb[1])), fabs(eb[2])) : 0.0);
-    const double md = ac_wave_max(in ? fmax(fmax(V[0], V[3]), V[5]) : 0.0);
+    const double se = ac_sum(in ? err : 0.0);
+    const double mg = ac_max(in ? fmax(fmax(fabs(eb[0]), fabs(eb[1])), fabs(eb[2])) : 0.0);
+    const double md = ac_max(in ? fmax(fmax(V[0], V[3]), V[5]) : 0.0);
     if (threadIdx.x == 0) { out[54] = se; out[55] = mg; out[56] = md; }
 }
 
@@ -257,10 +247,10 @@ __global__ void __launch_bounds__(AC_WG) k_ac_schur(const double* __restrict__ l
         const double y2 = (W[3 * p] * Vi[2] + W[3 * p + 1] * Vi[5]) + W[3 * p + 2] * Vi[8];
 #pragma unroll
         for (int q = 0; q <= p; ++q, ++s) {
-            const double r = ac_wave_sum(in ? (y0 * W[3 * q] + y1 * W[3 * q + 1]) + y2 * W[3 * q + 2] : 0.0);
+            const double r = ac_sum(in ? (y0 * W[3 * q] + y1 * W[3 * q + 1]) + y2 * W[3 * q + 2] : 0.0);
             if (threadIdx.x == 0) out[s] = r;
         }
-        const double r = ac_wave_sum(in ? (y0 * eb0 + y1 * eb1) + y2 * eb2 : 0.0);
+        const double r = ac_sum(in ? (y0 * eb0 + y1 * eb1) + y2 * eb2 : 0.0);
         if (threadIdx.x == 0) out[78 + p] = r;
     }
 }
@@ -303,10 +293,10 @@ __global__ void __launch_bounds__(AC_WG) k_ac_backsub(AcCams cnew, AcStep st, co
     const double ex0 = obs[4 * j] - px, ey0 = obs[4 * j + 1] - py;
     ac_project(cnew.c[1], n0, n1, n2, iz, px, py);
     const double ex1 = obs[4 * j + 2] - px, ey1 = obs[4 * j + 3] - py;
-    const double s0 = ac_wave_sum(in ? (ex0 * ex0 + ey0 * ey0) + (ex1 * ex1 + ey1 * ey1) : 0.0);
-    const double s1 = ac_wave_sum(in ? (d0 * d0 + d1 * d1) + d2 * d2 : 0.0);
-    const double s2 = ac_wave_sum(in ? (m0 * m0 + m1 * m1) + m2 * m2 : 0.0);
-    const double s3 = ac_wave_sum(in ? (d0 * (st.mu * d0 + eb[0]) + d1 * (st.mu * d1 + eb[1])) + d2 * (st.mu * d2 + eb[2]) : 0.0);
+    const double s0 = ac_sum(in ? (ex0 * ex0 + ey0 * ey0) + (ex1 * ex1 + ey1 * ey1) : 0.0);
+    const double s1 = ac_sum(in ? (d0 * d0 + d1 * d1) + d2 * d2 : 0.0);
+    const double s2 = ac_sum(in ? (m0 * m0 + m1 * m1) + m2 * m2 : 0.0);
+    const double s3 = ac_sum(in ? (d0 * (st.mu * d0 + eb[0]) + d1 * (st.mu * d1 + eb[1])) + d2 * (st.mu * d2 + eb[2]) : 0.0);
     if (threadIdx.x == 0) { out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3; }
 }
 
@@ -324,7 +314,7 @@ __global__ void __launch_bounds__(AC_WG) k_ac_error(AcCams cams, const double* _
     ac_project(cams.c[1], m0, m1, m2, iz, px, py);
     const double ex1 = obs[4 * j + 2] - px, ey1 = obs[4 * j + 3] - py;
     if (in && res) { res[i] = ex0; res[(size_t)n + i] = ey0; res[(size_t)2 * n + i] = ex1; res[(size_t)3 * n + i] = ey1; }
-    const double s0 = ac_wave_sum(in ? (ex0 * ex0 + ey0 * ey0) + (ex1 * ex1 + ey1 * ey1) : 0.0);
+    const double s0 = ac_sum(in ? (ex0 * ex0 + ey0 * ey0) + (ex1 * ex1 + ey1 * ey1) : 0.0);
     if (threadIdx.x == 0) part[(size_t)blockIdx.x * AC_PART] = s0;
 }
 

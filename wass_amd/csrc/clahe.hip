@@ -35,13 +35,7 @@ __global__ void __launch_bounds__(256) k_clahe_lut(const uint8_t* __restrict__ s
         }
         __syncthreads();
     }
-    // inclusive prefix sum over the 256 bins (Hillis-Steele in LDS)
-    for (int o = 1; o < 256; o <<= 1) {
-        const int v = t >= o ? hist[t - o] : 0;
-        __syncthreads();
-        hist[t] += v;
-        __syncthreads();
-    }
+    lds_scan<256>(hist);                                      // inclusive prefix sum over the 256 bins
     const int r = __float2int_rn((float)hist[t] * lut_scale);
     lut[(size_t)blockIdx.x * 256 + t] = (uint8_t)min(max(r, 0), 255);
 }

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/wass_gpu.h"
+#include "reduce.h"
 #include "scratch.h"
 
 namespace wass {

@@ -1,6 +1,6 @@
 // cube.h -- what the one-shot operators of the count x H x W cube share (filter, radiance, polarimetric, pyramid, visibility,
-// wavestats; prepare_pol takes the keys): the host scaffolding of a call that allocates its scratch, runs and frees it, and the
-// ordered-key maxima of their kernels.  Plain functions and one RAII struct; every operator keeps its own plan and byte formula.
+// wavestats): the host scaffolding of a call that allocates its scratch, runs and frees it.  Plain functions and one RAII struct;
+// every operator keeps its own plan and byte formula.  (The ordered-key maxima of their kernels are reduce.h's.)
 // A call makes ONE hipMalloc and one hipFree by design: the scratch of a cube is gigabytes and is not kept in the context.
 // The handles of spectrum.hip (wass_spec3d, wass_spatial_filter) hold an Arena for their lifetime and stage through the same
 // functions.  The piece-by-piece hand-out itself (Carve, align256) is scratch.h's, which the context's pool shares.
@@ -10,7 +10,6 @@
 
 namespace wass {
 
-// ---------------------------------------------------------------- host side
 // A Carve over ONE hipMalloc of `total` bytes, freed when the struct goes out of scope.  A total of 0 makes no call at all, and
 // every piece of it is a pointer nobody may follow.  An Arena that has reserved nothing measures, as every Carve without memory.
 struct Arena : Carve {
@@ -86,66 +85,6 @@ inline hipError_t download_rows(void* host, const void* dev, size_t elem, int co
         e = hipMemcpy2DAsync((char*)host + ((size_t)t * st + (size_t)r0 * sy) * elem, sy * elem, (const char*)dev + (size_t)t * plane, rowb, rowb, rows,
                              kind, s);
     return e;
-}
-
-// ---------------------------------------------------------------- device side
-// An unsigned key that orders like the number it was made from.  No number has key 0 or ~0: the callers keep 0 for "nothing seen".
-__device__ __forceinline__ unsigned order_key(float v)
-{
-    const unsigned b = __float_as_uint(v);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ unsigned long long order_key(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__host__ __device__ __forceinline__ float order_unkey(unsigned k)
-{
-    return __builtin_bit_cast(float, (k >> 31) ? (k & 0x7fffffffu) : ~k);
-}
-
-__host__ __device__ __forceinline__ double order_unkey(unsigned long long k)
-{
-    return __builtin_bit_cast(double, (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
-
-__device__ __forceinline__ unsigned wave_max(unsigned k)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned other = (unsigned)__shfl_xor((int)k, o, 64);
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long k)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(k, o, 64);
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
-// The largest key of a block of 64 x BY threads into *dst (0 = nothing seen, and nothing is written); every thread of the block
-// calls it, and a kernel may call it more than once.
-template <int BY, class K> __device__ __forceinline__ void block_max(K k, K* dst)
-{
-    __shared__ K part[BY];
-    k = wave_max(k);
-    __syncthreads();                                    // `part` may still be read by an earlier call
-    if (threadIdx.x == 0) part[threadIdx.y] = k;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-#pragma unroll
-        for (int w = 1; w < BY; ++w) k = part[w] > k ? part[w] : k;
-        if (k) atomicMax(dst, k);
-    }
 }
 
 }  // namespace wass

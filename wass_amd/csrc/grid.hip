@@ -80,12 +80,7 @@ __global__ void __launch_bounds__(1024) k_grid_scan(const unsigned int* __restri
     for (size_t i = a; i < b; ++i) s += cnt[i];
     part[threadIdx.x] = s;
     __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const unsigned int v = threadIdx.x >= (unsigned)o ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
+    lds_scan<1024>(part);
     unsigned int run = part[threadIdx.x] - s;                // exclusive prefix of this thread's chunk
     for (size_t i = a; i < b; ++i) { off[i] = run; run += cnt[i]; }
 }

@@ -84,10 +84,7 @@ __global__ void __launch_bounds__(1024) k_dct_load(const float* __restrict__ zz,
     }
     part[threadIdx.x] = n;
     __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree<1024>([&](int t, int u) { part[t] += part[u]; });
     if (threadIdx.x == 0) { cnt[blockIdx.x] = part[0]; act[blockIdx.x] = part[0] != 0; }
 }
 
@@ -245,10 +242,7 @@ __global__ void __launch_bounds__(64 * STEP_WAVES) k_dct_step(const float* __res
     }
     __syncthreads();
     if (RPROP) {
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) mx[threadIdx.x] = fmaxf(mx[threadIdx.x], mx[threadIdx.x + o]);
-            __syncthreads();
-        }
+        block_tree<256>([&](int t, int u) { mx[t] = fmaxf(mx[t], mx[u]); });
         if (threadIdx.x == 0) tmax[blockIdx.y * gridDim.x + blockIdx.x] = mx[0];
     }
 }
@@ -265,10 +259,7 @@ __global__ void __launch_bounds__(256) k_dct_maxred(const float* __restrict__ tm
     for (int i = threadIdx.x; i < n; i += 256) v = fmaxf(v, tmax[i]);
     m[threadIdx.x] = v;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) m[threadIdx.x] = fmaxf(m[threadIdx.x], m[threadIdx.x + o]);
-        __syncthreads();
-    }
+    block_tree<256>([&](int t, int u) { m[t] = fmaxf(m[t], m[u]); });
     if (threadIdx.x == 0) {
         out[blockIdx.x] = m[0];
         if ((double)m[0] < tol) act[blockIdx.x] = 0;
@@ -301,7 +292,7 @@ __global__ void __launch_bounds__(256) k_dct_recon(const float* __restrict__ T, 
         }
     }
     // wave sum in a fixed order (lane order), then the four waves in order
-    for (int o = 32; o > 0; o >>= 1) se += __shfl_down(se, o);
+    se = wave_fold(se, [](double a, double b) { return a + b; });
     if (l == 0) part[w] = se;
     __syncthreads();
     if (threadIdx.x == 0) lossp[blockIdx.y * gridDim.x + blockIdx.x] = part[0] + part[1] + part[2] + part[3];
@@ -326,10 +317,7 @@ __global__ void __launch_bounds__(256) k_dct_final(const double* __restrict__ lo
     for (int i = threadIdx.x; i < nf * nf; i += 256) t += fabs((double)x[(size_t)(i / nf) * nfp + i % nf]);
     a[threadIdx.x] = s; b[threadIdx.x] = t;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { a[threadIdx.x] += a[threadIdx.x + o]; b[threadIdx.x] += b[threadIdx.x + o]; }
-        __syncthreads();
-    }
+    block_tree<256>([&](int t, int u) { a[t] += a[u]; b[t] += b[u]; });
     if (threadIdx.x == 0) { res[0] = cnt[0] ? a[0] / cnt[0] : 0.0; res[1] = b[0]; res[2] = (double)cnt[0]; }
 }
 

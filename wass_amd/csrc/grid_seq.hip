@@ -117,10 +117,7 @@ __global__ void __launch_bounds__(256) k_seq_stats(const float* __restrict__ zi,
     }
     sh[threadIdx.x] = p;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) seq_merge(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
+    block_tree<256>([&](int t, int u) { seq_merge(sh[t], sh[u]); });
     if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
 }
 
@@ -133,10 +130,7 @@ __global__ void __launch_bounds__(256) k_seq_stats_final(const SeqPart* __restri
     if ((int)threadIdx.x < nblk) p = part[threadIdx.x];      // nblk <= 256
     sh[threadIdx.x] = p;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) seq_merge(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
+    block_tree<256>([&](int t, int u) { seq_merge(sh[t], sh[u]); });
     if (threadIdx.x == 0) {
         res[3 * blockIdx.x] = sh[0].cnt ? sh[0].sum / (double)sh[0].cnt : (double)__builtin_nanf("");
         res[3 * blockIdx.x + 1] = (double)sh[0].mn;

@@ -24,7 +24,7 @@ namespace wass {
 constexpr int QS_BITS = 11, QS_BINS = 1 << QS_BITS, QS_PASSES = 6, QS_COPIES = 4, QS_MAXQ = 8;
 // one workgroup takes QS_TILE elements per sweep (QS_ITEMS independent loads per lane), one launch QS_MAX_BLOCKS tiles per sweep
 constexpr int QS_THREADS = 256, QS_ITEMS = 8, QS_TILE = QS_THREADS * QS_ITEMS, QS_MAX_BLOCKS = 1024;
-constexpr unsigned long long QS_SIGN = 0x8000000000000000ull, QS_NONE = ~0ull;
+constexpr unsigned long long QS_NONE = ~0ull;
 
 struct QsQuery {
     double q;
@@ -43,20 +43,7 @@ constexpr size_t QS_HIST_OFF = (sizeof(QsState) + 255) & ~(size_t)255;
 // one set of histogram copies per query, and one more (index QS_MAXQ) for pass 0: its digit counts are the same for every query
 constexpr size_t QS_BYTES = QS_HIST_OFF + (size_t)(QS_MAXQ + 1) * QS_COPIES * QS_BINS * 4;
 
-// monotone map double -> u64 (negative: all bits flipped, else the sign bit set); -0.0 < +0.0, NaN is kept out by the callers
-__host__ __device__ inline unsigned long long qs_key(double v)
-{
-    unsigned long long u;
-    memcpy(&u, &v, 8);
-    return (u & QS_SIGN) ? ~u : (u | QS_SIGN);
-}
-__host__ __device__ inline double qs_value(unsigned long long key)
-{
-    const unsigned long long u = (key & QS_SIGN) ? (key ^ QS_SIGN) : ~key;
-    double v;
-    memcpy(&v, &u, 8);
-    return v;
-}
+// the keys are reduce.h's order_key / order_unkey: -0.0 < +0.0, NaN is kept out by the callers, so QS_NONE is no value's key
 
 // numpy's "linear" method for n >= 1 values: virtual index (n - 1) * q, _get_indexes (previous = floor, next = previous + 1, both
 // -1 = the last element at or above n - 1, both 0 below 0) and _get_gamma (virtual - previous, with previous as numpy's index: -1
@@ -124,7 +111,7 @@ __global__ void __launch_bounds__(QS_THREADS) k_qs_hist(const double* __restrict
             for (int k = 0; k < QS_ITEMS; ++k) {
                 if (!ok[k]) continue;
                 if (v[k] != v[k]) { if (pass == 0) atomicAdd(&lnan, 1u); continue; }
-                const unsigned long long key = qs_key(v[k]);
+                const unsigned long long key = order_key(v[k]);
                 if (pass > 0 && (key >> hi_shift) != prefix) continue;
                 atomicAdd(&lh[(unsigned int)(key >> shift) & mask], 1u);
             }
@@ -222,16 +209,13 @@ __global__ void __launch_bounds__(QS_THREADS) k_qs_next(const double* __restrict
 #pragma unroll
         for (int k = 0; k < QS_ITEMS; ++k) {
             if (!ok[k] || v[k] != v[k]) continue;
-            const unsigned long long key = qs_key(v[k]);
+            const unsigned long long key = order_key(v[k]);
             if (key > lo && key < m) m = key;
         }
     }
     red[threadIdx.x] = m;
     __syncthreads();
-    for (int o = QS_THREADS / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o && red[threadIdx.x + o] < red[threadIdx.x]) red[threadIdx.x] = red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree<QS_THREADS>([&](int t, int u) { if (red[u] < red[t]) red[t] = red[u]; });
     if (threadIdx.x == 0 && red[0] != QS_NONE) atomicMin(&st->qy[j].hi_key, red[0]);
 }
 
@@ -274,7 +258,7 @@ static int quantiles_run(wass_ctx* c, const double* d_vals, const uint8_t* d_val
         unsigned long long lo, hi;
         double gamma;
         qs_indexes(h.total, q[i], &lo, &hi, &gamma);
-        out[i] = qs_lerp(qs_value(Q.lo_key), qs_value(Q.hi_key), gamma);
+        out[i] = qs_lerp(order_unkey(Q.lo_key), order_unkey(Q.hi_key), gamma);
     }
     return WASS_OK;
 }

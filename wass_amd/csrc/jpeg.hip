@@ -203,9 +203,7 @@ __global__ void __launch_bounds__(64) k_jpeg_dct(Src src, int w, int h, int C, i
 __device__ __forceinline__ int block_excl_scan(int v, int* total, int* lds)         // 256 threads; returns the exclusive prefix, *total = the sum
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    const int incl = wave_scan(v, [](int a, int b) { return a + b; });
     if (lane == 63) lds[wv] = incl;
     __syncthreads();
     int base = 0, tot = 0;
@@ -351,10 +349,7 @@ __global__ void __launch_bounds__(256) k_minmax_part(V v, size_t n, float init_m
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const float x = v.value(i); mn = fminf(x, mn); mx = fmaxf(x, mx); }
     smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { smn[threadIdx.x] = fminf(smn[threadIdx.x], smn[threadIdx.x + s]); smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + s]); }
-        __syncthreads();
-    }
+    block_tree<256>([&](int t, int u) { smn[t] = fminf(smn[t], smn[u]); smx[t] = fmaxf(smx[t], smx[u]); });
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = smn[0]; part[2 * blockIdx.x + 1] = smx[0]; }
 }
 __global__ void k_minmax_final(const float* __restrict__ part, int nb, float* __restrict__ out)

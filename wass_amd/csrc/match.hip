@@ -171,9 +171,7 @@ __device__ __forceinline__ double wave_sum_f64(double v, bool seq)
         for (int l = 1; l < 64; ++l) s += __shfl(v, l);
         return s;
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
+    return wave_all(v, [](double a, double b) { return a + b; });
 }
 
 // the sum over the workgroup: a thread's own terms in index order, the wave's sum, the sixteen waves in order
@@ -366,8 +364,7 @@ __global__ void __launch_bounds__(IID_THREADS) k_match_iidyn(const double* __res
             if (x[e] > m) m = x[e];
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { const double o = __shfl_xor(m, s); if (o > m) m = o; }
+    m = wave_all(m, [](double a, double o) { return o > a ? o : a; });
     if (lane == 0) r_fin[wave] = m;
     __syncthreads();
     m = r_fin[0];

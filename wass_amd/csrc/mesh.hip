@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, WAS
     codes[idx] = (uint8_t)(c0 | (c1 << 4));
     found += ok ? 1u : 0u;
     }
-    for (int o = 32; o > 0; o >>= 1) found += __shfl_down(found, o);
+    found = wave_fold(found, [](unsigned int a, unsigned int b) { return a + b; });
     if ((threadIdx.x & 63) == 0 && found) atomicAdd(count + slot_of_block(), (unsigned long long)found);
 }
 
@@ -239,11 +239,7 @@ __global__ void __launch_bounds__(256) k_ccl_init(const uint8_t* __restrict__ va
     const bool v = i < n && valid[i];
     // start of my horizontal run inside this block = last "break" at or before me
     int s = (threadIdx.x == 0 || !v || !hlink(valid, Z, w, i, zgap)) ? i : -1;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(s, o); if (lane >= o) s = max(s, t); }
-    if (lane == 63) wmax[wv] = s;
-    __syncthreads();
-    for (int k = 0; k < wv; ++k) s = max(s, wmax[k]);
+    s = block_scan(s, wmax, [](int a, int b) { return max(a, b); });
     if (i < n) { parent[i] = v ? s : -1; size[i] = 0; mincm[i] = 0xFFFFFFFFu; }
 }
 __global__ void __launch_bounds__(256) k_ccl_merge(const uint8_t* __restrict__ valid, const double* __restrict__ Z, int w, int n,
@@ -313,10 +309,7 @@ __global__ void __launch_bounds__(256) k_ccl_best(int n, const int* __restrict__
     const int i = blockIdx.x * 256 + threadIdx.x;
     unsigned long long key = 0;
     if (i < n && parent[i] == i) key = ((unsigned long long)size[i] << 32) | (unsigned long long)(0xFFFFFFFFu - mincm[i]);
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_down(key, o);
-        key = other > key ? other : key;
-    }
+    key = wave_fold(key, [](unsigned long long a, unsigned long long b) { return b > a ? b : a; });
     if ((threadIdx.x & 63) == 0 && key) atomicMax(best, key);
 }
 // keep the component whose (size, mincm) equals the winner
@@ -653,7 +646,7 @@ __global__ void __launch_bounds__(256) k_crop_plane_dev(uint8_t* __restrict__ va
             if (fabs((a * X[i] + b * Y[i] + c * Z[i]) + d) < thr) ++cnt; else valid[i] = 0;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    cnt = wave_fold(cnt, [](unsigned int a, unsigned int b) { return a + b; });
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept + slot_of_block(), (unsigned long long)cnt);
 }
 
@@ -720,7 +713,7 @@ __global__ void __launch_bounds__(256) k_crop_moments_dev(uint8_t* __restrict__ 
         const double wt = rp.weighted ? dist : 1.0;
         acc[0] += 1.0; acc[1] += wt; acc[2] += px * wt; acc[3] += py * wt; acc[4] += pz * wt;
     }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    cnt = wave_fold(cnt, [](unsigned int a, unsigned int b) { return a + b; });
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept + slot_of_block(), (unsigned long long)cnt);
     block_sum_store<5>(acc, partial);
 }
@@ -940,18 +933,6 @@ __global__ void k_refine_finish(const double* __restrict__ partial, int nb, DevS
 // ------------------------------------------------------------------ xyzC (PovMesh.cpp:377-460)
 struct RTDev { double R[9], T[3]; };
 
-__device__ __forceinline__ unsigned long long dkey(double v)     // order-preserving map double -> u64
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-__host__ __device__ __forceinline__ double dunkey(unsigned long long k)
-{
-    const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-    double d;
-    memcpy(&d, &b, 8);
-    return d;
-}
 // min/max of R*p+T per axis (exact, order independent) + number of valid points per block
 __global__ void __launch_bounds__(256) k_block_counts(const uint8_t* __restrict__ valid, size_t n,
                                                       unsigned int* __restrict__ blockcnt)
@@ -972,7 +953,7 @@ __device__ __forceinline__ void xyzc_limits_body(const uint8_t* __restrict__ val
         mulv(rt.R, p, t);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const unsigned long long key = dkey(t[k] + rt.T[k]);
+            const unsigned long long key = order_key(t[k] + rt.T[k]);
             mn[k] = key < mn[k] ? key : mn[k];
             mx[k] = key > mx[k] ? key : mx[k];
         }
@@ -1373,7 +1354,7 @@ __global__ void __launch_bounds__(256) k_crop_limits_counts_dev(uint8_t* __restr
                 mulv(R, p, t);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const unsigned long long key = dkey(t[k] + T[k]);
+                    const unsigned long long key = order_key(t[k] + T[k]);
                     mn[k] = key < mn[k] ? key : mn[k];
                     mx[k] = key > mx[k] ? key : mx[k];
                 }
@@ -1383,7 +1364,7 @@ __global__ void __launch_bounds__(256) k_crop_limits_counts_dev(uint8_t* __restr
         const int cnt = __syncthreads_count(v);
         if (threadIdx.x == 0) blockcnt[chunk] = (unsigned)cnt;
     }
-    for (int o = 32; o > 0; o >>= 1) nkept += __shfl_down(nkept, o);
+    nkept = wave_fold(nkept, [](unsigned int a, unsigned int b) { return a + b; });
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         for (int o = 32; o > 0; o >>= 1) {
@@ -1432,8 +1413,8 @@ __global__ void k_frame_header(DevState* __restrict__ ds, const unsigned long lo
     const unsigned int npts = *total;
     double mx[3];
     for (int k = 0; k < 3; ++k) {
-        ds->mn[k] = npts ? dunkey(hl[k]) : 1.7976931348623157e308;
-        mx[k] = npts ? dunkey(hl[3 + k]) : -1.7976931348623157e308;
+        ds->mn[k] = npts ? order_unkey(hl[k]) : 1.7976931348623157e308;
+        mx[k] = npts ? order_unkey(hl[3 + k]) : -1.7976931348623157e308;
         ds->sc[k] = 65535.0 / (mx[k] - ds->mn[k]);
     }
     ds->npts = npts;
@@ -2207,8 +2188,8 @@ static int encode_xyzc_impl(wass_ctx* c, wass_mesh* m, const double plane[4], vo
     double mn[3], mx[3], sc[3];
     for (int k = 0; k < 3; ++k) {
         // no valid point: the reference writes +-DBL_MAX limits; keep that
-        mn[k] = npts ? dunkey(hl[k]) : 1.7976931348623157e308;
-        mx[k] = npts ? dunkey(hl[3 + k]) : -1.7976931348623157e308;
+        mn[k] = npts ? order_unkey(hl[k]) : 1.7976931348623157e308;
+        mx[k] = npts ? order_unkey(hl[3 + k]) : -1.7976931348623157e308;
         sc[k] = 65535.0 / (mx[k] - mn[k]);
     }
     const size_t total_bytes = 148 + (size_t)npts * 6;

@@ -13,11 +13,10 @@
 //                   Every float32 product and sum is rounded on its own (the library is built with -ffp-contract=off); quotients and
 //                   roots are formed in fp64 and rounded again, which is the correctly rounded float32 result; exp and atan2 are fp64.
 //   k_prepare_pol_ranges   the ranges of S0, S1, S2 and DOLP (NaN skipped): k_prepare_pol leaves one record of ordered integer keys per
-//                   block (cube.h's order_key), this kernel takes their maxima.  No float atomics, no dependence on the order of execution.
+//                   block (reduce.h's order_key), this kernel takes their maxima.  No float atomics, no dependence on the order of execution.
 //
 // OpenCV is absent here: written from knowledge of OpenCV 4.5.5 (resize.cpp, imgwarp.cpp, undistort.dispatch.cpp), PARITY UNPINNED.
 #include "common.h"
-#include "cube.h"          // order_key, order_unkey, wave_max
 #include "undistort_map.h"
 
 #include <cmath>

@@ -18,7 +18,7 @@
 //                     the chain.  Rows go in slabs under the scratch cap; a series never crosses a slab.  No atomics.
 //   k_thr_*           Isub = I - (Ibg - min(Ibg)) in float32; per frame the minimum of Ibg, the range of Isub, the 30-bin histogram
 //                     of Isub against 31 given float32 edges (numpy's rule: left edge inclusive, last bin closed) and the mask
-//                     Isub > thr.  Integer atomics only (cube.h's ordered keys and block maximum): the same input gives the same bits.
+//                     Isub > thr.  Integer atomics only (reduce.h's ordered keys and block maximum): the same input gives the same bits.
 // Host side: every *_plan keeps its byte formula; the batch and slab rules, the scratch, the staging of a host batch or slab
 // (pictures too: they are cubes of bytes) and the end of a call are cube.h's.
 #include "common.h"

@@ -1216,7 +1216,7 @@ __global__ void __launch_bounds__(256) k_count_diff(const uint32_t* __restrict__
         if (2 * dw < D && (a & 0xFFFFu) != (b & 0xFFFFu)) ++bad;
         if (2 * dw + 1 < D && (a >> 16) != (b >> 16)) ++bad;
     }
-    for (int o = 32; o > 0; o >>= 1) bad += __shfl_down(bad, o);
+    bad = wave_fold(bad, [](unsigned int a, unsigned int b) { return a + b; });
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, (unsigned long long)bad);
 }
 

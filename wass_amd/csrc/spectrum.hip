@@ -162,14 +162,12 @@ __global__ void __launch_bounds__(256) k_dft_stage(const DftArgs a)
             }
 }
 
-static __device__ __forceinline__ double block_sum_256(double v, double* sh)
+// the sum of a block of 256 in every thread: reduce.h's tree, and a barrier after the read so that sh can be filled again at once
+static __device__ __forceinline__ double block_sum(double v, double* sh)
 {
     sh[threadIdx.x] = v;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree<256>([&](int t, int u) { sh[t] += sh[u]; });
     const double r = sh[0];
     __syncthreads();
     return r;
@@ -198,7 +196,7 @@ __global__ void __launch_bounds__(256) k_seg_cell(const float* __restrict__ src,
         if (!cnt) *flag = 1;
         else tot = sd + (double)(nt - cnt) * (double)m;
     }
-    tot = block_sum_256(tot, sh);
+    tot = block_sum(tot, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -208,7 +206,7 @@ __global__ void __launch_bounds__(256) k_seg_mean(const double* __restrict__ par
     __shared__ double sh[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < npart; i += 256) s += part[i];
-    s = block_sum_256(s, sh);
+    s = block_sum(s, sh);
     if (threadIdx.x == 0) mean[0] = s / count;
 }
 
@@ -262,7 +260,7 @@ __global__ void __launch_bounds__(256) k_w1_mean(const float* __restrict__ x, in
     x += (size_t)blockIdx.x * T;
     double s = 0.0;
     for (int i = threadIdx.x; i < T; i += 256) s += (double)(x[i] * scale);
-    s = block_sum_256(s, sh);
+    s = block_sum(s, sh);
     if (threadIdx.x == 0) smean[blockIdx.x] = s / (double)T;
 }
 
@@ -278,7 +276,7 @@ __global__ void __launch_bounds__(256) k_w1_prep(const float* __restrict__ x, in
     const double m = smean[ser];
     double s = 0.0;
     for (int i = threadIdx.x; i < nps; i += 256) s += (double)(p[i] * scale) - m;
-    const double sm = block_sum_256(s, sh) / (double)nps;
+    const double sm = block_sum(s, sh) / (double)nps;
     for (int i = threadIdx.x; i < nps; i += 256) B[(size_t)i * ncol + col] = (float)((((double)(p[i] * scale) - m) - sm) * win[i]);
 }
 
@@ -293,7 +291,7 @@ __global__ void __launch_bounds__(256) k_w1_power(const float* __restrict__ Xre,
         const double re = (double)Xre[(size_t)m * ncol + i], im = (double)Xim[(size_t)m * ncol + i];
         s += re * re + im * im;
     }
-    s = block_sum_256(s, sh);
+    s = block_sum(s, sh);
     // one-sided: every bin but DC and (even nps) Nyquist stands for two
     const bool twice = m != 0 && !(nps % 2 == 0 && m == nps / 2);
     if (threadIdx.x == 0) out[m] = s * dens * (twice ? 2.0 : 1.0);

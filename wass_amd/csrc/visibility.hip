@@ -16,7 +16,7 @@
 // addresses do not depend on the heights, only the end of the ray does.  A ray is dropped, not occluded, when it leaves the
 // grid or rises above the frame's maximum (p2 only grows); NaN fails every comparison, so a NaN cell never occludes and its
 // own ray is dropped at once.  The loop is bounded by max(H, W) steps whatever the input.
-// The only atomics are integer ones (a maximum of order-preserving keys, cube.h's, and counts): the same input gives the same bits.
+// The only atomics are integer ones (a maximum of order-preserving keys, reduce.h's, and counts): the same input gives the same bits.
 // Host side: vis_plan keeps the byte formula; the batch rule, the scratch, the staging of a host batch and the end of a call are
 // cube.h's.
 #include "common.h"
@@ -31,7 +31,7 @@ constexpr int VIS_DEFAULT_BATCH = 8;
 constexpr int VIS_U = 4;                                // steps whose heights are loaded ahead of the comparisons
 constexpr int VIS_BX = 64, VIS_BY = 4;                  // a block: 4 waves, each 64 cells of one row
 
-// the frame's largest height from its key (cube.h's order_key); key 0, nothing seen, stands for minus infinity
+// the frame's largest height from its key (reduce.h's order_key); key 0, nothing seen, stands for minus infinity
 __device__ __forceinline__ double vis_top(unsigned long long k) { return k ? order_unkey(k) : -INFINITY; }
 
 // d = -(r / |r|), r = cell - camera: the unit direction from the cell to the camera, numpy's operations in numpy's order

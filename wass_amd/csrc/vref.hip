@@ -222,13 +222,7 @@ __global__ void __launch_bounds__(VR_THREADS) k_vref_forward(VrefFwd a, VrefAxis
         red[0][threadIdx.x] = sd;
         red[1][threadIdx.x] = ss;
         __syncthreads();
-        for (int o = VR_THREADS / 2; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) {
-                red[0][threadIdx.x] += red[0][threadIdx.x + o];
-                red[1][threadIdx.x] += red[1][threadIdx.x + o];
-            }
-            __syncthreads();
-        }
+        block_tree<VR_THREADS>([&](int t, int u) { red[0][t] += red[0][u]; red[1][t] += red[1][u]; });
         if (threadIdx.x == 0) {
             const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
             a.partial[2 * b] = red[0][0];
@@ -249,13 +243,7 @@ __global__ void __launch_bounds__(VR_THREADS) k_vref_loss(const double* __restri
     red[0][threadIdx.x] = sd;
     red[1][threadIdx.x] = ss;
     __syncthreads();
-    for (int o = VR_THREADS / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + o];
-            red[1][threadIdx.x] += red[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    block_tree<VR_THREADS>([&](int t, int u) { red[0][t] += red[0][u]; red[1][t] += red[1][u]; });
     if (threadIdx.x == 0) {
         const double data = red[0][0] / n_nodes, smooth = red[1][0] / n_nodes;
         row[0] = steps; row[1] = data; row[2] = smooth; row[3] = data + alpha * smooth;
