@@ -650,6 +650,8 @@ int wass_spec3d_create(wass_ctx* ctx, int nt, int ny, int nx, const double* win_
 int wass_spec3d_push(wass_spec3d* h, const float* seg, size_t stride_t, size_t stride_y, double datascale);
 int wass_spec3d_push_dev(wass_spec3d* h, const float* d_seg, size_t stride_t, size_t stride_y, double datascale);
 int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* n_segments, int* had_all_nan_cell);
+/* wass_spec3d_finish with S written to device memory (nt x ny x nx fp64, dense): the same bits, no download */
+int wass_spec3d_finish_dev(wass_spec3d* h, double scale, double* d_S, int* n_segments, int* had_all_nan_cell);
 void wass_spec3d_destroy(wass_spec3d* h);
 /* compute_spectrum (:9-49): S[nperseg / 2 + 1] (host) = the sum over n_series series (host, n_series x n_samples float32) of
  * scipy.signal.csd(x, x, fs, nperseg=nperseg) with x = (float32)(series * scale) minus its mean: segments of nperseg with
@@ -949,6 +951,56 @@ int wass_wavestats(wass_ctx* ctx, const float* in, size_t stride_t, size_t strid
 int wass_wavestats_dev(wass_ctx* ctx, const float* d_in, size_t stride_t, size_t stride_y, int count, int H, int W, double dt,
                        double datascale, int crossing, int demean, int hist_bins, double hist_width, int slab_rows, double* d_fields,
                        int32_t* d_n_cross, uint64_t* d_hist);
+
+/* ---- Spectral products of the 3-D spectrum (beyond the reference: DESIGN.md "Spectral products" is the specification).
+ * S is an nt x ny x nx fp64 cube, dense, as wass_spec3d_finish[_dev] leaves it (fftshifted); p0 is its first frequency above
+ * zero, and frequencies p0 .. nt - 1 are the positive half.  v = S * scale (scale > 0) is one rounding; every sum below is fp64,
+ * every product and sum rounded on its own, in ONE order that depends on nt, ny, nx, p0 and the labels alone.  A label map is
+ * ny x nx int32 in host memory, -1 = unused, else 0 .. n - 1; the host computes it (no atan2, sqrt or tanh runs on the device).
+ * block_sum(x[0 .. 255]) below is the tree for o = 128, 64, .. 1: x[t] += x[t + o] for t < o.
+ *   T[p - p0][b] = block_sum over t of (the cells c_t, c_(t + 256), .. of label b's cells c_0 < c_1 < .. in raster order, added in
+ *                  that order from 0.0): T_dir with lab_dir (nf x n_dir, nf = nt - p0), T_k with lab_k (nf x n_k); 0 for an empty label
+ *   E2[i][j]     = v summed over p = p0 .. nt - 1 in that order from 0.0, for every cell, used or not
+ *   peak         = the largest v over p >= p0 (wass_specprod_peak_dev: pa <= p < pb) and the cells with lab_dir (labels) >= 0;
+ *                  *peak_index = (p ny + i) nx + j of the lowest such index among equal values; NaN and -1 if no cell is used
+ * A v of the positive half that is negative or not finite: WASS_ERR_INVALID_ARG (the kernels set a flag; the outputs are then
+ * not defined); the other half is never read.  A label outside -1 .. n - 1: WASS_ERR_INVALID_ARG.
+ * wass_specprod_tables takes S in host memory and stages it in slabs of at most `slab` frequencies (0: as many as fit 16 GiB of
+ * scratch together with the tables); the result does not depend on the slab.  _dev reads S in place.  All outputs are host
+ * memory.  wass_specprod_scratch_bytes says how much device memory a call takes and how many frequencies go per slab, without a
+ * GPU, and checks the same arguments.
+ *
+ * wass_specprod_current_sums_dev: the weighted normal equations of the current fit.  omega[nt], kappa_x[nx], kappa_y[ny],
+ * sigma0[ny][nx] and labels are host memory.  A bin (p, i, j) is taken when labels[i][j] >= 0, pa <= p < pb, w >= threshold_value
+ * and |r| <= gate_value (pass infinity for no gate), with w = v, kx = kappa_x[j], ky = kappa_y[i], d = omega[p] - sigma0[i][j],
+ * r = d - (kx * U + ky * V).  sums[WASS_SPECPROD_*]: AXX = sum (w kx) kx, AXY = sum (w kx) ky, AYY = sum (w ky) ky,
+ * BX = sum (w kx) d, BY = sum (w ky) d, SW = sum w, SR2 = sum (w r) r; *n_bins the bins taken (exact).  Order: per cell over
+ * p ascending from 0.0; block_sum over the 256 cells c = 256 g + t of group g (raster order, an unused cell or one past the map
+ * adds 0.0); then block_sum over t of (groups t, t + 256, .. added in that order from 0.0).  A bin of a used cell in pa .. pb - 1
+ * that is negative or not finite: WASS_ERR_INVALID_ARG.
+ * Every call returns after a synchronisation and gives the same bits on every run. */
+enum {
+    WASS_SPECPROD_AXX = 0,
+    WASS_SPECPROD_AXY,
+    WASS_SPECPROD_AYY,
+    WASS_SPECPROD_BX,
+    WASS_SPECPROD_BY,
+    WASS_SPECPROD_SW,
+    WASS_SPECPROD_SR2,
+    WASS_SPECPROD_NSUMS
+};
+int wass_specprod_scratch_bytes(int nt, int ny, int nx, int p0, int n_dir, int n_k, int slab, int host, size_t* bytes, int* freqs_per_slab);
+int wass_specprod_tables(wass_ctx* ctx, const double* S, int nt, int ny, int nx, int p0, double scale, const int32_t* lab_dir, int n_dir,
+                         const int32_t* lab_k, int n_k, int slab, double* T_dir, double* T_k, double* E2, double* peak_value,
+                         int64_t* peak_index);
+int wass_specprod_tables_dev(wass_ctx* ctx, const double* d_S, int nt, int ny, int nx, int p0, double scale, const int32_t* lab_dir, int n_dir,
+                             const int32_t* lab_k, int n_k, double* T_dir, double* T_k, double* E2, double* peak_value, int64_t* peak_index);
+int wass_specprod_peak_dev(wass_ctx* ctx, const double* d_S, int nt, int ny, int nx, int p0, int pa, int pb, double scale,
+                           const int32_t* labels, double* peak_value, int64_t* peak_index);
+int wass_specprod_current_sums_dev(wass_ctx* ctx, const double* d_S, int nt, int ny, int nx, int pa, int pb, double scale,
+                                   const int32_t* labels, const double* omega, const double* kappa_x, const double* kappa_y,
+                                   const double* sigma0, double U, double V, double threshold_value, double gate_value, double* sums,
+                                   int64_t* n_bins);
 
 /* ---- Feature matcher: the game-theoretic inlier selection of wass_match (src/wass_match/GTMatcher.cpp, iidyn.cpp) as array
  * functions.  A feature is four float32, x y scale angle (the head of a record of FeatureSet::save); a candidate is a pair of

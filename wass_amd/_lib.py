@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("WASS_GPU_LIB") or os.path.join(_HERE, "libwassgpu.so")
 
 WASS_OK = 0
+WASS_ERR_INVALID_ARG = -1
 WASS_ERR_COST_OVERFLOW = -5
 
 
@@ -228,6 +229,7 @@ SYMBOLS = {
     "wass_spec3d_push": (_i, [_vp, _vp, _sz, _sz, C.c_double]),
     "wass_spec3d_push_dev": (_i, [_vp, _vp, _sz, _sz, C.c_double]),
     "wass_spec3d_finish": (_i, [_vp, C.c_double, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "wass_spec3d_finish_dev": (_i, [_vp, C.c_double, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "wass_spec3d_destroy": (None, [_vp]),
     "wass_spec1d_welch": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, _vp]),
     "wass_sosfiltfilt_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
@@ -283,6 +285,14 @@ SYMBOLS = {
     "wass_wavestats_scratch_bytes": (_i, [_i, _i, _i, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
     "wass_wavestats": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, C.c_double, C.c_double, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
     "wass_wavestats_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, C.c_double, C.c_double, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
+    "wass_specprod_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
+    "wass_specprod_tables": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_int64)]),
+    "wass_specprod_tables_dev": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_int64)]),
+    "wass_specprod_peak_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "wass_specprod_current_sums_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, _vp, C.POINTER(C.c_int64)]),
     "wass_match_scratch_bytes": (_i, [_i, _i, C.POINTER(_sz)]),
     "wass_match_knn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "wass_match_knn_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),

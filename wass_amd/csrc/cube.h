@@ -1,5 +1,5 @@
 // cube.h -- what the one-shot operators of the count x H x W cube share (filter, radiance, polarimetric, pyramid, visibility,
-// wavestats): the host scaffolding of a call that allocates its scratch, runs and frees it.  Plain functions and one RAII struct;
+// wavestats, specprod): the host scaffolding of a call that allocates its scratch, runs and frees it.  Plain functions and one RAII struct;
 // every operator keeps its own plan and byte formula.  (The ordered-key maxima of their kernels are reduce.h's.)
 // A call makes ONE hipMalloc and one hipFree by design: the scratch of a cube is gigabytes and is not kept in the context.
 // The handles of spectrum.hip (wass_spec3d, wass_spatial_filter) hold an Arena for their lifetime and stage through the same

@@ -116,6 +116,18 @@ template <int N, class F> __device__ __forceinline__ void block_tree(F merge)
     }
 }
 
+// The sum of a block of N doubles in every thread: sh[t] = v, a barrier, block_tree with +=, and a barrier after the read so that sh
+// can be filled again at once.
+template <int N> __device__ __forceinline__ double block_sum(double v, double* sh)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    block_tree<N>([&](int t, int u) { sh[t] += sh[u]; });
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
 // Inclusive prefix sum of a[0 .. N) in LDS by N threads (Hillis-Steele): for o = 1, 2, .. N/2: thread t reads a[t - o] (0 for t < o),
 // barrier, a[t] += that, barrier.  Element t ends as the doubling order makes it (integers here: the order cannot show).  The
 // caller barriers between filling a[] and the call; the call ends with a barrier, so any thread may read any element after it.

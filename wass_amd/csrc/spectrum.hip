@@ -162,17 +162,6 @@ __global__ void __launch_bounds__(256) k_dft_stage(const DftArgs a)
             }
 }
 
-// the sum of a block of 256 in every thread: reduce.h's tree, and a barrier after the read so that sh can be filled again at once
-static __device__ __forceinline__ double block_sum(double v, double* sh)
-{
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    block_tree<256>([&](int t, int u) { sh[t] += sh[u]; });
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // One thread per cell, the frames in order: the cell's mean over its frames that are not NaN (np.nanmean(axis=0) of the float32
 // segment times datascale: a float32 sum), NaN and *flag = 1 for a cell that is NaN throughout.  part[block] = the fp64 sum of
 // the block's cells after the fill (the cells of all-NaN columns count as 0).
@@ -196,7 +185,7 @@ __global__ void __launch_bounds__(256) k_seg_cell(const float* __restrict__ src,
         if (!cnt) *flag = 1;
         else tot = sd + (double)(nt - cnt) * (double)m;
     }
-    tot = block_sum(tot, sh);
+    tot = block_sum<256>(tot, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -206,7 +195,7 @@ __global__ void __launch_bounds__(256) k_seg_mean(const double* __restrict__ par
     __shared__ double sh[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < npart; i += 256) s += part[i];
-    s = block_sum(s, sh);
+    s = block_sum<256>(s, sh);
     if (threadIdx.x == 0) mean[0] = s / count;
 }
 
@@ -260,7 +249,7 @@ __global__ void __launch_bounds__(256) k_w1_mean(const float* __restrict__ x, in
     x += (size_t)blockIdx.x * T;
     double s = 0.0;
     for (int i = threadIdx.x; i < T; i += 256) s += (double)(x[i] * scale);
-    s = block_sum(s, sh);
+    s = block_sum<256>(s, sh);
     if (threadIdx.x == 0) smean[blockIdx.x] = s / (double)T;
 }
 
@@ -276,7 +265,7 @@ __global__ void __launch_bounds__(256) k_w1_prep(const float* __restrict__ x, in
     const double m = smean[ser];
     double s = 0.0;
     for (int i = threadIdx.x; i < nps; i += 256) s += (double)(p[i] * scale) - m;
-    const double sm = block_sum(s, sh) / (double)nps;
+    const double sm = block_sum<256>(s, sh) / (double)nps;
     for (int i = threadIdx.x; i < nps; i += 256) B[(size_t)i * ncol + col] = (float)((((double)(p[i] * scale) - m) - sm) * win[i]);
 }
 
@@ -291,7 +280,7 @@ __global__ void __launch_bounds__(256) k_w1_power(const float* __restrict__ Xre,
         const double re = (double)Xre[(size_t)m * ncol + i], im = (double)Xim[(size_t)m * ncol + i];
         s += re * re + im * im;
     }
-    s = block_sum(s, sh);
+    s = block_sum<256>(s, sh);
     // one-sided: every bin but DC and (even nps) Nyquist stands for two
     const bool twice = m != 0 && !(nps % 2 == 0 && m == nps / 2);
     if (threadIdx.x == 0) out[m] = s * dens * (twice ? 2.0 : 1.0);
@@ -504,7 +493,8 @@ extern "C" int wass_spec3d_push(wass_spec3d* h, const float* seg, size_t stride_
     return spec3d_run(h, h->raw, (size_t)h->ny * h->nx, h->nx, datascale);
 }
 
-extern "C" int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* n_segments, int* had_all_nan_cell)
+// the end of a Welch accumulation: the scaled sum to S, which `kind` says is host or device memory
+static int spec3d_finish(wass_spec3d* h, double scale, double* S, hipMemcpyKind kind, int* n_segments, int* had_all_nan_cell)
 {
     if (!h) return WASS_ERR_INVALID_ARG;
     wass_ctx* c = h->c;
@@ -516,7 +506,7 @@ extern "C" int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* 
     int flag = 0;
     hipLaunchKernelGGL(k_spec_scale, dim3((unsigned)((win + 255) / 256)), dim3(256), 0, s, h->S, win, scale);
     WASS_HIP(c, hipGetLastError());
-    WASS_HIP(c, hipMemcpyAsync(S, h->S, win * 8, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemcpyAsync(S, h->S, win * 8, kind, s));
     WASS_HIP(c, hipMemcpyAsync(&flag, h->flag, sizeof flag, hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipMemsetAsync(h->S, 0, win * 8, s));          // the handle starts over
     WASS_HIP(c, hipMemsetAsync(h->flag, 0, 256, s));
@@ -525,6 +515,16 @@ extern "C" int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* 
     if (had_all_nan_cell) *had_all_nan_cell = flag;
     h->nseg = 0;
     return WASS_OK;
+}
+
+extern "C" int wass_spec3d_finish(wass_spec3d* h, double scale, double* S, int* n_segments, int* had_all_nan_cell)
+{
+    return spec3d_finish(h, scale, S, hipMemcpyDeviceToHost, n_segments, had_all_nan_cell);
+}
+
+extern "C" int wass_spec3d_finish_dev(wass_spec3d* h, double scale, double* d_S, int* n_segments, int* had_all_nan_cell)
+{
+    return spec3d_finish(h, scale, d_S, hipMemcpyDeviceToDevice, n_segments, had_all_nan_cell);
 }
 
 extern "C" int wass_spec1d_welch(wass_ctx* c, const float* series, int n_series, int n_samples, int nperseg, double fs, double scale, double* S)

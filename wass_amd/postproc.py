@@ -126,6 +126,42 @@ class Spectrum3D(_Handle):
         self.ctx._check(self.ctx._lib.wass_spec3d_finish(self._h, float(scale), S.ctypes.data, C.byref(n), C.byref(flag)))
         return S, n.value, bool(flag.value)
 
+    def finish_dev(self, scale: float = 1.0, out=None):
+        """finish with S left on the device: a float64 tensor of nt x ny x nx (`out`, contiguous, or a new one), the same bits."""
+        import torch
+        shape = (self.nt, self.ny, self.nx)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.ctx.device_id}")
+        elif not _is_device(out) or tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float64 device tensor of shape {shape}")
+        n, flag = C.c_int(), C.c_int()
+        self.ctx._check(self.ctx._lib.wass_spec3d_finish_dev(self._h, float(scale), out.data_ptr(), C.byref(n), C.byref(flag)))
+        return out, n.value, bool(flag.value)
+
+
+def compute_3D_spectrum_dev(data, du: float, dt: float, datascale: float = 1.0, ctx: Context | None = None):
+    """compute_3D_spectrum with the spectrum left in device memory: (S float64 tensor [Nt, Ny, Nx], kx, ky, f, had_nan) with the
+    1-D axes of the reference (KX, KY = np.meshgrid(kx, ky)).  `data` is a host array (segments are uploaded) or a float32 device
+    tensor (read in place).  had_nan: a cell was NaN through a whole segment, and S is NaN everywhere, as in compute_3D_spectrum."""
+    p = spectrum3d_plan(data.shape, du, dt)
+    if ctx is None:
+        ctx = Context(0)
+    dev = _is_device(data)
+    if dev:
+        import torch
+        if data.dtype != torch.float32 or data.stride(2) != 1:
+            data = data.to(torch.float32).contiguous()
+        torch.cuda.current_stream(data.device).synchronize()
+    with Spectrum3D(ctx, p.nt, p.ny, p.nx, p.win_t, p.win_y, p.win_x) as sp:
+        for s in p.starts:
+            seg = data[s:s + p.nt, p.r0:p.r0 + p.ny, p.c0:p.c0 + p.nx]
+            (sp.push_dev if dev else sp.push)(seg, datascale)
+        S, n, had_nan = sp.finish_dev(p.scale)
+    assert n == len(p.starts)
+    if had_nan:
+        S.fill_(float("nan"))
+    return S, p.kx, p.ky, p.f, had_nan
+
 
 def compute_3D_spectrum(data, du: float, dt: float, segments: int = 8, datascale: float = 1.0, ctx: Context | None = None):
     """(S_welch float64 [Nt, Ny, Nx], KX, KY, f) as the reference returns them.  `segments` is accepted and ignored (the
@@ -1430,3 +1466,318 @@ def wave_statistics(data, dt: float, datascale: float = 1.0, crossing: str = "up
         maps["n_cross"] = n_cross
         maps.update(derived)
     return WaveStatistics(hist=hist, hist_width=hist_width, dt=dt, crossing=crossing, **maps)
+
+
+# ---- spectral products of S(f, ky, kx): directional spectra and the surface current (beyond the reference; DESIGN.md, "Spectral
+# products", has the definitions).  Everything that needs atan2, sqrt or tanh is evaluated here in numpy fp64; the device gets label
+# maps and sums (specprod.hip).
+_TWO_PI = 2.0 * np.pi
+CURRENT_SUMS = ("Axx", "Axy", "Ayy", "bx", "by", "sw", "sr2")
+
+
+def dft_axes(nt: int, ny: int, nx: int, du: float, dt: float):
+    """(kx, ky, f): the exact bins of np.fft.fftn after np.fft.fftshift, as angular wavenumbers 2 pi m / (n du) and frequencies
+    m / (nt dt), m = -(n // 2) .. .  The reference's wavenumber axes (spectrum3d_plan) are spaced 2 pi / (du (n - 1)) instead; the
+    functions below take either."""
+    def ax(n, d):
+        return (np.arange(n) - n // 2) * (1.0 / (n * d))            # np.fft.fftfreq's rounding
+    return _TWO_PI * ax(int(nx), du), _TWO_PI * ax(int(ny), du), ax(int(nt), dt)
+
+
+def _spacing(a) -> float:
+    return float((a[-1] - a[0]) / (len(a) - 1)) if len(a) > 1 else 1.0
+
+
+def _spec_axes(shape, kx, ky, f):
+    """the axes as float64, checked against the cube; the positive half as (p0, nf)"""
+    if len(shape) != 3:
+        raise ValueError("S must be nt x ny x nx")
+    nt, ny, nx = (int(v) for v in shape)
+    kx, ky, f = (np.ascontiguousarray(a, np.float64) for a in (kx, ky, f))
+    if kx.shape != (nx,) or ky.shape != (ny,) or f.shape != (nt,):
+        raise ValueError(f"axes of {len(f)}, {len(ky)}, {len(kx)} bins for a spectrum of shape {(nt, ny, nx)}")
+    for a in (kx, ky, f):
+        if not np.isfinite(a).all() or (len(a) > 1 and not (np.diff(a) > 0).all()):
+            raise ValueError("every axis must be finite and ascending")
+    P = np.flatnonzero(f > 0.5 * _spacing(f))            # not f > 0: np.arange may leave the reference's zero bin a rounding error above zero
+    if not len(P):
+        raise ValueError("no frequency above zero")
+    return kx, ky, f, int(P[0]), len(P)
+
+
+def spectral_label_maps(kx, ky, ndir: int, dk: float | None = None, k_min: float = 0.0, k_max: float = np.inf):
+    """(L_dir, L_k, nk, kmod) for wavenumber axes kx, ky: int32 ny x nx maps, -1 = unused.  The propagation vector of cell (i, j) is
+    kappa = (-kx[j], -ky[i]) (numpy's forward transform puts cos(k0 . r - w0 t) at (+f0, -k0)); theta = atan2(kappa_y, kappa_x) mod
+    2 pi, counter-clockwise from +x of the grid.  L_dir = floor(theta / dtheta + 0.5) mod ndir: bins centred on b * dtheta.
+    L_k = floor(kmod / dk + 0.5) with dk = max(dkx, dky) by default; rings from nk = floor(min(max|kx|, max|ky|) / dk) + 1 on (the
+    corners) are unused, as are kmod == 0 and everything outside [k_min, k_max]."""
+    ndir = int(ndir)
+    if ndir < 1:
+        raise ValueError("ndir must be at least 1")
+    kx, ky = np.asarray(kx, np.float64), np.asarray(ky, np.float64)
+    dk = max(_spacing(kx), _spacing(ky)) if dk is None else float(dk)
+    if not (dk > 0 and np.isfinite(dk)) or not k_min >= 0 or not k_max >= k_min:
+        raise ValueError("dk must be positive and 0 <= k_min <= k_max")
+    KX, KY = np.meshgrid(-kx, -ky)
+    kmod = np.sqrt(KX * KX + KY * KY)
+    theta = np.mod(np.arctan2(KY, KX), _TWO_PI)
+    used = (kmod != 0) & (kmod >= k_min) & (kmod <= k_max)
+    L_dir = np.where(used, np.mod(np.floor(theta / (_TWO_PI / ndir) + 0.5), ndir), -1).astype(np.int32)
+    ring = np.floor(kmod / dk + 0.5)
+    nk = int(np.floor(min(np.abs(kx).max(), np.abs(ky).max()) / dk)) + 1
+    L_k = np.where(used & (ring < nk), ring, -1).astype(np.int32)
+    return L_dir, L_k, nk, kmod
+
+
+def spectrum_products_scratch_bytes(nt: int, ny: int, nx: int, nf: int | None = None, ndir: int = 72, nk: int | None = None, slab: int = 0,
+                                    host: bool = True):
+    """(bytes of device scratch, frequencies per slab) of one spectrum_products call; no GPU needed.  nf: the frequencies above zero
+    (default (nt - 1) // 2, the DFT's); nk: the rings (default min(ny, nx) // 2 + 1).  The label maps, their cell lists, the two
+    tables, E2 and the peak's partials, and for a host S a slab of `slab` frequencies (0: as many as fit 16 GiB), each part rounded
+    up to 256 bytes."""
+    nt, ny, nx = int(nt), int(ny), int(nx)
+    nf = (nt - 1) // 2 if nf is None else int(nf)
+    nk = min(ny, nx) // 2 + 1 if nk is None else int(nk)
+    return _scratch_bytes("specprod", (nt, ny, nx, nt - nf, int(ndir), nk, int(slab), int(bool(host))), f"{nt}, {ny}, {nx}, nf {nf}")
+
+
+def _check_spec(ctx, rc):
+    """the library's refusal of a bin that is negative or not finite is a ValueError, like the host's argument checks"""
+    from . import _lib
+    if rc == _lib.WASS_ERR_INVALID_ARG:
+        raise ValueError(ctx._lib.wass_last_error(ctx._h).decode())
+    ctx._check(rc)
+
+
+def _device_spectrum(S, ctx):
+    """S as a dense float64 device tensor: a host array is uploaded once, a device tensor is taken as it is"""
+    import torch
+    if _is_device(S):
+        if S.dtype != torch.float64 or not S.is_contiguous():
+            S = S.to(torch.float64).contiguous()
+        torch.cuda.current_stream(S.device).synchronize()
+        return S
+    S = np.ascontiguousarray(S, np.float64)
+    S = torch.from_numpy(S if S.flags.writeable else S.copy()).to(torch.device("cuda", ctx.device_id))
+    torch.cuda.current_stream(S.device).synchronize()
+    return S
+
+
+@dataclass
+class SpectralProducts:
+    """What spectrum_products returns: numpy fp64.  With dkx, dky, df the spacings of the axes, dtheta = 2 pi / ndir and the factor 2
+    for the half of the spectrum that is left out (S is even under (f, k) -> (-f, -k))."""
+    freq: np.ndarray                # f[P], the frequencies above zero
+    theta: np.ndarray               # b * dtheta, the centres of the direction bins (towards, counter-clockwise from +x of the grid)
+    k: np.ndarray                   # b * dk, the centres of the wavenumber rings
+    D: np.ndarray                   # [nf][ndir] frequency-direction spectrum: 2 T_dir dkx dky / dtheta
+    S_f: np.ndarray                 # [nf] frequency spectrum: 2 dkx dky sum_b T_dir
+    F_fk: np.ndarray                # [nf][nk] frequency-wavenumber spectrum: 2 T_k dkx dky / dk
+    S_k: np.ndarray                 # [nk] wavenumber spectrum: sum_p F_fk df
+    E_k2: np.ndarray                # [ny][nx] 2-D wavenumber spectrum: 2 E2 df, on the axes given (propagation is towards -k)
+    mean_direction: np.ndarray      # [nf] atan2(b1, a1)
+    spread: np.ndarray              # [nf] sqrt(2 (1 - hypot(a1, b1)))
+    m0: float                       # sum_p S_f df
+    peak_value: float               # the largest bin of the positive half over the used cells, and where it is
+    peak_index: tuple               # (p, i, j) into S, or None
+    T_dir: np.ndarray               # the device's sums
+    T_k: np.ndarray
+    E2: np.ndarray
+    kx: np.ndarray
+    ky: np.ndarray
+    f: np.ndarray
+    dk: float
+
+    def summary(self) -> dict:
+        """m0, Hm0 = 4 sqrt(m0), the peak frequency (of S_f), the peak direction (the bin of the largest D), the energy-weighted
+        mean direction atan2(sum D sin, sum D cos) mod 2 pi, and the peak bin as (f, kappa_x, kappa_y)."""
+        pf, pd = np.unravel_index(int(np.argmax(self.D)), self.D.shape)
+        c, s = float((self.D * np.cos(self.theta)).sum()), float((self.D * np.sin(self.theta)).sum())
+        out = {"m0": self.m0, "Hm0": float(4.0 * np.sqrt(self.m0)), "peak_frequency": float(self.freq[int(np.argmax(self.S_f))]),
+               "peak_direction": float(self.theta[pd]), "mean_direction": float(np.mod(np.arctan2(s, c), _TWO_PI)), "peak": None}
+        if self.peak_index is not None:
+            p, i, j = self.peak_index
+            out["peak"] = (float(self.f[p]), float(-self.kx[j]), float(-self.ky[i]))
+        return out
+
+
+def _derive_products(T_dir, T_k, E2, dkx, dky, df, dk, dtheta):
+    nf, ndir = T_dir.shape
+    D = 2.0 * T_dir * dkx * dky / dtheta
+    srow = np.zeros(nf)
+    for b in range(ndir):                                # sequential in b: the stated order
+        srow = srow + T_dir[:, b]
+    S_f = 2.0 * dkx * dky * srow
+    F_fk = 2.0 * T_k * dkx * dky / dk
+    S_k = np.zeros(T_k.shape[1])
+    for p in range(nf):
+        S_k = S_k + F_fk[p] * df
+    theta = np.arange(ndir) * dtheta
+    c, s = np.cos(theta), np.sin(theta)
+    sa, sb, sd = np.zeros(nf), np.zeros(nf), np.zeros(nf)
+    for b in range(ndir):
+        sa, sb, sd = sa + D[:, b] * c[b], sb + D[:, b] * s[b], sd + D[:, b]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a1, b1 = sa / sd, sb / sd
+        mean_direction = np.arctan2(b1, a1)
+        spread = np.sqrt(2.0 * (1.0 - np.hypot(a1, b1)))
+    m0 = 0.0
+    for p in range(nf):
+        m0 = m0 + S_f[p] * df
+    return dict(theta=theta, D=D, S_f=S_f, F_fk=F_fk, S_k=S_k, E_k2=2.0 * E2 * df, mean_direction=mean_direction, spread=spread, m0=float(m0))
+
+
+def spectrum_tables(S, p0: int, L_dir, ndir: int, L_k, nk: int, scale: float = 1.0, ctx: Context | None = None, slab: int = 0):
+    """(T_dir [nf][ndir], T_k [nf][nk], E2 [ny][nx], peak value, peak flat index) of the frequencies p0 .. nt - 1 of S for label
+    maps given as they are (int32 ny x nx, -1 = unused): what spectrum_products hands to the device after it has made the maps."""
+    if len(S.shape) != 3:
+        raise ValueError("S must be nt x ny x nx")
+    nt, ny, nx = (int(v) for v in S.shape)
+    p0, ndir, nk = int(p0), int(ndir), int(nk)
+    L_dir, L_k = np.ascontiguousarray(L_dir, np.int32), np.ascontiguousarray(L_k, np.int32)
+    if L_dir.shape != (ny, nx) or L_k.shape != (ny, nx) or not 0 <= p0 < nt or ndir < 1 or nk < 1:
+        raise ValueError("label maps of ny x nx, 0 <= p0 < nt and at least one label of each kind are needed")
+    if ctx is None:
+        ctx = Context(0)
+    nf = nt - p0
+    T_dir, T_k, E2 = np.empty((nf, ndir)), np.empty((nf, nk)), np.empty((ny, nx))
+    pv, pi = C.c_double(), C.c_int64()
+    outs = (T_dir.ctypes.data, T_k.ctypes.data, E2.ctypes.data, C.byref(pv), C.byref(pi))
+    if _is_device(S):
+        d_S = _device_spectrum(S, ctx)
+        _check_spec(ctx, ctx._lib.wass_specprod_tables_dev(ctx._h, d_S.data_ptr(), nt, ny, nx, p0, float(scale), L_dir.ctypes.data, ndir,
+                                                           L_k.ctypes.data, nk, *outs))
+    else:
+        S = np.ascontiguousarray(S, np.float64)
+        _check_spec(ctx, ctx._lib.wass_specprod_tables(ctx._h, S.ctypes.data, nt, ny, nx, p0, float(scale), L_dir.ctypes.data, ndir,
+                                                       L_k.ctypes.data, nk, int(slab), *outs))
+    return T_dir, T_k, E2, pv.value, int(pi.value)
+
+
+def spectrum_products(S, kx, ky, f, ndir: int = 72, dk: float | None = None, k_min: float = 0.0, k_max: float = np.inf, scale: float = 1.0,
+                      ctx: Context | None = None, slab: int = 0) -> SpectralProducts:
+    """The spectral half of the wave product: the frequency-direction spectrum, mean direction and spread, the frequency-wavenumber
+    and wavenumber spectra and the peak of S(f, ky, kx), an nt x ny x nx float64 spectrum with ascending uniform axes f, ky, kx
+    (compute_3D_spectrum[_dev]'s, or dft_axes').  S is a host array (staged in slabs of at most `slab` frequencies; 0: as many as fit
+    16 GiB) or a device tensor (read in place: nothing of S is downloaded).  Only the frequencies above half a bin, f > df / 2, are read (the
+    reference's zero bin is a rounding error above zero); a bin there that is negative or not finite is a ValueError.  The sums run on the GPU in fp64 in a fixed order ("Spectral
+    products"): the same bits on every run, for host and device input and for every slab.
+    scale multiplies S on the way in.  compute_3D_spectrum leaves sum S dkx dky df at the variance of the (window-corrected) surface
+    divided by nt * ny * nx of the window, so scale = nt * ny * nx makes m0 that variance (less the bins at f = 0, at the Nyquist
+    frequency and at k = 0, which are left out) and Hm0 the significant wave height in the units of the data."""
+    nt, ny, nx = (int(v) for v in S.shape) if len(S.shape) == 3 else (0, 0, 0)
+    kx, ky, f, p0, nf = _spec_axes(S.shape, kx, ky, f)
+    scale = float(scale)
+    if not (scale > 0 and np.isfinite(scale)):
+        raise ValueError("scale must be positive and finite")
+    L_dir, L_k, nk, _ = spectral_label_maps(kx, ky, ndir, dk, k_min, k_max)
+    ndir = int(ndir)
+    dkx, dky, df = _spacing(kx), _spacing(ky), _spacing(f)
+    dk = max(dkx, dky) if dk is None else float(dk)
+    T_dir, T_k, E2, pv, pi = spectrum_tables(S, p0, L_dir, ndir, L_k, nk, scale, ctx, slab)
+    at = None if pi < 0 else (pi // (ny * nx), pi % (ny * nx) // nx, pi % nx)
+    return SpectralProducts(freq=f[p0:], k=np.arange(nk) * dk, peak_value=pv, peak_index=at, T_dir=T_dir, T_k=T_k, E2=E2, kx=kx, ky=ky, f=f,
+                            dk=dk, **_derive_products(T_dir, T_k, E2, dkx, dky, df, dk, _TWO_PI / ndir))
+
+
+def spectrum_peak(S, labels, pa: int, pb: int, p0: int, scale: float = 1.0, ctx: Context | None = None):
+    """(value, flat index (p ny + i) nx + j): the largest S * scale over the frequencies pa <= p < pb and the cells with labels >= 0, the
+    lowest index among equals; (NaN, -1) without a used bin.  p0 is the first frequency above zero: all bins from there on are
+    checked, and one that is negative or not finite is a ValueError."""
+    if ctx is None:
+        ctx = Context(0)
+    d_S = _device_spectrum(S, ctx)
+    nt, ny, nx = (int(v) for v in d_S.shape)
+    labels = np.ascontiguousarray(labels, np.int32)
+    if labels.shape != (ny, nx):
+        raise ValueError("labels must be ny x nx")
+    pv, pi = C.c_double(), C.c_int64()
+    _check_spec(ctx, ctx._lib.wass_specprod_peak_dev(ctx._h, d_S.data_ptr(), nt, ny, nx, int(p0), int(pa), int(pb), float(scale), labels.ctypes.data,
+                                                     C.byref(pv), C.byref(pi)))
+    return pv.value, int(pi.value)
+
+
+def current_sums(S, omega, kappa_x, kappa_y, sigma0, labels, U: float, V: float, threshold_value: float, gate_value: float = np.inf,
+                 pa: int = 0, pb: int | None = None, scale: float = 1.0, ctx: Context | None = None):
+    """(sums, n): the weighted normal equations of the current fit over the bins (p, i, j) with labels[i][j] >= 0, pa <= p < pb,
+    w = S * scale >= threshold_value and |r| <= gate_value, r = d - (kappa_x[j] U + kappa_y[i] V), d = omega[p] - sigma0[i][j]:
+    sums = {Axx: sum (w kx) kx, Axy: sum (w kx) ky, Ayy: sum (w ky) ky, bx: sum (w kx) d, by: sum (w ky) d, sw: sum w,
+    sr2: sum (w r) r}, n the bins taken.  Every map is taken as given, so a probe can use values that are exact in binary.  S is a
+    device tensor, or a host array that is uploaded whole."""
+    if ctx is None:
+        ctx = Context(0)
+    d_S = _device_spectrum(S, ctx)
+    nt, ny, nx = (int(v) for v in d_S.shape)
+    pb = nt if pb is None else int(pb)
+    omega, kappa_x, kappa_y, sigma0 = (np.ascontiguousarray(a, np.float64) for a in (omega, kappa_x, kappa_y, sigma0))
+    labels = np.ascontiguousarray(labels, np.int32)
+    if omega.shape != (nt,) or kappa_x.shape != (nx,) or kappa_y.shape != (ny,) or sigma0.shape != (ny, nx) or labels.shape != (ny, nx):
+        raise ValueError("omega[nt], kappa_x[nx], kappa_y[ny], sigma0[ny][nx] and labels[ny][nx] are needed")
+    sums, n = np.empty(len(CURRENT_SUMS)), C.c_int64()
+    _check_spec(ctx, ctx._lib.wass_specprod_current_sums_dev(ctx._h, d_S.data_ptr(), nt, ny, nx, int(pa), pb, float(scale), labels.ctypes.data,
+                                                             omega.ctypes.data, kappa_x.ctypes.data, kappa_y.ctypes.data, sigma0.ctypes.data,
+                                                             float(U), float(V), float(threshold_value), float(gate_value), sums.ctypes.data,
+                                                             C.byref(n)))
+    return dict(zip(CURRENT_SUMS, (float(v) for v in sums))), int(n.value)
+
+
+def solve_current(s: dict, n: int):
+    """(U, V, singular) of [Axx Axy; Axy Ayy] (U, V) = (bx, by) by Cramer's rule: det = Axx Ayy - Axy Axy, U = (bx Ayy - by Axy) / det,
+    V = (Axx by - Axy bx) / det.  Fewer than two bins or a determinant that is not positive: NaN and singular."""
+    det = s["Axx"] * s["Ayy"] - s["Axy"] * s["Axy"]
+    if n < 2 or not det > 0:
+        return float("nan"), float("nan"), True
+    return (s["bx"] * s["Ayy"] - s["by"] * s["Axy"]) / det, (s["Axx"] * s["by"] - s["Axy"] * s["bx"]) / det, False
+
+
+@dataclass
+class CurrentFit:
+    """What dispersion_current returns.  (U, V) is the current along +x and +y of the grid, in the units of 2 pi f / k."""
+    U: float
+    V: float
+    speed: float            # hypot(U, V)
+    direction: float        # atan2(V, U) mod 2 pi: where the current goes, counter-clockwise from +x
+    n_bins: int             # the bins of the last round
+    rms: float              # sqrt(sr2 / sw) of the last round: the weighted residual, at the current that round started from
+    singular: bool
+    trace: list             # one dict per round: round, U, V, n_bins, singular and the seven sums
+
+
+def dispersion_current(S, kx, ky, f, depth: float = np.inf, g: float = 9.81, threshold: float = 0.1, f_min: float = 0.0, f_max: float = np.inf,
+                       k_min: float = 0.0, k_max: float = np.inf, iterations: int = 3, gate: float = 2.0, scale: float = 1.0,
+                       ctx: Context | None = None) -> CurrentFit:
+    """The surface current that Doppler-shifts the dispersion shell of S(f, ky, kx): the weighted least-squares fit of
+    omega = sigma0(k) + kappa . (U, V) over the bins at or above threshold * (the largest bin), sigma0 = sqrt(g k tanh(k depth)),
+    weights S.  Round 0 takes all those bins with U = V = 0; each of the `iterations` rounds after it takes those with
+    |omega - sigma0 - kappa . (U, V)| <= gate * domega at the current of the round before and solves again.  A round that is
+    singular (fewer than two bins, or all kappa on one line) ends the fit with NaN.  The used cells are those with k_min <= |k| <=
+    k_max and k != 0, the used frequencies those above half a bin with f_min <= f <= f_max.  S: a device tensor (read in place) or a host
+    array (uploaded once).  The sums run on the GPU in a fixed order; the 2 x 2 solve is Cramer's rule on the host."""
+    kx, ky, f, p0, nf = _spec_axes(S.shape, kx, ky, f)
+    if not (g > 0 and depth > 0 and threshold >= 0 and gate >= 0 and iterations >= 0):
+        raise ValueError("g, depth > 0 and threshold, gate, iterations >= 0 are needed")
+    if ctx is None:
+        ctx = Context(0)
+    labels, _, _, kmod = spectral_label_maps(kx, ky, 1, None, k_min, k_max)
+    sigma0 = np.sqrt(g * kmod) if np.isinf(depth) else np.sqrt(g * kmod * np.tanh(kmod * depth))
+    omega, domega = _TWO_PI * f, _TWO_PI * _spacing(f)
+    Pu = p0 + np.flatnonzero((f[p0:] >= f_min) & (f[p0:] <= f_max))
+    pa, pb = (int(Pu[0]), int(Pu[-1]) + 1) if len(Pu) else (p0, p0)
+    d_S = _device_spectrum(S, ctx)
+    smax, _ = spectrum_peak(d_S, labels, pa, pb, p0, scale, ctx)
+    thr = threshold * smax
+    U = V = 0.0
+    trace, singular = [], bool(np.isnan(smax))
+    sums, n = dict.fromkeys(CURRENT_SUMS, 0.0), 0
+    for m in range(int(iterations) + 1):
+        if singular:
+            break
+        sums, n = current_sums(d_S, omega, -kx, -ky, sigma0, labels, U, V, thr, gate * domega if m else np.inf, pa, pb, scale, ctx)
+        U, V, singular = solve_current(sums, n)
+        trace.append({"round": m, "U": U, "V": V, "n_bins": n, "singular": singular, **sums})
+    if singular:
+        U = V = float("nan")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rms = float(np.sqrt(np.float64(sums["sr2"]) / np.float64(sums["sw"])))
+    return CurrentFit(U=U, V=V, speed=float(np.hypot(U, V)), direction=float(np.mod(np.arctan2(V, U), _TWO_PI)), n_bins=n, rms=rms,
+                      singular=bool(singular), trace=trace)
