@@ -107,7 +107,7 @@ typedef struct {
     int num_disp;         /* MAX_DISPARITY, multiple of 16                   */
     int win;              /* WINSIZE (odd)                                   */
     int P1, P2;           /* DENSE_P1_MULT*win*win, DENSE_P2_MULT*win*win    */
-    int uniq_ratio;       /* DENSE_UNIQUENESS_RATIO                          */
+    int uniq_ratio;       /* DENSE_UNIQUENESS_RATIO, at most 100 (< 0: 10)   */
     int disp12_max_diff;  /* DENSE_DISP12MAXDIFF                             */
     int prefilter_cap;    /* DENSE_PREFILTER_CAP                             */
     int speckle_win;      /* DENSE_SPECKLE_WINDOW_SIZE (> 0: cv::filterSpeckles) */
@@ -122,7 +122,11 @@ typedef struct {
  * [num_disp, num_disp + w).  right/left: w x h u8, pitch in bytes.
  * disp16_out: w x h int16 (4 fractional bits), in the right image's frame.
  * Returns WASS_ERR_COST_OVERFLOW (result still written) if a block cost
- * exceeded the int16 range the reference's scalar and SIMD builds agree on. */
+ * exceeded the int16 range the reference's scalar and SIMD builds agree on.
+ * uniq_ratio above 100 is refused with WASS_ERR_INVALID_ARG: the reference's
+ * factor 100 - ratio is then negative and it rejects every pixel with a
+ * positive cost outside best +- 1, which the selection kernels' unsigned
+ * 24-bit product does not reproduce. */
 /* DENSE_SCALE != 1 (:788-796): both crops are first resized with cv::resize INTER_CUBIC -- by (scale, 1) when the scale is
  * above 1, by (scale, scale) below -- and disp16_out has the size of the RESIZED crops: */
 int wass_dense_input_size(int w, int h, double dense_scale, int* ws, int* hs);

@@ -27,6 +27,31 @@ def _pad(right, left, D, off=0):
     return R, L
 
 
+# What these cases can see: synth.make_pair ramps the true disparity by 0.6 D over the picture's HEIGHT.  Below roughly h >= 8 D / 13
+# rows (a pixel of disparity per row, thirteen across a 13-row window; these cases have 2 to 50 per row) no window matches any
+# disparity, every cost is huge and S saturates.  On the CPU oracle, window 13 (11 at D = 96):
+#
+#   w, h, D, paths        pixels whose whole S vector is 0x7FFF    valid in raw
+#   320, 64, 256, 8       98.5 %                                    1.4 %
+#   340, 32, 272, 8       98.6 %                                    1.3 %
+#   460, 48, 384, 8       99.3 %                                    0.6 %
+#   600, 64, 512, 8       99.2 %                                    0.7 %
+#   720, 40, 640, 8       98.0 %                                    1.6 %
+#   800, 40, 768, 8       98.8 %                                    1.0 %
+#   950, 40, 896, 8       98.3 %  (the only NP = 7 case)            1.2 %
+#   1100, 40, 1024, 8     98.1 %                                    1.6 %
+#   460, 48, 384, 5       77.5 %                                    16.5 %
+#   950, 40, 896, 5       74.8 %                                    12.7 %
+#   150, 70, 128, 8       95.2 %                                    4.3 %
+#   257, 33, 96, 8        72.0 %                                    22.4 %
+#   300, 37, 256, 5       64.9 %  (_FUSED5_CASES)                   24.8 %
+#   290, 131, 192, 5      70.5 %  (_FUSED5_CASES)                   22.4 %
+#
+# In the 8-path rows from D = 256 up 99.99 % of all S entries are 0x7FFF: those cases compare a volume of one constant and a map of
+# "invalid", and a wrong step across a lane or slot boundary passes them.  They stay for the schedule they drive (C, and S wherever it
+# is not saturated); what they cannot see is held by tests/test_sgm_select_gpu.py on the scenes of tests/sgm_scenes.py, whose disparity
+# varies over the columns.  A new large-D case belongs there: take a scene from sgm_scenes, and let tests/test_sgm_scenes.py show on the
+# oracle that it is not saturated.
 CASES = [
     # w, h, D, ndirs, win, min_disp, off
     (64, 48, 16, 5, 13, 1, 0),

@@ -68,6 +68,9 @@ static int make_dims(wass_ctx* c, int w, int h, const wass_sgm_params* p, SgmDim
     if (d.P2 < d.P1 + 1) d.P2 = d.P1 + 1;
     if (d.P2 > 32767) return set_err(c, WASS_ERR_INVALID_ARG, "P2 %d does not fit the int16 cost type", d.P2);
     d.uniq = p->uniq_ratio >= 0 ? p->uniq_ratio : 10;
+    // wta_batch_eval forms S * (100 - uniq) with __umul24: the reference's product only while the factor is not negative (above 100 the
+    // reference rejects every pixel that has a disparity outside best +- 1; the 24-bit unsigned product would accept some)
+    if (d.uniq > 100) return set_err(c, WASS_ERR_INVALID_ARG, "DENSE_UNIQUENESS_RATIO (uniq_ratio) %d > 100 is not supported", d.uniq);
     d.d12 = p->disp12_max_diff > 0 ? p->disp12_max_diff : 1;
     d.ftzero = (p->prefilter_cap > 15 ? p->prefilter_cap : 15) | 1;
     if (d.ftzero > 127) return set_err(c, WASS_ERR_UNSUPPORTED, "DENSE_PREFILTER_CAP %d > 126", p->prefilter_cap);
