@@ -471,8 +471,8 @@ FRAME_FIELDS = ("n_gaps", "component_size", "found", "refine_ok", "ransac_inlier
 
 @pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
 def test_stage_by_stage_calls_while_a_frame_is_in_flight(gpu_ctx, oracle, shape):
-    """finish_frame_async for mesh A, the four calls on mesh B before A's record is read: A's result and bytes are those of A run
-    alone, B's results the references'.  Once: an ordering check."""
+    """finish_frame_async for mesh A, the four calls on mesh B and the encoder twice (with the plane, without) before A's record is
+    read: A's result and bytes are those of A run alone, B's results the references'.  Once: an ordering check."""
     import torch
     w, h = shape
     uv = M.record_samples(w, h)
@@ -483,6 +483,7 @@ def test_stage_by_stage_calls_while_a_frame_is_in_flight(gpu_ctx, oracle, shape)
     p_ref, n_ref, _ = oracle.refine_plane(vb, pb, **RP)
     crop_by = p_ref if n_ref >= 3 else np.array([0.0, 0.0, 1.0, -20.0])
     c_mask, c_kept = oracle.crop_plane(vb, pb, crop_by, 0.25)
+    enc_by = crop_by if n_ref >= 3 else TILTED             # (the stand-in plane of 1 x 1 is level: see TILTED)
 
     def frame(between):
         pin = torch.zeros(148 + 6 * w * h, dtype=torch.uint8).pin_memory()
@@ -498,10 +499,10 @@ def test_stage_by_stage_calls_while_a_frame_is_in_flight(gpu_ctx, oracle, shape)
         rs = b.ransac_plane(uv, 0.3)
         rf = _raw_refine(gpu_ctx, b)
         kept = b.crop_plane(crop_by, 0.25)
-        return zg, rs, rf, kept, b.download()[0]
+        return zg, rs, rf, kept, b.encode_xyzc(enc_by), b.encode_xyzc(None), b.download()[0]
 
     alone, alone_bytes, _ = frame(lambda: None)
-    fr, fr_bytes, (zg, rs, rf, kept, mask) = frame(four_calls)
+    fr, fr_bytes, (zg, rs, rf, kept, enc, enc_none, mask) = frame(four_calls)
     print(f"{w}x{h}: frame {[getattr(fr, k) for k in FRAME_FIELDS]} zgap {fr.zgap}; between: zgap {zg}, RANSAC {rs[0], rs[2]}, refine {rf[0], rf[3]}, kept {kept}")
     assert [getattr(fr, k) for k in FRAME_FIELDS] == [getattr(alone, k) for k in FRAME_FIELDS] and _same(fr.zgap, alone.zgap)
     np.testing.assert_array_equal(np.array(fr.ransac_plane[:]), np.array(alone.ransac_plane[:]))
@@ -515,6 +516,99 @@ def test_stage_by_stage_calls_while_a_frame_is_in_flight(gpu_ctx, oracle, shape)
         np.testing.assert_array_equal(rf[2], p_ref)
     assert kept == c_kept
     np.testing.assert_array_equal(mask, c_mask)
+    assert enc == oracle.encode_xyzc(c_mask, pb, enc_by) and enc_none == _identity_xyzc(c_mask, pb)
+
+
+# The encoder is a stage-by-stage call like the four above: it writes R|T and the crop switch, off, into the record and runs the
+# chain's last step (k_crop_limits_counts_dev, k_scan_blocks, k_frame_header, k_xyzc_pack_dev).
+# Planes for the encoder are tilted: RT_from_plane divides by a^2 + b^2, and a plane [0, 0, 1, d] makes its R a matrix of NaNs in
+# the reference as here, which neither keeps out of its limits the same way (reduce.h: the callers of order_key keep NaN out).
+TILTED = np.array([0.6, 0.0, 0.8, -16.0])
+FAR_PLANE = np.array([0.6, 0.0, 0.8, -1e6])                # about 1e6 away from every point of exact_sea: a crop by it keeps none
+
+
+def _identity_xyzc(valid, p3d):
+    """oracle.encode_xyzc without a plane (the C oracle takes one; RT_from_plane has no plane that gives the identity: a = b = 0 is 0 / 0).
+    With R = I and T = 0 the oracle's R p + T is p itself -- 1 x + 0 y + 0 z + 0 rounds nothing for finite points -- so its limits,
+    scales and truncating conversions are these fp64 expressions; 0 * inf (one point, or no extent on an axis) converts to 0."""
+    pts = p3d.reshape(-1, 3)[valid.ravel() != 0]
+    n = len(pts)
+    mn = pts.min(0) if n else np.full(3, np.finfo(np.float64).max)
+    mx = pts.max(0) if n else np.full(3, -np.finfo(np.float64).max)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        sc = 65535.0 / (mx - mn)
+        q = (pts - mn) * sc
+    q = np.where(np.isnan(q), 0.0, q).astype(np.uint16)
+    return np.uint32(n).tobytes() + sc.tobytes() + mn.tobytes() + np.eye(3).tobytes() + np.zeros(3).tobytes() + q.tobytes()
+
+
+def _encode_both(ctx, oracle, valid, p3d, plane, tag):
+    """the encoder with a plane and without on a fresh upload, against the references; the valid mask stays as uploaded"""
+    m = ctx.mesh_upload(valid, p3d)
+    got, got_none = m.encode_xyzc(plane), m.encode_xyzc(None)
+    print(f"{tag} {valid.shape[1]}x{valid.shape[0]}: {int(valid.sum())} valid, {len(got)} and {len(got_none)} bytes")
+    assert len(got) == len(got_none) == 148 + 6 * int(valid.sum())
+    assert got == oracle.encode_xyzc(valid, p3d, plane) and got_none == _identity_xyzc(valid, p3d)
+    np.testing.assert_array_equal(m.download()[0], valid)
+
+
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_the_encoder_first_on_a_fresh_context(oracle, shape):
+    """no record, no pinned stage: the encoder's own put creates both"""
+    valid, p3d = M.exact_sea(*shape)
+    with wass_amd.Context(0) as ctx:
+        _encode_both(ctx, oracle, valid, p3d, TILTED, "fresh")
+
+
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_the_encoder_after_a_fit_that_left_its_crop_switch_on(gpu_ctx, oracle, shape):
+    """fit_plane on exact_sea leaves refine_ok = 1 and its plane in the record (1 x 1: no refinement, refine_ok = 0).  The encoder
+    of another mesh with a plane far from its points must switch the crop off itself: a crop that ran would remove every point.
+    refine_plane and crop_plane after it write their own switches again."""
+    w, h = shape
+    _check_fit(gpu_ctx, oracle, *M.exact_sea(w, h), M.record_samples(w, h))
+    valid, p3d = M.exact_sea(w, h, seed=3)
+    _encode_both(gpu_ctx, oracle, valid, p3d, FAR_PLANE, "after a fit")
+    plane = _check_refine(gpu_ctx, oracle, valid, p3d)
+    _check_crop(gpu_ctx, oracle, valid, p3d, plane)
+
+
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_the_encoder_after_a_fit_that_found_no_plane(gpu_ctx, oracle, shape):
+    w, h = shape
+    _check_fit(gpu_ctx, oracle, *M.sparse_sea(w, h), M.record_samples(w, h))
+    valid, p3d = M.exact_sea(w, h, seed=3)
+    _encode_both(gpu_ctx, oracle, valid, p3d, TILTED, "after 'not found'")
+
+
+@pytest.mark.parametrize("shape", M.RECORD_SHAPES, ids=ids)
+def test_the_encoder_into_a_buffer_of_exactly_its_size(gpu_ctx, oracle, shape):
+    """encode_xyzc_to into pinned memory of exactly 148 + 6 n bytes, n < w h, between guard cells: it fits, one byte fewer is refused
+    before anything is downloaded, no guard cell changes, and the mesh still encodes afterwards"""
+    import torch
+    from guarded import GUARD, Guarded, host
+    valid, p3d = M.exact_sea(*shape)
+    valid.ravel()[0] = 0
+    p3d[valid == 0] = 0
+    plane = TILTED
+    need = 148 + 6 * int(valid.sum())
+    assert valid.sum() < valid.size
+    ref = oracle.encode_xyzc(valid, p3d, plane)
+    g = Guarded(False)
+    parent = torch.full((need + 64,), GUARD["u"], dtype=torch.uint8).pin_memory()
+    inside = np.zeros(need + 64, bool)
+    inside[32:-32] = True
+    g.kept.append((parent, host(parent).copy(), inside))
+    m = gpu_ctx.mesh_upload(valid, p3d)
+    with pytest.raises(wass_amd.WassError) as e:
+        m.encode_xyzc_to(plane, parent.data_ptr() + 32, need - 1)
+    print(f"{shape}: {need} bytes; one fewer: {e.value}")
+    assert e.value.code == WASS_ERR_INVALID_ARG and f"xyzC needs {need} bytes, buffer has {need - 1}" in str(e.value)
+    assert (host(parent) == GUARD["u"]).all()                          # refused before the download
+    assert m.encode_xyzc_to(plane, parent.data_ptr() + 32, need) == need
+    assert host(parent)[32:-32].tobytes() == ref
+    g.check("encode_xyzc_to")
+    assert m.encode_xyzc(plane) == ref
 
 
 def test_the_refusals_answer_as_before(gpu_ctx, oracle):

@@ -133,10 +133,7 @@ int wass_ctx_create(int device_id, wass_ctx** out)
     if (hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking) != hipSuccess) { wass_ctx_destroy(c); return WASS_ERR_DEVICE; }
     if (hipStreamCreateWithFlags(&c->tail, hipStreamNonBlocking) != hipSuccess) { wass_ctx_destroy(c); return WASS_ERR_DEVICE; }
     if (hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming) != hipSuccess) { wass_ctx_destroy(c); return WASS_ERR_DEVICE; }
-    if (hipEventCreateWithFlags(&c->ev_pack, hipEventDisableTiming) != hipSuccess) { wass_ctx_destroy(c); return WASS_ERR_DEVICE; }
-    for (auto& fs : c->fslot)
-        if (hipEventCreateWithFlags(&fs.ev_copy, hipEventDisableTiming | (getenv("WASS_SPIN_WAIT") ? 0 : hipEventBlockingSync)) != hipSuccess) { wass_ctx_destroy(c); return WASS_ERR_DEVICE; }
-    c->ev_copy = c->fslot[0].ev_copy;                      // "the most recently recorded download event": an alias of one of the two
+    if (!c->ft.init()) { wass_ctx_destroy(c); return WASS_ERR_DEVICE; }
     for (auto& set : c->evs)
         for (auto& e : set)
             if (hipEventCreate(&e) != hipSuccess) { wass_ctx_destroy(c); return WASS_ERR_DEVICE; }
@@ -171,18 +168,12 @@ void wass_ctx_destroy(wass_ctx* c)
     if (c->tail) { (void)hipStreamSynchronize(c->tail); (void)hipStreamDestroy(c->tail); }
     if (c->ev_post) (void)hipEventDestroy(c->ev_post);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
-    for (auto& fs : c->fslot) { if (fs.h_frame) (void)hipHostFree(fs.h_frame); if (fs.ev_copy) (void)hipEventDestroy(fs.ev_copy); }
-    if (c->ev_stage2) (void)hipEventDestroy(c->ev_stage2);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
     if (c->ev_producer) (void)hipEventDestroy(c->ev_producer);
     if (c->ev_dl) (void)hipEventDestroy(c->ev_dl);
     if (c->ev_dl_tail) (void)hipEventDestroy(c->ev_dl_tail);
-    for (auto& set : c->ev_tail_sets) for (auto& e : set) if (e) (void)hipEventDestroy(e);
-    if (c->ev_pack) (void)hipEventDestroy(c->ev_pack);
     for (auto& u : c->uploads) if (u.ev) (void)hipEventDestroy(u.ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;                                                // frees every Buf: the device is selected and no stream has work left
+    delete c;                                                // frees every Buf and the frame tail: the device is selected and no stream has work left
 }
 
 const char* wass_last_error(const wass_ctx* c) { return c ? c->err.c_str() : "null context"; }

@@ -11,6 +11,7 @@
 #include "../../include/wass_gpu.h"
 #include "reduce.h"
 #include "scratch.h"
+#include "mesh_tail.h"
 
 namespace wass {
 
@@ -122,36 +123,11 @@ struct wass_ctx {
     wass::Buf raw2;                // speckle filter: median-filtered padded disparity
     wass::Buf grid;                // wass_mesh_grid_idw: accumulators and maps of the surface grid (grid.hip)
     wass::Buf dct, dct_io;         // wass_grid_dct*: bases, state and partial slabs of the solve / host-pointer staging (grid_dct.hip)
-    wass::Buf counters;            // striped atomics of the mesh stages
-    wass::Buf tri_cnt;             // striped count of the points the last triangulation produced (read by the frame tail)
-    wass::Buf inl;                 // every n-th refinement inlier of the frame tail (plane_refinement_inliers.xyz)
-    wass::Buf dstate;              // device-resident scalar record + radix histogram (mesh.hip DevState)
-    wass::Buf scratch;             // mesh stages: gaps / labels / partial sums / packed output
-    wass::Buf xyzc;                // packed u16 triples of mesh_cam.xyzC (own buffer: downloaded asynchronously)
-    wass::Buf limits;              // striped min/max keys of the frame tail
-    // Up to TWO frames may be pending (round 5): a driver enqueues frame n's tail BEFORE it reads frame n-1's record, so that the tail
-    // stream never waits for the previous frame's downloads plus a host round trip (with one record per context that chain, not the
-    // SGM stage, set the C++ driver's frame period).  Everything a pending frame's record needs is per slot; slot = frame number & 1.
-    struct FrameSlot {
-        void* h_frame = nullptr;   // pinned: the device state record as downloaded
-        hipEvent_t ev_copy = nullptr;   // the frame's downloads have finished
-        int inl_every = 0;         // > 0: the frame also selected every n-th refinement inlier
-        bool inl_text = false;     // ... and formatted plane_refinement_inliers.xyz on the device
-        size_t inl_cap = 0;        // ... capacity (points) of the selection
-        unsigned long long sgm_call = 0;   // 1-based index of the SGM call whose disparity the frame was built from
-        int tail_set = 0;          // the timing-event set its tail was recorded into
-    } fslot[2];
-    unsigned long long nframe_enq = 0, nframe_col = 0;   // frame tails enqueued / records read
-    int ds_slot = 0;               // which of the two device state records (and inlier buffers) the stage helpers use
-    wass::Buf inl2;                // the odd frames' selected inliers (the even frames' live in `inl`)
-    void* h_frame = nullptr;       // (alias of the last collected slot's record)
-    bool frame_pending = false;
-    void* h_stage = nullptr;       // pinned source images of the frame tail's small H2D copies (mesh.hip host_stage)
-    hipEvent_t ev_stage = nullptr, ev_stage2 = nullptr;   // the RANSAC triplets' staging areas (two, alternated) have been copied to the device
+    wass::Buf scratch;             // mesh stages: labels / candidates / partial sums / block counts (mesh_layout.h), one phase after the other
+    wass::FrameTail ft;            // the frame tail: records, events, pinned blocks and buffers of the chain behind the SGM call (mesh_tail.h)
     hipEvent_t ev_producer = nullptr; // wass_ctx_wait_for_stream
     hipEvent_t ev_dl = nullptr;        // wass_download_async: orders the copy stream after the SGM stream
     hipEvent_t ev_dl_tail = nullptr;   // ... and after the tail stream
-    bool stage_uv_busy = false;
     hipStream_t copy = nullptr;    // D2H of the xyzC payload
     // Everything after the SGM call (disparity clean-up, triangulation, mesh stages: post.hip, mesh.hip) is enqueued on
     // ts(): the main stream, or -- with tail overlap on -- a second stream that waits for the last SGM call, so that
@@ -160,16 +136,6 @@ struct wass_ctx {
     hipEvent_t ev_post = nullptr;  // the clean-up on the tail stream has read the disparity of the last SGM call
     bool tail_overlap = false;
     hipStream_t ts() const { return tail_overlap ? tail : stream; }
-    hipEvent_t ev_pack = nullptr, ev_copy = nullptr;
-    // stage times of the frame tail (wass_frame_result.stage_ms): [0] before k_triangulate, [1] entry of the mesh tail, [2] z-gap
-    // percentile found, [3] biggest component kept, [4] RANSAC plane picked, [5] file image packed.  Created on first use.
-    // Two sets, alternated by wass_triangulate[_dev]: a pipelined driver enqueues frame n+1's triangulation BEFORE it reads frame
-    // n's record, so one set would be re-recorded under the reader (every frame but the last of a sequence had all-zero rows).
-    hipEvent_t ev_tail_sets[4][6] = {};    // (four: with two frames pending a record is read after two more triangulations)
-    hipEvent_t* ev_tail = ev_tail_sets[0];  // set of the last triangulation
-    int tail_set = 0;
-    bool tail_timed[4] = {};
-    wass::Buf ccmask;              // valid mask after the outlier removal, kept for graph_components.jpg when asked for
     // the debug pictures rendered and JPEG-coded on the device (jpeg.hip): coefficient / offset / bit-stream scratch, Huffman tables,
     // result words; four tickets in flight (event + header sizes + pinned result words per ticket)
     wass::Buf jpeg_scratch, jpeg_huff, jpeg_out, jpeg_info, jpeg_part;

@@ -512,7 +512,7 @@ int wass_debug_pictures_async(wass_ctx* c, const wass_mesh* m, const wass_debug_
     const int W0 = d->W0, H0 = d->H0, cw = d->roi_r[2], ch = d->roi_r[3];
     if (W0 <= 0 || H0 <= 0 || cw <= 0 || ch <= 0 || d->roi_l[2] != cw || d->roi_l[3] != ch || m->w != cw || m->h != ch || !m->codes)
         return set_err(c, WASS_ERR_INVALID_ARG, "debug pictures: the two ROIs and the mesh must have one size");
-    if (!d->d_left_crop || !d->d_right_crop || !d->d_disp16 || !d->d_dispf || !c->ccmask.p || c->ccmask.cap < (size_t)cw * ch)
+    if (!d->d_left_crop || !d->d_right_crop || !d->d_disp16 || !d->d_dispf || !c->ft.ccmask.p || c->ft.ccmask.cap < (size_t)cw * ch)
         return set_err(c, WASS_ERR_INVALID_ARG, "debug pictures: a map is missing (the frame tail must have been asked for the component mask)");
     uint8_t* dv = device_view(h_dst);
     if (!dv) return set_err(c, WASS_ERR_INVALID_ARG, "debug pictures: the destination must be pinned host memory");
@@ -570,7 +570,7 @@ int wass_debug_pictures_async(wass_ctx* c, const wass_mesh* m, const wass_debug_
                 break;
             }
             default: {
-                SrcComponents s{ m->codes, (const uint8_t*)c->ccmask.p, cw, ch };
+                SrcComponents s{ m->codes, (const uint8_t*)c->ft.ccmask.p, cw, ch };
                 rc = encode_picture(c, st, s, pic[k].w, pic[k].h, 3, q, dst, cap, inf);
                 break;
             }

@@ -11,10 +11,10 @@
 #include "fmt_g6.h"
 
 #include <math.h>
+#include <algorithm>
 #include <stdlib.h>
 #include <mutex>
 #include <new>
-#include <vector>
 
 namespace wass {
 
@@ -38,9 +38,7 @@ __device__ __forceinline__ void tmulv(const double* M, const double* v, double* 
     o[2] = M[2] * v[0] + M[5] * v[1] + M[8] * v[2];
 }
 
-// Counters are striped over NSLOT addresses (summed on the host): tens of thousands of waves hitting one
-// address serialise at ~12 ns per atomic, which would dominate these otherwise trivial kernels.
-constexpr int NSLOT = 64;
+// the stripe (of NSLOT, mesh_layout.h) that this wave's counter updates go to
 __device__ __forceinline__ int slot_of_block() { return (int)((blockIdx.x * 7u + blockIdx.y * 13u + (threadIdx.x >> 6)) & (NSLOT - 1)); }
 
 // StereoMatchEnv::unrectify (wass_stereo.cpp:299-324)
@@ -329,38 +327,10 @@ __global__ void __launch_bounds__(256) k_ccl_keep(uint8_t* __restrict__ valid, i
 }
 
 // ------------------------------------------------------------------ device-resident scalars
-// Decisions that only need a few numbers (the digit of a radix-select pass, the best RANSAC candidate, a 3x3
-// eigenvector) are taken by single-workgroup kernels writing into this record, so that a whole stage chain runs
-// without host round trips; the host reads the record once at the end.
-struct DevState {
-    unsigned long long sel_k, sel_prefix, sel_total;      // radix select: remaining rank, key prefix, number of keys
-    int sel_hi_shift, sel_fail;
-    double zgap;
-    unsigned long long ccl_best;                          // (size << 32) | ~mincm of the winning component
-    int ransac_found, zero;                               // zero: the crop switch of a refinement without a crop (wass_mesh_refine_plane)
-    unsigned long long ransac_best;
-    double ransac_plane[4];
-    double wsum, centroid[3], ninl;
-    double plane[4];                                      // refined plane
-    int refine_ok, pad1;
-    // host-sync-free frame tail (wass_mesh_finish_frame_async): everything the xyzC encoder needs, decided on the device
-    double rtR[9], rtT[3], rtRinv[9], rtTinv[3];
-    double mn[3], sc[3];
-    unsigned int npts, have_plane;
-    unsigned long long kept1, kept2;
-    unsigned long long ntri;                              // valid points the triangulation produced
-    unsigned int ninl_sel, inl_text_bad;                  // refinement inliers seen by the selection for plane_refinement_inliers.xyz;
-    unsigned long long inl_text_bytes;                    // ... bytes of that file's text when the device formatted it, numbers it could not format
-};
-
 // ------------------------------------------------------------------ z-gap percentile (PovMesh.cpp:888-926)
 // |z - z(neighbour k in the row above)|, k = -1, 0, +1, computed on the fly (no gap array): histogram of one 11-bit digit of the fp64 bit patterns that match the
 // prefix found so far.  Blocks own a 256-column strip and walk rows (no index divisions); their totals go to one of
 // GAP_HIST_COPIES copies of the global histogram (same-address atomics serialise), which k_radix_pick adds up.
-constexpr int GAP_HIST_COPIES = 4;
-// 5 x 11 + 9 bits = 64.  (13-bit digits, five passes: measured SLOWER -- 42 + 23 us per pass against 26 + 11: the 32 KB
-// histogram per workgroup costs occupancy and the pick kernel scans four times the bins.)
-constexpr int GAP_BITS = 11, GAP_BINS = 1 << GAP_BITS, GAP_PASSES = 6;
 __global__ void __launch_bounds__(256) k_gap_hist(const uint8_t* __restrict__ valid, const double* __restrict__ Z, int w, int h,
                                                   int shift, unsigned int mask, const DevState* __restrict__ ds,
                                                   unsigned int* __restrict__ hist)
@@ -441,8 +411,6 @@ __global__ void __launch_bounds__(256) k_radix_pick(unsigned int* __restrict__ h
 }
 
 // ------------------------------------------------------------------ RANSAC (PovMesh.cpp:665-777)
-struct PlaneCand { double n[3]; double d; int ok; int pad; };
-
 __global__ void k_ransac_planes(const uint8_t* __restrict__ valid, const double* __restrict__ X, const double* __restrict__ Y,
                                 const double* __restrict__ Z, int w, const int32_t* __restrict__ uv, int rounds,
                                 PlaneCand* __restrict__ cand, unsigned long long* __restrict__ counts,
@@ -760,7 +728,6 @@ __global__ void __launch_bounds__(256) k_inlier_pack(const uint8_t* __restrict__
 // lengths per block of 256 points -> k_scan_blocks -> the lines written at their offsets.  A number outside the formatter's
 // domain (inf, nan, |v| >= 1e6 or < 1e-22: never a triangulated coordinate) is counted in *bad and the host formats the file
 // from the doubles instead, as before.
-constexpr int INL_LINE_MAX = 40;
 // pass 1: a block formats 256 lines into LDS (a thread's line is a string of single bytes: in HBM that is 40 partial cache-line
 // writes per thread, 64 different lines per instruction), packs them back to back -- still in LDS -- and writes the packed chunk to
 // the block's staging area as dwords; blockbytes[b] = its length.  pass 2 (after the scan): the chunks copied to their final
@@ -862,7 +829,6 @@ __device__ static void smallest_eigvec3(const double Ain[9], double vout[3])
     vout[0] = V[0][m] / nn; vout[1] = V[1][m] / nn; vout[2] = V[2][m] / nn;
 }
 
-
 // Sum of per-block partials in a fixed two-level order (64 strided sub-sums, then those in lane order)
 template <int NV>
 __device__ static void sum_partials_lane(const double* partial, int nb, int lane, double (&out)[NV])
@@ -933,53 +899,6 @@ __global__ void k_refine_finish(const double* __restrict__ partial, int nb, DevS
 // ------------------------------------------------------------------ xyzC (PovMesh.cpp:377-460)
 struct RTDev { double R[9], T[3]; };
 
-// min/max of R*p+T per axis (exact, order independent) + number of valid points per block
-__global__ void __launch_bounds__(256) k_block_counts(const uint8_t* __restrict__ valid, size_t n,
-                                                      unsigned int* __restrict__ blockcnt)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = __syncthreads_count(i < n && valid[i]);
-    if (threadIdx.x == 0) blockcnt[blockIdx.x] = (unsigned)c;
-}
-__device__ __forceinline__ void xyzc_limits_body(const uint8_t* __restrict__ valid, const double* __restrict__ X,
-                                                 const double* __restrict__ Y, const double* __restrict__ Z, size_t n,
-                                                 const RTDev& rt, unsigned long long* __restrict__ lim /* [NSLOT][6] keys */)
-{
-    unsigned long long mn[3] = { ~0ull, ~0ull, ~0ull }, mx[3] = { 0, 0, 0 };
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        if (!valid[i]) continue;
-        const double p[3] = { X[i], Y[i], Z[i] };
-        double t[3];
-        mulv(rt.R, p, t);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const unsigned long long key = order_key(t[k] + rt.T[k]);
-            mn[k] = key < mn[k] ? key : mn[k];
-            mx[k] = key > mx[k] ? key : mx[k];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long a = __shfl_down(mn[k], o), b = __shfl_down(mx[k], o);
-            mn[k] = a < mn[k] ? a : mn[k];
-            mx[k] = b > mx[k] ? b : mx[k];
-        }
-    if ((threadIdx.x & 63) == 0) {
-        unsigned long long* l = lim + (size_t)slot_of_block() * 6;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (mn[k] != ~0ull) atomicMin(&l[k], mn[k]);
-            if (mx[k] != 0) atomicMax(&l[3 + k], mx[k]);
-        }
-    }
-}
-__global__ void __launch_bounds__(256) k_xyzc_limits(const uint8_t* __restrict__ valid, const double* __restrict__ X,
-                                                     const double* __restrict__ Y, const double* __restrict__ Z, size_t n,
-                                                     RTDev rt, unsigned long long* __restrict__ lim)
-{
-    xyzc_limits_body(valid, X, Y, Z, n, rt, lim);
-}
 // exclusive scan of the per-block counts (single block; nblocks <= ~25k at full size)
 __global__ void __launch_bounds__(1024) k_scan_blocks(unsigned int* __restrict__ cnt, int nb, unsigned int* __restrict__ total)
 {
@@ -1033,15 +952,6 @@ __device__ __forceinline__ void xyzc_pack_body(const uint8_t* __restrict__ valid
         out[(size_t)off * 3 + 2] = (uint16_t)((t[2] - mnz) * sz);
     }
 }
-__global__ void __launch_bounds__(256) k_xyzc_pack(const uint8_t* __restrict__ valid, const double* __restrict__ X,
-                                                   const double* __restrict__ Y, const double* __restrict__ Z, size_t n,
-                                                   RTDev rt, double mnx, double mny, double mnz, double sx, double sy,
-                                                   double sz, const unsigned int* __restrict__ blockoff,
-                                                   uint16_t* __restrict__ out)
-{
-    xyzc_pack_body(valid, X, Y, Z, n, rt, mnx, mny, mnz, sx, sy, sz, blockoff, out);
-}
-
 __global__ void __launch_bounds__(256) k_interleave(const double* __restrict__ X, const double* __restrict__ Y,
                                                     const double* __restrict__ Z, size_t n, double* __restrict__ out)
 {
@@ -1116,7 +1026,7 @@ static int mesh_alloc(wass_ctx* c, int w, int h, wass_mesh** out)
     return WASS_OK;
 }
 
-static inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
+static inline unsigned nblk(size_t n) { return (unsigned)nblocks256(n); }
 
 // refine_plane's window and limits (PovMesh.cpp:585-588)
 static RefineDev refine_dev(const wass_refine_params* rp, const wass_mesh* m)
@@ -1131,15 +1041,11 @@ static RefineDev refine_dev(const wass_refine_params* rp, const wass_mesh* m)
     return rd;
 }
 
+// What the phases of one entry point need of the scratch buffer, ensured ONCE before anything is enqueued; every phase then
+// carves its pieces from the start of the buffer (mesh_layout.h says which pieces are dead by when).
+static int scratch_for(wass_ctx* c, std::initializer_list<size_t> phases) { return ensure(c, c->scratch, std::max(phases)); }
+template <class Lay, class... A> static Lay scratch_carve(wass_ctx* c, A... args) { return carved<Lay>(c->scratch.p, args...); }
 // striped device counters (NSLOT u64) -> host sum
-static int counters_reset(wass_ctx* c, unsigned long long** cnt)
-{
-    int rc = ensure(c, c->counters, (size_t)NSLOT * 6 * 8);
-    if (rc) return rc;
-    *cnt = (unsigned long long*)c->counters.p;
-    WASS_HIP(c, hipMemsetAsync(*cnt, 0, (size_t)NSLOT * 8, c->ts()));
-    return WASS_OK;
-}
 static int counters_sum(wass_ctx* c, const unsigned long long* cnt, unsigned long long* out)
 {
     unsigned long long h[NSLOT];
@@ -1207,18 +1113,17 @@ int wass_triangulate_dev(wass_ctx* c, const float* d_disp, int W, int H, const i
     // counted into a buffer of its own: the frame tail (wass_mesh_finish_frame_async) reports it, long after the shared
     // counters have been reused by the plane stages
     unsigned long long* cnt = nullptr;
-    if ((rc = ensure(c, c->tri_cnt, (size_t)NSLOT * 8))) { wass_mesh_destroy(m); return rc; }
-    cnt = (unsigned long long*)c->tri_cnt.p;
+    FrameTail& ft = c->ft;
+    if ((rc = ensure(c, ft.tri_cnt, (size_t)NSLOT * 8))) { wass_mesh_destroy(m); return rc; }
+    cnt = (unsigned long long*)ft.tri_cnt.p;
     if (hipMemsetAsync(cnt, 0, (size_t)NSLOT * 8, c->ts()) != hipSuccess) { wass_mesh_destroy(m); return set_err(c, WASS_ERR_DEVICE, "memset failed"); }
     dim3 grid((m->w + 255) / 256, std::min(m->h, 512));
-    if (!c->ev_tail_sets[0][0])
-        for (auto& set : c->ev_tail_sets)
-            for (auto& e : set)
-                if (hipEventCreate(&e) != hipSuccess) { e = nullptr; wass_mesh_destroy(m); return set_err(c, WASS_ERR_DEVICE, "hipEventCreate failed"); }
-    c->tail_set = (c->tail_set + 1) & 3;         // a frame's set stays readable for three more triangulations (two frames may be pending)
-    c->ev_tail = c->ev_tail_sets[c->tail_set];
-    (void)hipEventRecord(c->ev_tail[0], c->ts());
-    c->tail_timed[c->tail_set] = false;
+    for (auto& set : ft.ev_sets)
+        for (auto& e : set)
+            if (!e.create(hipEventDefault)) { wass_mesh_destroy(m); return set_err(c, WASS_ERR_DEVICE, "hipEventCreate failed"); }
+    ft.tail_set = (ft.tail_set + 1) % 4;         // a frame's set stays readable for three more triangulations (two frames may be pending)
+    (void)hipEventRecord(ft.ev()[0], c->ts());
+    ft.timed[ft.tail_set] = false;
     hipLaunchKernelGGL(k_triangulate, grid, dim3(256), 0, c->ts(), d_disp, W, H, roi_l[0], roi_r[0], roi_r[1], m->w, m->h,
                        gd, d_right_img, img_w, img_h, d_lmask, d_rmask, tp->min_angle_deg, tp->bbox[0], tp->bbox[1],
                        tp->bbox[2], tp->bbox[3], tp->cam_distance, m->valid, m->x, m->y, m->z, m->gray, m->codes, cnt);
@@ -1323,8 +1228,8 @@ __global__ void k_frame_rt(DevState* __restrict__ ds)
     }
 }
 // frame tail, step 2 -- three passes over the points in one: crop_plane by the refined plane (k_crop_plane_dev), the
-// limits of the transformed survivors (k_xyzc_limits_dev) and the per-block survivor counts of the compaction
-// (k_block_counts).  Block b owns points [256 b, 256 b + 256), as the pack kernel does.
+// limits of the transformed survivors and the per-block survivor counts of the compaction.  Block b owns points
+// [256 b, 256 b + 256), as the pack kernel does.  With ds->refine_ok == 0 nothing is cropped (the xyzC encoder).
 constexpr int CLC_CHUNKS = 16;
 __global__ void __launch_bounds__(256) k_crop_limits_counts_dev(uint8_t* __restrict__ valid, const double* __restrict__ X,
                                                                 const double* __restrict__ Y, const double* __restrict__ Z, size_t n,
@@ -1441,14 +1346,35 @@ __global__ void __launch_bounds__(256) k_xyzc_pack_dev(const uint8_t* __restrict
     xyzc_pack_body(valid, X, Y, Z, n, rt, ds->mn[0], ds->mn[1], ds->mn[2], ds->sc[0], ds->sc[1], ds->sc[2], blockoff, out);
 }
 
-constexpr size_t DSTATE_HIST_OFF = (sizeof(DevState) + 255) & ~(size_t)255;
-constexpr size_t DSTATE_STRIDE = (DSTATE_HIST_OFF + (size_t)GAP_HIST_COPIES * GAP_BINS * 4 + 255) & ~(size_t)255;
-// two records (+ histograms), alternated by the frame tail (wass_ctx::ds_slot): frame n's is downloaded while frame n+1's is being built
+// Pinned, context-owned source images of the small host-to-device copies of the sync-free frame tail (StageLay).  An
+// asynchronous copy from pageable or stack memory is only safe if the runtime happens to stage it before returning; these
+// copies are enqueued and never waited for, so their sources must outlive the call.
+static int host_stage(wass_ctx* c)
+{
+    FrameTail& ft = c->ft;
+    if (!ft.h_stage.p) {
+        if (!ft.h_stage.alloc(lay_bytes<StageLay>())) return set_err(c, WASS_ERR_NO_MEMORY, "hipHostMalloc failed");
+        ft.stage = carved<StageLay>(ft.h_stage.p);
+        memset(ft.stage.init, 0, sizeof(DevState));
+        ft.stage.init->sel_hi_shift = 64;
+        limits_init(ft.stage.lim_init);
+        for (int k = 0; k < 2; ++k) {
+            ft.slots[k].h_uv = ft.stage.uv[k];
+            if (!ft.slots[k].ev_uv.create(hipEventDisableTiming)) return set_err(c, WASS_ERR_DEVICE, "hipEventCreate failed");
+        }
+    }
+    return WASS_OK;
+}
+
+// What every mesh stage needs before it enqueues, called first by every entry: the current slot's record with its histograms (two,
+// alternated by the frame tail -- frame n's is downloaded while frame n+1's is being built), the counters and the pinned stage.
 static int dstate(wass_ctx* c, DevState** ds)
 {
-    int rc = ensure(c, c->dstate, 2 * DSTATE_STRIDE);
-    if (rc) return rc;
-    *ds = (DevState*)((char*)c->dstate.p + (size_t)(c->ds_slot & 1) * DSTATE_STRIDE);
+    FrameTail& ft = c->ft;
+    FrameTail::Slot& s = ft.cur();
+    int rc = carve_buf(c, s.rec_buf, [&](Carve& a) { s.rec.carve(a); });
+    if (rc || (rc = carve_buf(c, ft.counters, [&](Carve& a) { ft.cn.carve(a); })) || (rc = host_stage(c))) return rc;
+    *ds = s.rec.ds;
     return WASS_OK;
 }
 
@@ -1457,11 +1383,7 @@ static int enqueue_ccl(wass_ctx* c, wass_mesh* m, DevState* ds)
 {
     const size_t n = m->n();
     if (n > 0x7FFFFFFFull) return set_err(c, WASS_ERR_UNSUPPORTED, "mesh too large");
-    int rc = ensure(c, c->scratch, n * 12);
-    if (rc) return rc;
-    int* parent = (int*)c->scratch.p;
-    unsigned int* size = (unsigned int*)(parent + n);
-    unsigned int* mincm = size + n;
+    const auto [parent, size, mincm] = scratch_carve<CclLay>(c, n);
     unsigned long long* best = &ds->ccl_best;
     const dim3 blk(256), g1(nblk(n));
     hipLaunchKernelGGL(k_ccl_init, g1, blk, 0, c->ts(), m->valid, m->z, m->w, (int)n, (const double*)&ds->zgap, parent, size, mincm, best);
@@ -1479,62 +1401,9 @@ static int enqueue_ccl(wass_ctx* c, wass_mesh* m, DevState* ds)
     return WASS_OK;
 }
 
-int wass_mesh_keep_biggest_component(wass_ctx* c, wass_mesh* m, double zgap, uint64_t* size_out)
-{
-    if (!c || !m) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
-    WASS_HIP(c, hipSetDevice(c->device));
-    DevState* ds = nullptr;
-    int rc = dstate(c, &ds);
-    if (rc) return rc;
-    WASS_HIP(c, hipMemcpyAsync(&ds->zgap, &zgap, 8, hipMemcpyHostToDevice, c->ts()));
-    WASS_HIP(c, hipStreamSynchronize(c->ts()));       // zgap lives on the caller's stack
-    if ((rc = enqueue_ccl(c, m, ds))) return rc;
-    if (size_out) {
-        unsigned long long hb = 0;
-        WASS_HIP(c, hipMemcpyAsync(&hb, &ds->ccl_best, 8, hipMemcpyDeviceToHost, c->ts()));
-        WASS_HIP(c, hipStreamSynchronize(c->ts()));
-        *size_out = hb >> 32;
-    }
-    return WASS_OK;
-}
-
-// Pinned, context-owned source images of the small host-to-device copies of the sync-free frame tail.  An asynchronous
-// copy from pageable or stack memory is only safe if the runtime happens to stage it before returning; these copies
-// are enqueued and never waited for, so their sources must outlive the call:
-// [DevState init | parameters of a stage-by-stage call | limits init | uv samples].
-constexpr size_t STAGE_PARAM_OFF = 2048;
-constexpr size_t STAGE_UV_OFF = 4096 + NSLOT * 6 * 8;
-constexpr int RANSAC_MAX_ROUNDS = 1800;                       // PLANE_RANSAC_ROUNDS: k_ransac_score keeps 36 bytes of LDS per round (64 KB)
-static_assert((size_t)RANSAC_MAX_ROUNDS * (32 + 4) <= 64 * 1024, "k_ransac_score: a plane and a counter per round in LDS");
-constexpr size_t STAGE_UV_BYTES = (size_t)RANSAC_MAX_ROUNDS * 24;
-constexpr size_t STAGE_BYTES = STAGE_UV_OFF + 2 * STAGE_UV_BYTES;   // two areas, alternated: the host never waits for the previous frame's copy
-static int host_stage(wass_ctx* c, unsigned char** out)
-{
-    static_assert(sizeof(DevState) <= STAGE_PARAM_OFF, "DevState init image");
-    if (!c->h_stage) {
-        if (hipHostMalloc((void**)&c->h_stage, STAGE_BYTES, hipHostMallocDefault) != hipSuccess)
-            return set_err(c, WASS_ERR_NO_MEMORY, "hipHostMalloc failed");
-        unsigned char* p = (unsigned char*)c->h_stage;
-        DevState init;
-        memset(&init, 0, sizeof init);
-        init.sel_hi_shift = 64;
-        memcpy(p, &init, sizeof init);
-        unsigned long long* lim = (unsigned long long*)(p + 4096);
-        for (int i = 0; i < NSLOT; ++i) for (int k = 0; k < 6; ++k) lim[i * 6 + k] = k < 3 ? ~0ull : 0ull;
-        if (hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_stage2, hipEventDisableTiming) != hipSuccess)
-            return set_err(c, WASS_ERR_DEVICE, "hipEventCreate failed");
-    }
-    *out = (unsigned char*)c->h_stage;
-    return WASS_OK;
-}
-
 // Before anything overwrites the current record: the download that read THIS record (two frames ago in a sequence; the
 // frame still in flight when a stage-by-stage call comes in between) must have finished.
-static int record_wait(wass_ctx* c)
-{
-    WASS_HIP(c, hipStreamWaitEvent(c->ts(), c->fslot[c->ds_slot & 1].ev_copy, 0));
-    return WASS_OK;
-}
+static int record_wait(wass_ctx* c) { WASS_HIP(c, hipStreamWaitEvent(c->ts(), c->ft.cur().ev_copy, 0)); return WASS_OK; }
 // the record as the stages enqueued so far leave it, on the host; returns when they have run
 static int record_read(wass_ctx* c, const DevState* ds, DevState* h)
 {
@@ -1548,22 +1417,34 @@ static int record_read(wass_ctx* c, const DevState* ds, DevState* h)
 // returns, because every such call ends in a synchronise.
 static int record_put(wass_ctx* c, void* field, const void* src, size_t bytes)
 {
-    unsigned char* stage = nullptr;
-    int rc = host_stage(c, &stage);
-    if (rc || (rc = record_wait(c))) return rc;
-    memcpy(stage + STAGE_PARAM_OFF, src, bytes);
-    WASS_HIP(c, hipMemcpyAsync(field, stage + STAGE_PARAM_OFF, bytes, hipMemcpyHostToDevice, c->ts()));
+    int rc = record_wait(c);
+    if (rc) return rc;
+    memcpy(c->ft.stage.param, src, bytes);                  // (callers assert bytes <= STAGE_PARAM_BYTES)
+    WASS_HIP(c, hipMemcpyAsync(field, c->ft.stage.param, bytes, hipMemcpyHostToDevice, c->ts()));
+    return WASS_OK;
+}
+
+int wass_mesh_keep_biggest_component(wass_ctx* c, wass_mesh* m, double zgap, uint64_t* size_out)
+{
+    if (!c || !m) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    WASS_HIP(c, hipSetDevice(c->device));
+    DevState* ds = nullptr;
+    int rc = dstate(c, &ds);
+    if (rc || (rc = scratch_for(c, { lay_bytes<CclLay>(m->n()) })) || (rc = record_put(c, &ds->zgap, &zgap, 8)) || (rc = enqueue_ccl(c, m, ds))) return rc;
+    unsigned long long hb = 0;
+    WASS_HIP(c, hipMemcpyAsync(&hb, &ds->ccl_best, 8, hipMemcpyDeviceToHost, c->ts()));
+    WASS_HIP(c, hipStreamSynchronize(c->ts()));       // (also without size_out: the pinned stage is free again when the call returns)
+    if (size_out) *size_out = hb >> 32;
     return WASS_OK;
 }
 
 // compute_zgap_percentile: the record reset to its initial image, then the radix select; leaves zgap, sel_total and sel_fail in it
 static int enqueue_percentile(wass_ctx* c, wass_mesh* m, double percentile, DevState* ds)
 {
-    unsigned int* hist = (unsigned int*)((char*)ds + DSTATE_HIST_OFF);      // 256-byte aligned: one fill kernel, not three
-    unsigned char* stage = nullptr;
-    int rc = host_stage(c, &stage);
-    if (rc || (rc = record_wait(c))) return rc;
-    WASS_HIP(c, hipMemcpyAsync(ds, stage, sizeof(DevState), hipMemcpyHostToDevice, c->ts()));
+    unsigned int* hist = c->ft.cur().rec.hist;
+    int rc = record_wait(c);
+    if (rc) return rc;
+    WASS_HIP(c, hipMemcpyAsync(ds, c->ft.stage.init, sizeof(DevState), hipMemcpyHostToDevice, c->ts()));
     WASS_HIP(c, hipMemsetAsync(hist, 0, (size_t)GAP_HIST_COPIES * GAP_BINS * 4, c->ts()));
     for (int pass = 0; pass < GAP_PASSES; ++pass) {
         const int shift = pass < GAP_PASSES - 1 ? 64 - GAP_BITS * (pass + 1) : 0;       // 53, 42, 31, 20, 9, 0 (last digit: 9 bits)
@@ -1579,8 +1460,7 @@ int wass_mesh_zgap_percentile(wass_ctx* c, wass_mesh* m, double percentile, doub
 {
     if (!c || !m || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
-    DevState* ds = nullptr;
-    DevState h;
+    DevState *ds = nullptr, h;
     int rc = dstate(c, &ds);
     if (rc || (rc = enqueue_percentile(c, m, percentile, ds)) || (rc = record_read(c, ds, &h))) return rc;
     if (h.sel_fail == 2) return set_err(c, WASS_ERR_DEVICE, "radix select lost its rank (internal error)");
@@ -1589,15 +1469,13 @@ int wass_mesh_zgap_percentile(wass_ctx* c, wass_mesh* m, double percentile, doub
     return WASS_OK;
 }
 
-static int enqueue_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile, DevState** dsp)
+static int enqueue_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile, DevState* ds)
 {
-    DevState* ds = nullptr;
-    int rc = dstate(c, &ds);
-    if (rc || (rc = enqueue_percentile(c, m, percentile, ds))) return rc;
-    if (c->ev_tail[2]) (void)hipEventRecord(c->ev_tail[2], c->ts());
+    int rc = enqueue_percentile(c, m, percentile, ds);
+    if (rc) return rc;
+    if (c->ft.ev()[2]) (void)hipEventRecord(c->ft.ev()[2], c->ts());
     if ((rc = enqueue_ccl(c, m, ds))) return rc;
-    if (c->ev_tail[3]) (void)hipEventRecord(c->ev_tail[3], c->ts());
-    *dsp = ds;
+    if (c->ft.ev()[3]) (void)hipEventRecord(c->ft.ev()[3], c->ts());
     return WASS_OK;
 }
 
@@ -1607,10 +1485,9 @@ int wass_mesh_remove_outliers(wass_ctx* c, wass_mesh* m, double percentile, doub
 {
     if (!c || !m) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
-    DevState* ds = nullptr;
-    DevState h;
-    int rc = enqueue_remove_outliers(c, m, percentile, &ds);
-    if (rc || (rc = record_read(c, ds, &h))) return rc;
+    DevState *ds = nullptr, h;
+    int rc = dstate(c, &ds);
+    if (rc || (rc = scratch_for(c, { lay_bytes<CclLay>(m->n()) })) || (rc = enqueue_remove_outliers(c, m, percentile, ds)) || (rc = record_read(c, ds, &h))) return rc;
     if (h.sel_fail == 2) return set_err(c, WASS_ERR_DEVICE, "radix select lost its rank (internal error)");
     if (zgap_out) *zgap_out = h.zgap;
     if (n_gaps) *n_gaps = h.sel_total;
@@ -1701,18 +1578,6 @@ int wass_ransac_sample_seeded(uint32_t seed, int width, int height, int rounds, 
 // ---- the plane stages.  Each is enqueued by ONE helper, which the stage-by-stage entry points call with parameters they have
 // written into the record themselves and the chain (enqueue_fit_plane) calls with what the stage before left there.
 
-// [candidates | inlier counts | samples] [per-block partial sums of the refinement] in the scratch buffer
-constexpr int REFINE_BLOCKS = 1024;
-static int plane_scratch(wass_ctx* c, int rounds, PlaneCand** cand, double** part)
-{
-    const size_t cand_bytes = (((size_t)rounds * (24 + sizeof(PlaneCand) + 8) + 256) + 255) & ~(size_t)255;
-    int rc = ensure(c, c->scratch, cand_bytes + (size_t)REFINE_BLOCKS * 6 * 8);
-    if (rc) return rc;
-    *cand = (PlaneCand*)c->scratch.p;
-    *part = (double*)((char*)c->scratch.p + cand_bytes);
-    return WASS_OK;
-}
-
 // what ransac_find_plane accepts; checked before anything is enqueued
 static int check_ransac_args(wass_ctx* c, const wass_mesh* m, const int32_t* uv, int rounds)
 {
@@ -1726,26 +1591,19 @@ static int check_ransac_args(wass_ctx* c, const wass_mesh* m, const int32_t* uv,
 
 // ransac_find_plane: a candidate per sample triple, every candidate scored in one pass over the points, the choice ->
 // ds->ransac_plane, ransac_best, ransac_found.  k_ransac_planes also clears the nzero counters at `zero`.
-static int enqueue_ransac(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds, double thr, PlaneCand* cand,
+static int enqueue_ransac(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds, double thr, const PlaneLay& pl,
                           unsigned long long* zero, int nzero, DevState* ds)
 {
-    unsigned long long* counts = (unsigned long long*)(cand + rounds);
-    int32_t* duv = (int32_t*)(counts + rounds);
+    const auto [cand, counts, duv, part] = pl;
     hipStream_t s = c->ts();
-    // the caller's sample array may be pageable and short-lived: go through the pinned stage (the previous frame's
-    // copy out of it was enqueued a whole frame ago; wait for it before overwriting)
-    unsigned char* stage = nullptr;
-    int rc = host_stage(c, &stage);
-    if (rc) return rc;
-    // (two areas, alternated with the frame slot: the copy out of THIS one was enqueued two frames ago)
-    const int ua = c->ds_slot & 1;
-    hipEvent_t evs = ua ? c->ev_stage2 : c->ev_stage;
-    unsigned char* area = stage + STAGE_UV_OFF + (size_t)ua * STAGE_UV_BYTES;
-    if (c->stage_uv_busy) WASS_HIP(c, hipEventSynchronize(evs));
-    memcpy(area, uv, (size_t)rounds * 24);
-    WASS_HIP(c, hipMemcpyAsync(duv, area, (size_t)rounds * 24, hipMemcpyHostToDevice, s));
-    WASS_HIP(c, hipEventRecord(evs, s));
-    c->stage_uv_busy = true;
+    // the caller's sample array may be pageable and short-lived: go through the pinned stage (two areas, one per frame slot: the
+    // copy out of THIS one was enqueued two frames ago; wait for it before overwriting)
+    FrameTail::Slot& fs = c->ft.cur();
+    if (fs.uv_busy) WASS_HIP(c, hipEventSynchronize(fs.ev_uv));
+    memcpy(fs.h_uv, uv, (size_t)rounds * 24);
+    WASS_HIP(c, hipMemcpyAsync(duv, fs.h_uv, (size_t)rounds * 24, hipMemcpyHostToDevice, s));
+    WASS_HIP(c, hipEventRecord(fs.ev_uv, s));
+    fs.uv_busy = true;
     constexpr int PTS = 8;
     hipLaunchKernelGGL(k_ransac_planes, dim3((rounds + 63) / 64), dim3(64), 0, s, m->valid, m->x, m->y, m->z, m->w, (const int32_t*)duv,
                        rounds, cand, counts, zero, nzero);
@@ -1782,12 +1640,9 @@ int wass_mesh_ransac_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rou
     int rc = check_ransac_args(c, m, uv, rounds);
     if (rc) return rc;
     WASS_HIP(c, hipSetDevice(c->device));
-    DevState* ds = nullptr;
-    DevState h;
-    PlaneCand* cand = nullptr;
-    double* part = nullptr;
-    if ((rc = dstate(c, &ds)) || (rc = plane_scratch(c, rounds, &cand, &part)) || (rc = record_wait(c)) ||
-        (rc = enqueue_ransac(c, m, uv, rounds, thr, cand, nullptr, 0, ds)) || (rc = record_read(c, ds, &h)))
+    DevState *ds = nullptr, h;
+    if ((rc = dstate(c, &ds)) || (rc = scratch_for(c, { lay_bytes<PlaneLay>(rounds) })) || (rc = record_wait(c)) ||
+        (rc = enqueue_ransac(c, m, uv, rounds, thr, scratch_carve<PlaneLay>(c, rounds), nullptr, 0, ds)) || (rc = record_read(c, ds, &h)))
         return rc;
     for (int k = 0; k < 4; ++k) plane_out[k] = h.ransac_plane[k];
     if (best_inliers) *best_inliers = h.ransac_best;
@@ -1800,12 +1655,14 @@ int wass_mesh_crop_plane(wass_ctx* c, wass_mesh* m, const double plane[4], doubl
     if (!c || !m || !plane) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
     DevState* ds = nullptr;
-    unsigned long long* cnt = nullptr;
     int rc = dstate(c, &ds);
     // the plane and the switch behind it, on: what the chain's final crop finds in the record
     const struct { double plane[4]; int on, pad; } given = { { plane[0], plane[1], plane[2], plane[3] }, 1, 0 };
     static_assert(offsetof(DevState, refine_ok) == offsetof(DevState, plane) + 32 && offsetof(DevState, pad1) == offsetof(DevState, plane) + 36, "one copy");
-    if (rc || (rc = counters_reset(c, &cnt)) || (rc = record_put(c, ds->plane, &given, sizeof given))) return rc;
+    static_assert(sizeof given <= STAGE_PARAM_BYTES, "the pinned stage's parameter block");
+    if (rc || (rc = record_put(c, ds->plane, &given, sizeof given))) return rc;
+    unsigned long long* cnt = c->ft.cn.kept;                   // its first NSLOT words: the one counter of this call
+    WASS_HIP(c, hipMemsetAsync(cnt, 0, (size_t)NSLOT * 8, c->ts()));
     enqueue_crop(c, m, ds->plane, &ds->refine_ok, thr, cnt);
     unsigned long long hk = 0;
     if ((rc = counters_sum(c, cnt, &hk))) return rc;
@@ -1817,18 +1674,13 @@ int wass_mesh_refine_plane(wass_ctx* c, wass_mesh* m, const wass_refine_params* 
 {
     if (!c || !m || !rp || !plane_out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
-    DevState* ds = nullptr;
-    DevState h;
-    PlaneCand* cand = nullptr;
-    double* part = nullptr;
+    DevState *ds = nullptr, h;
     int rc = dstate(c, &ds);
     // the refinement on, its crop off: both words written here, whatever an earlier fit_plane left in the record
     const int given[2] = { 1, 0 };
     static_assert(offsetof(DevState, zero) == offsetof(DevState, ransac_found) + 4, "one copy");
-    if (rc || (rc = plane_scratch(c, 0, &cand, &part)) || (rc = ensure(c, c->counters, (size_t)NSLOT * 6 * 8)) ||
-        (rc = record_put(c, &ds->ransac_found, given, sizeof given)))
-        return rc;
-    enqueue_refine(c, m, refine_dev(rp, m), ds->ransac_plane, &ds->zero, 0.0, (unsigned long long*)c->counters.p, &ds->ransac_found, part, ds);
+    if (rc || (rc = scratch_for(c, { lay_bytes<PlaneLay>(0) })) || (rc = record_put(c, &ds->ransac_found, given, sizeof given))) return rc;
+    enqueue_refine(c, m, refine_dev(rp, m), ds->ransac_plane, &ds->zero, 0.0, c->ft.cn.kept, &ds->ransac_found, scratch_carve<PlaneLay>(c, 0).part, ds);
     if ((rc = record_read(c, ds, &h))) return rc;
     if (n_inliers) *n_inliers = (uint64_t)(h.ninl + 0.5);
     if (!h.refine_ok) return set_err(c, WASS_ERR_TOO_FEW_POINTS, "plane refinement has %g inliers", h.ninl);
@@ -1844,13 +1696,10 @@ int wass_mesh_refinement_inliers(wass_ctx* c, wass_mesh* m, const wass_refine_pa
     const RefineDev rd = refine_dev(rp, m);
     const size_t n = m->n();
     const unsigned nb = nblk(n);
-    const size_t cap = (n + (size_t)every - 1) / (size_t)every;                 // at most every point is an inlier
-    const size_t off_cnt = 64, off_out = (off_cnt + (size_t)nb * 4 + 255) & ~(size_t)255;
-    int rc = ensure(c, c->scratch, off_out + cap * 24);
+    const size_t cap = points_selected(n, (size_t)every);                       // at most every point is an inlier
+    int rc = scratch_for(c, { lay_bytes<PackLay>(n, cap * 24) });
     if (rc) return rc;
-    unsigned int* total = (unsigned int*)c->scratch.p;
-    unsigned int* bcnt = (unsigned int*)((char*)c->scratch.p + off_cnt);
-    double* dout = (double*)((char*)c->scratch.p + off_out);
+    const auto [total, bcnt, dout] = scratch_carve<PackLay>(c, n, cap * 24);
     hipStream_t s = c->ts();
     hipLaunchKernelGGL(k_inlier_counts, dim3(nb), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, rd, bcnt);
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, bcnt, (int)nb, total);
@@ -1859,7 +1708,7 @@ int wass_mesh_refinement_inliers(wass_ctx* c, wass_mesh* m, const wass_refine_pa
     unsigned int ht = 0;
     WASS_HIP(c, hipMemcpyAsync(&ht, total, 4, hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipStreamSynchronize(s));
-    const size_t keep = ((size_t)ht + (size_t)every - 1) / (size_t)every;
+    const size_t keep = points_selected(ht, (size_t)every);
     if (keep == 0) return WASS_OK;
     double* host = (double*)malloc(keep * 24);
     if (!host) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
@@ -1870,29 +1719,27 @@ int wass_mesh_refinement_inliers(wass_ctx* c, wass_mesh* m, const wass_refine_pa
     return WASS_OK;
 }
 
-// wass_stereo.cpp:2062-2107 as one call: ransac_find_plane -> crop_plane(ransac_thr) -> refine_plane ->
-// crop_plane(max_distance); candidate choice, centroid and the 3x3 eigen-solve run on the device, one read-back.
-static int enqueue_fit_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds, double ransac_thr, const wass_refine_params* rp,
-                             double max_distance, DevState** dsp, unsigned long long** keptp, bool final_crop = true)
+static int check_fit_args(wass_ctx* c, const wass_mesh* m, const int32_t* uv, int rounds, const wass_refine_params* rp)
 {
     if (!c || !m || !uv || !rp || rounds <= 0) return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
-    int rc = check_ransac_args(c, m, uv, rounds);
-    if (rc) return rc;
-    WASS_HIP(c, hipSetDevice(c->device));
-    DevState* ds = nullptr;
-    PlaneCand* cand = nullptr;
-    double* part = nullptr;
-    if ((rc = dstate(c, &ds)) || (rc = plane_scratch(c, rounds, &cand, &part)) || (rc = ensure(c, c->counters, (size_t)NSLOT * 6 * 8))) return rc;
-    unsigned long long* kept1 = (unsigned long long*)c->counters.p;            // [NSLOT]
+    return check_ransac_args(c, m, uv, rounds);
+}
+// wass_stereo.cpp:2062-2107 as one call: ransac_find_plane -> crop_plane(ransac_thr) -> refine_plane ->
+// crop_plane(max_distance); candidate choice, centroid and the 3x3 eigen-solve run on the device, one read-back.
+// The caller has checked the arguments (check_fit_args), ensured the scratch buffer for PlaneLay and holds the record and counters.
+static int enqueue_fit_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds, double ransac_thr, const wass_refine_params* rp,
+                             double max_distance, DevState* ds, bool final_crop = true)
+{
+    const PlaneLay pl = scratch_carve<PlaneLay>(c, rounds);
+    unsigned long long* kept1 = c->ft.cn.kept;                                      // [NSLOT]
     unsigned long long* kept2 = kept1 + NSLOT;
-    if ((rc = enqueue_ransac(c, m, uv, rounds, ransac_thr, cand, kept1, 2 * NSLOT, ds))) return rc;
-    if (c->ev_tail[4]) (void)hipEventRecord(c->ev_tail[4], c->ts());
-    enqueue_refine(c, m, refine_dev(rp, m), ds->ransac_plane, &ds->ransac_found, ransac_thr, kept1, &ds->ransac_found, part, ds);
+    int rc = enqueue_ransac(c, m, uv, rounds, ransac_thr, pl, kept1, 2 * NSLOT, ds);
+    if (rc) return rc;
+    if (c->ft.ev()[4]) (void)hipEventRecord(c->ft.ev()[4], c->ts());
+    enqueue_refine(c, m, refine_dev(rp, m), ds->ransac_plane, &ds->ransac_found, ransac_thr, kept1, &ds->ransac_found, pl.part, ds);
     if (final_crop)                                              // the frame tail folds this pass into its limits / counts pass
         enqueue_crop(c, m, ds->plane, &ds->refine_ok, max_distance, kept2);
     WASS_HIP(c, hipGetLastError());
-    *dsp = ds;
-    *keptp = kept1;
     return WASS_OK;
 }
 
@@ -1900,15 +1747,17 @@ int wass_mesh_fit_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds
                         double max_distance, wass_plane_result* out)
 {
     if (!out) return set_err(c, WASS_ERR_INVALID_ARG, "bad argument");
-    DevState* ds = nullptr;
-    unsigned long long* kept1 = nullptr;
-    int rc = enqueue_fit_plane(c, m, uv, rounds, ransac_thr, rp, max_distance, &ds, &kept1);
+    int rc = check_fit_args(c, m, uv, rounds, rp);
     if (rc) return rc;
+    WASS_HIP(c, hipSetDevice(c->device));
+    DevState* ds = nullptr;
+    if ((rc = dstate(c, &ds)) || (rc = scratch_for(c, { lay_bytes<PlaneLay>(rounds) })) || (rc = enqueue_fit_plane(c, m, uv, rounds, ransac_thr, rp, max_distance, ds)))
+        return rc;
     hipStream_t s = c->ts();
     DevState h;
     unsigned long long hk[2 * NSLOT];
     WASS_HIP(c, hipMemcpyAsync(&h, ds, sizeof h, hipMemcpyDeviceToHost, s));
-    WASS_HIP(c, hipMemcpyAsync(hk, kept1, sizeof hk, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipMemcpyAsync(hk, c->ft.cn.kept, sizeof hk, hipMemcpyDeviceToHost, s));
     WASS_HIP(c, hipStreamSynchronize(s));
     memset(out, 0, sizeof *out);
     out->found = h.ransac_found;
@@ -1919,6 +1768,26 @@ int wass_mesh_fit_plane(wass_ctx* c, wass_mesh* m, const int32_t* uv, int rounds
         out->refine_inliers = (uint64_t)(h.ninl + 0.5);
         if (!h.refine_ok) return set_err(c, WASS_ERR_TOO_FEW_POINTS, "plane refinement has %g inliers", h.ninl);
     }
+    return WASS_OK;
+}
+
+// The last step of the chain up to the image's header, for the frame tail and the xyzC encoder alike.  The record holds R|T and
+// the crop switch (refine_ok); decided on the device: the crop by ds->plane where the switch is on, the limits of the transformed
+// survivors, their number per block and in all, the scale factors, the header in the image.  What is left is k_xyzc_pack_dev.
+static int enqueue_limits_header(wass_ctx* c, wass_mesh* m, DevState* ds, double crop_thr, const PackLay& pk,
+                                 const unsigned long long* tri, const unsigned int* inl_total)
+{
+    const CountersLay& cn = c->ft.cn;
+    hipStream_t s = c->ts();
+    const size_t n = m->n();
+    const unsigned nb = nblk(n);
+    WASS_HIP(c, hipMemcpyAsync(cn.lim, c->ft.stage.lim_init, (size_t)NSLOT * 6 * 8, hipMemcpyHostToDevice, s));
+    WASS_HIP(c, hipStreamWaitEvent(s, c->ft.ev_copy, 0));                 // the previous download still reading the image
+    hipLaunchKernelGGL(k_crop_limits_counts_dev, dim3((nb + CLC_CHUNKS - 1) / CLC_CHUNKS), dim3(256), 0, s, m->valid, m->x, m->y, m->z, n,
+                       (const DevState*)ds, crop_thr, cn.kept + NSLOT, cn.lim, pk.bcnt, nb);
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, pk.bcnt, (int)nb, pk.total);
+    hipLaunchKernelGGL(k_frame_header, dim3(1), dim3(64), 0, s, ds, (const unsigned long long*)cn.lim, (const unsigned int*)pk.total,
+                       (const unsigned long long*)cn.kept, (unsigned char*)c->ft.xyzc.p, tri, inl_total, (const unsigned int*)nullptr);
     return WASS_OK;
 }
 
@@ -1949,125 +1818,97 @@ int wass_mesh_finish_frame_async_ex2(wass_ctx* c, wass_mesh* m, double percentil
     if (inliers_text_dst && inliers_every <= 0) return set_err(c, WASS_ERR_INVALID_ARG, "bad inlier selection");
     WASS_HIP(c, hipSetDevice(c->device));
     const size_t n = m->n();
-    if (capacity < 148 + n * 6)
-        return set_err(c, WASS_ERR_INVALID_ARG, "the asynchronous form needs room for every grid point: %zu bytes", 148 + n * 6);
-    if (c->nframe_enq - c->nframe_col >= 2)
+    if (capacity < xyzc_bytes(n))
+        return set_err(c, WASS_ERR_INVALID_ARG, "the asynchronous form needs room for every grid point: %zu bytes", xyzc_bytes(n));
+    FrameTail& ft = c->ft;
+    if (ft.nframe_enq - ft.nframe_col >= 2)
         return set_err(c, WASS_ERR_INVALID_ARG, "two frames are pending already: read the older one's record first (wass_ctx_frame_result)");
-    const int slot = (int)(c->nframe_enq & 1);
-    wass_ctx::FrameSlot& fs = c->fslot[slot];
-    if (!fs.h_frame && hipHostMalloc((void**)&fs.h_frame, sizeof(DevState) + 64, hipHostMallocDefault) != hipSuccess)
-        return set_err(c, WASS_ERR_NO_MEMORY, "hipHostMalloc failed");
-    c->ds_slot = slot;                                     // the stage helpers below build THIS slot's record
-    wass::Buf& inlbuf = slot ? c->inl2 : c->inl;           // ... and the selection lives in this slot's buffer
-    hipEvent_t ev_prev = c->ev_copy;                       // the previous frame's downloads (they read the shared file image and masks)
+    int rc = check_fit_args(c, m, uv, rounds, rp);
+    if (rc) return rc;
+    const bool sel = inliers_dst || inliers_text_dst, text = inliers_text_dst != nullptr;
+    const size_t cap = sel ? points_selected(n, (size_t)inliers_every) : 0;
+    if (inliers_dst && inliers_capacity < cap) return set_err(c, WASS_ERR_INVALID_ARG, "inliers_dst must hold %zu points", cap);
+    if (text && inliers_text_capacity < cap * INL_LINE_MAX)
+        return set_err(c, WASS_ERR_INVALID_ARG, "inliers_text_dst must hold %zu bytes", cap * (size_t)INL_LINE_MAX);
+    FrameTail::Slot& fs = ft.slot(ft.nframe_enq);
+    if (!fs.h_frame.alloc(sizeof(DevState))) return set_err(c, WASS_ERR_NO_MEMORY, "hipHostMalloc failed");
+    hipEvent_t ev_prev = ft.ev_copy;                       // the previous frame's downloads (they read the shared file image and masks)
+    ft.cur_frame = ft.nframe_enq;                          // the stage helpers below build THIS slot's record, the selection lives in its buffer
+    // all memory of the chain before anything is enqueued.  The scratch buffer serves the components, then the plane stages, then the
+    // compactions' block counts, which lie over the candidates: k_refine_finish was the last reader of the plane stages' pieces.
+    InlierLay il = {};
     DevState* ds = nullptr;
-    unsigned long long* kept1 = nullptr;
-    int rc;
-    const bool timed = c->ev_tail[0] != nullptr;          // a wass_triangulate[_dev] call of this context has created (and recorded) them
-    if (timed) (void)hipEventRecord(c->ev_tail[1], c->ts());
-    if ((rc = enqueue_remove_outliers(c, m, percentile, &ds))) return rc;
+    if ((rc = dstate(c, &ds)) || (rc = scratch_for(c, { lay_bytes<CclLay>(n), lay_bytes<PlaneLay>(rounds), lay_bytes<PackLay>(n) })) || (rc = ensure(c, ft.xyzc, xyzc_bytes(n) + 16)) ||
+        (component_mask_dst && (rc = ensure(c, ft.ccmask, n))) || (sel && (rc = carve_buf(c, fs.inl, [&](Carve& a) { il.carve(a, cap, text); }))))
+        return rc;
+    const bool timed = ft.ev()[0] != nullptr;             // a wass_triangulate[_dev] call of this context has created (and recorded) them
+    if (timed) (void)hipEventRecord(ft.ev()[1], c->ts());
+    if ((rc = enqueue_remove_outliers(c, m, percentile, ds))) return rc;
     if (component_mask_dst) {                              // what cluster_biggest_connected_component left valid (graph_components.jpg)
-        if ((rc = ensure(c, c->ccmask, n))) return rc;
         WASS_HIP(c, hipStreamWaitEvent(c->ts(), ev_prev, 0));
-        WASS_HIP(c, hipMemcpyAsync(c->ccmask.p, m->valid, n, hipMemcpyDeviceToDevice, c->ts()));
+        WASS_HIP(c, hipMemcpyAsync(ft.ccmask.p, m->valid, n, hipMemcpyDeviceToDevice, c->ts()));
     }
-    if ((rc = enqueue_fit_plane(c, m, uv, rounds, ransac_thr, rp, max_distance, &ds, &kept1, false))) return rc;
+    if ((rc = enqueue_fit_plane(c, m, uv, rounds, ransac_thr, rp, max_distance, ds, false))) return rc;
     const unsigned nb = nblk(n);
-    if ((rc = ensure(c, c->xyzc, 148 + n * 6 + 16))) return rc;
-    // block counts live behind the candidate area of the scratch buffer, which enqueue_fit_plane sized; grow if needed
-    const size_t need = 64 + (size_t)nb * 4 + 16;
-    if (c->scratch.cap < need && (rc = ensure(c, c->scratch, need))) return rc;
+    const PackLay pk = scratch_carve<PackLay>(c, n);
     hipStream_t s = c->ts();
     // plane_refinement_inliers.xyz: the refinement inliers are the points that survived the crop by the RANSAC plane, which
     // enqueue_fit_plane has just applied; the final crop (below) has not run yet -- the point main() collects them at
-    size_t inl_copy = 0, text_copy = 0;
-    const char* text_src = nullptr;
-    const unsigned int* text_totals = nullptr;             // [0] bytes of text, [1] numbers not formatted: written on the copy stream
-    unsigned int* inl_total = nullptr;
-    if (inliers_dst || inliers_text_dst) {
+    size_t text_copy = 0;
+    unsigned int* const inl_total = il.totals;             // (null without a selection) [0] refinement inliers, [2] bytes of text, [3] numbers not formatted
+    if (sel) {
         const RefineDev rd = refine_dev(rp, m);
-        const size_t cap = (n + (size_t)inliers_every - 1) / (size_t)inliers_every;
-        if (inliers_dst && inliers_capacity < cap) return set_err(c, WASS_ERR_INVALID_ARG, "inliers_dst must hold %zu points", cap);
         const unsigned nb2 = nblk(cap);
-        const size_t text_off = (256 + cap * 24 + (size_t)nb2 * 4 + 255) & ~(size_t)255;
-        if (inliers_text_dst && inliers_text_capacity < cap * INL_LINE_MAX)
-            return set_err(c, WASS_ERR_INVALID_ARG, "inliers_text_dst must hold %zu bytes", cap * (size_t)INL_LINE_MAX);
-        if ((rc = ensure(c, inlbuf, text_off + (inliers_text_dst ? cap * INL_LINE_MAX + (size_t)nb2 * 256 * INL_LINE_MAX + 256 : 0)))) return rc;   // text, staging
-        inl_total = (unsigned int*)inlbuf.p;                       // [0]: number of refinement inliers, [2]: bytes of text, [3]: numbers not formatted; points from byte 256
-        unsigned int* bc = (unsigned int*)((char*)c->scratch.p + 64);
-        double* dout = (double*)((char*)inlbuf.p + 256);
         WASS_HIP(c, hipStreamWaitEvent(s, fs.ev_copy, 0));        // the download (and the text kernels) that read THIS buffer: two frames ago
-        hipLaunchKernelGGL(k_inlier_counts, dim3(nb), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, rd, bc);
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, bc, (int)nb, inl_total);
-        hipLaunchKernelGGL(k_inlier_pack, dim3(nb), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, rd, (const unsigned int*)bc,
-                           (unsigned)inliers_every, dout);
-        inl_copy = inliers_dst ? cap * 24 : 0;                    // (text only: the points stay on the device, wass_ctx_frame_inliers fetches them on demand)
-        if (inliers_text_dst) {                                   // the file's text, formatted here (fmt_g6.h)
-            unsigned int* bb = (unsigned int*)((char*)inlbuf.p + 256 + cap * 24);
-            char* staging = (char*)inlbuf.p + text_off + cap * INL_LINE_MAX;
+        hipLaunchKernelGGL(k_inlier_counts, dim3(nb), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, rd, pk.bcnt);
+        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, pk.bcnt, (int)nb, inl_total);
+        hipLaunchKernelGGL(k_inlier_pack, dim3(nb), dim3(256), 0, s, m->valid, m->x, m->y, m->z, m->w, n, rd, (const unsigned int*)pk.bcnt,
+                           (unsigned)inliers_every, il.pts);
+        if (text) {                                               // the file's text, formatted here (fmt_g6.h)
             // (On the tail stream.  Putting these kernels on the copy stream behind an event, or into a small persistent grid held to one
             // wave per SIMD, changed nothing / made it worse: what they cost the C++ driver is their share of a tail stream that is
             // nearly as long as the SGM stage by now -- NOTES/tail_and_host.md, round 5.)
             WASS_HIP(c, hipMemsetAsync(inl_total + 2, 0, 8, s));
-            hipLaunchKernelGGL(k_inl_text_format, dim3(nb2), dim3(256), 0, s, (const double*)dout, (const unsigned int*)inl_total, (unsigned)inliers_every, staging,
-                               bb, inl_total + 3);
-            hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, bb, (int)nb2, inl_total + 2);
+            hipLaunchKernelGGL(k_inl_text_format, dim3(nb2), dim3(256), 0, s, (const double*)il.pts, (const unsigned int*)inl_total, (unsigned)inliers_every,
+                               il.staging, il.blockbytes, inl_total + 3);
+            hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, il.blockbytes, (int)nb2, inl_total + 2);
             // Pinned host memory is mapped into the device's address space: the packing kernel then writes the text straight into the
             // caller's buffer -- exactly the file's bytes cross PCIe, where a copy would have to move the 40-bytes-per-point worst
             // case (the length is only known on the device).
             char* direct = nullptr;
-            {
-                hipPointerAttribute_t at;
-                if (hipPointerGetAttributes(&at, inliers_text_dst) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) direct = (char*)at.devicePointer;
-                else (void)hipGetLastError();
-            }
-            hipLaunchKernelGGL(k_inl_text_pack, dim3(nb2), dim3(256), 0, s, (const char*)staging, (const unsigned int*)bb, (const unsigned int*)(inl_total + 2), nb2,
-                               direct ? direct : (char*)inlbuf.p + text_off);
-            text_totals = inl_total + 2;
-            if (direct) goto text_done;
-            text_copy = cap * INL_LINE_MAX;
-            text_src = (const char*)inlbuf.p + text_off;
-        text_done:;
+            hipPointerAttribute_t at;
+            if (hipPointerGetAttributes(&at, inliers_text_dst) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) direct = (char*)at.devicePointer;
+            else (void)hipGetLastError();
+            hipLaunchKernelGGL(k_inl_text_pack, dim3(nb2), dim3(256), 0, s, (const char*)il.staging, (const unsigned int*)il.blockbytes,
+                               (const unsigned int*)(inl_total + 2), nb2, direct ? direct : il.text);
+            if (!direct) text_copy = cap * INL_LINE_MAX;
         }
         fs.inl_cap = cap;
     }
+    unsigned char* img = (unsigned char*)ft.xyzc.p;
     hipLaunchKernelGGL(k_frame_rt, dim3(1), dim3(64), 0, s, ds);
-    unsigned char* stage = nullptr;
-    if ((rc = host_stage(c, &stage))) return rc;
-    if ((rc = ensure(c, c->limits, NSLOT * 6 * 8))) return rc;
-    unsigned long long* lim = (unsigned long long*)c->limits.p;            // [NSLOT][6] keys
-    WASS_HIP(c, hipMemcpyAsync(lim, stage + 4096, NSLOT * 6 * 8, hipMemcpyHostToDevice, s));
-    unsigned int* total = (unsigned int*)c->scratch.p;
-    unsigned int* bcnt = (unsigned int*)((char*)c->scratch.p + 64);
-    unsigned char* img = (unsigned char*)c->xyzc.p;
-    WASS_HIP(c, hipStreamWaitEvent(s, ev_prev, 0));                       // the previous frame's download still reading the image
-    hipLaunchKernelGGL(k_crop_limits_counts_dev, dim3((nb + CLC_CHUNKS - 1) / CLC_CHUNKS), dim3(256), 0, s, m->valid, m->x, m->y, m->z, n,
-                       (const DevState*)ds, max_distance, kept1 + NSLOT, lim, bcnt, nb);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, bcnt, (int)nb, total);
-    hipLaunchKernelGGL(k_frame_header, dim3(1), dim3(64), 0, s, ds, (const unsigned long long*)lim, (const unsigned int*)total,
-                       (const unsigned long long*)kept1, img, (const unsigned long long*)c->tri_cnt.p, (const unsigned int*)inl_total,
-                       (const unsigned int*)nullptr);
+    if ((rc = enqueue_limits_header(c, m, ds, max_distance, pk, (const unsigned long long*)ft.tri_cnt.p, inl_total))) return rc;
     hipLaunchKernelGGL(k_xyzc_pack_dev, dim3(nb), dim3(256), 0, s, m->valid, m->x, m->y, m->z, n, (const DevState*)ds,
-                       (const unsigned int*)bcnt, (uint16_t*)(img + 148));
+                       (const unsigned int*)pk.bcnt, (uint16_t*)(img + XYZC_HEADER));
     WASS_HIP(c, hipGetLastError());
-    if (timed) { (void)hipEventRecord(c->ev_tail[5], s); c->tail_timed[c->tail_set] = true; }
-    fs.tail_set = c->tail_set;
-    if (text_totals) hipLaunchKernelGGL(k_inl_text_totals, dim3(1), dim3(64), 0, s, ds, text_totals);   // after the header kernel's write of the record
-    WASS_HIP(c, hipEventRecord(c->ev_pack, s));
-    WASS_HIP(c, hipStreamWaitEvent(c->copy, c->ev_pack, 0));
-    WASS_HIP(c, hipMemcpyAsync(fs.h_frame, ds, sizeof(DevState), hipMemcpyDeviceToHost, c->copy));
-    WASS_HIP(c, hipMemcpyAsync(dst, img, 148 + n * 6, hipMemcpyDeviceToHost, c->copy));
-    if (inl_copy) WASS_HIP(c, hipMemcpyAsync(inliers_dst, (const char*)inlbuf.p + 256, inl_copy, hipMemcpyDeviceToHost, c->copy));
+    if (timed) { (void)hipEventRecord(ft.ev()[5], s); ft.timed[ft.tail_set] = true; }
+    fs.tail_set = ft.tail_set;
+    if (text) hipLaunchKernelGGL(k_inl_text_totals, dim3(1), dim3(64), 0, s, ds, (const unsigned int*)(inl_total + 2));   // after the header kernel's write of the record
+    WASS_HIP(c, hipEventRecord(ft.ev_pack, s));
+    WASS_HIP(c, hipStreamWaitEvent(c->copy, ft.ev_pack, 0));
+    WASS_HIP(c, hipMemcpyAsync(fs.h_frame.p, ds, sizeof(DevState), hipMemcpyDeviceToHost, c->copy));
+    WASS_HIP(c, hipMemcpyAsync(dst, img, xyzc_bytes(n), hipMemcpyDeviceToHost, c->copy));
+    // (text only: the points stay on the device, wass_ctx_frame_inliers fetches them on demand)
+    if (inliers_dst) WASS_HIP(c, hipMemcpyAsync(inliers_dst, il.pts, cap * 24, hipMemcpyDeviceToHost, c->copy));
     // (the text's length is only known on the device: the copy takes what a frame of this size can need at most -- 0.1 ms per MB)
-    if (text_copy) WASS_HIP(c, hipMemcpyAsync(inliers_text_dst, text_src, text_copy, hipMemcpyDeviceToHost, c->copy));
-    if (component_mask_dst) WASS_HIP(c, hipMemcpyAsync(component_mask_dst, c->ccmask.p, n, hipMemcpyDeviceToHost, c->copy));
+    if (text_copy) WASS_HIP(c, hipMemcpyAsync(inliers_text_dst, il.text, text_copy, hipMemcpyDeviceToHost, c->copy));
+    if (component_mask_dst) WASS_HIP(c, hipMemcpyAsync(component_mask_dst, ft.ccmask.p, n, hipMemcpyDeviceToHost, c->copy));
     WASS_HIP(c, hipEventRecord(fs.ev_copy, c->copy));
-    c->ev_copy = fs.ev_copy;                  // "the most recently recorded download event"
-    fs.inl_every = (inliers_dst || inliers_text_dst) ? inliers_every : 0;
-    fs.inl_text = inliers_text_dst != nullptr;
+    ft.ev_copy = fs.ev_copy;
+    fs.inl_every = sel ? inliers_every : 0;
+    fs.inl_text = text;
     fs.sgm_call = c->nsgm;                    // the SGM call that fed this frame is the last one enqueued (0: none)
-    c->frame_pending = true;
-    ++c->nframe_enq;
+    ++ft.nframe_enq;
     return WASS_OK;
 }
 
@@ -2078,17 +1919,15 @@ int wass_format_g6(double v, char* out) { return out ? wass::fmt_g6(v, out) : -1
 int wass_ctx_frame_inliers(wass_ctx* c, double* dst, size_t capacity_points, uint64_t* n_out)
 {
     if (!c || !dst) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
-    if (c->nframe_col == 0) return set_err(c, WASS_ERR_INVALID_ARG, "no collected frame");
-    const int slot = (int)((c->nframe_col - 1) & 1);       // the frame whose record was read last; its buffer lives until the frame after next
-    const wass_ctx::FrameSlot& fs = c->fslot[slot];
-    const wass::Buf& inlbuf = slot ? c->inl2 : c->inl;
-    if (fs.inl_every <= 0 || !inlbuf.p || !fs.h_frame) return set_err(c, WASS_ERR_INVALID_ARG, "no collected frame with an inlier selection");
+    if (c->ft.nframe_col == 0) return set_err(c, WASS_ERR_INVALID_ARG, "no collected frame");
+    const FrameTail::Slot& fs = c->ft.slot(c->ft.nframe_col - 1);   // the frame whose record was read last; its buffer lives until the frame after next
+    if (fs.inl_every <= 0 || !fs.inl.p || !fs.h_frame.p) return set_err(c, WASS_ERR_INVALID_ARG, "no collected frame with an inlier selection");
     WASS_HIP(c, hipSetDevice(c->device));
-    const DevState& h = *(const DevState*)fs.h_frame;
-    const uint64_t n = ((uint64_t)h.ninl_sel + (uint64_t)fs.inl_every - 1) / (uint64_t)fs.inl_every;
+    const DevState& h = *(const DevState*)fs.h_frame.p;
+    const uint64_t n = points_selected(h.ninl_sel, (size_t)fs.inl_every);
     if (n > capacity_points || n > fs.inl_cap) return set_err(c, WASS_ERR_INVALID_ARG, "dst must hold %llu points", (unsigned long long)n);
     // (the frame's own downloads have completed -- its record was read -- so its selection is complete; a plain blocking copy)
-    WASS_HIP(c, hipMemcpy(dst, (const char*)inlbuf.p + 256, (size_t)n * 24, hipMemcpyDeviceToHost));
+    WASS_HIP(c, hipMemcpy(dst, carved<InlierLay>(fs.inl.p, fs.inl_cap, fs.inl_text).pts, (size_t)n * 24, hipMemcpyDeviceToHost));
     if (n_out) *n_out = n;
     return WASS_OK;
 }
@@ -2096,12 +1935,12 @@ int wass_ctx_frame_inliers(wass_ctx* c, double* dst, size_t capacity_points, uin
 int wass_ctx_frame_result(wass_ctx* c, wass_frame_result* out)
 {
     if (!c || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
-    if (c->nframe_col >= c->nframe_enq) return set_err(c, WASS_ERR_INVALID_ARG, "no wass_mesh_finish_frame_async call to wait for");
-    const wass_ctx::FrameSlot& fs = c->fslot[c->nframe_col & 1];   // the OLDER of the pending frames
+    FrameTail& ft = c->ft;
+    if (ft.nframe_col >= ft.nframe_enq) return set_err(c, WASS_ERR_INVALID_ARG, "no wass_mesh_finish_frame_async call to wait for");
+    const FrameTail::Slot& fs = ft.slot(ft.nframe_col);             // the OLDER of the pending frames
     WASS_HIP(c, hipEventSynchronize(fs.ev_copy));
-    ++c->nframe_col;
-    c->h_frame = fs.h_frame;
-    const DevState& h = *(const DevState*)fs.h_frame;
+    ++ft.nframe_col;
+    const DevState& h = *(const DevState*)fs.h_frame.p;
     memset(out, 0, sizeof *out);
     out->zgap = h.zgap; out->n_gaps = h.sel_total; out->component_size = h.ccl_best >> 32;
     out->found = h.ransac_found; out->refine_ok = h.refine_ok;
@@ -2109,14 +1948,14 @@ int wass_ctx_frame_result(wass_ctx* c, wass_frame_result* out)
     for (int k = 0; k < 4; ++k) { out->ransac_plane[k] = h.ransac_plane[k]; out->plane[k] = h.ransac_found && h.refine_ok ? h.plane[k] : NAN; }
     if (h.ransac_found) { out->kept_after_ransac_crop = h.kept1; out->kept_final = h.kept2; out->refine_inliers = (uint64_t)(h.ninl + 0.5); }
     out->n_points = h.npts;
-    out->xyzc_bytes = 148 + (uint64_t)h.npts * 6;
+    out->xyzc_bytes = xyzc_bytes(h.npts);
     out->n_triangulated = h.ntri;
-    if (c->tail_timed[fs.tail_set]) {                        // all six events lie before the download this function has waited for
-        hipEvent_t* const ev = c->ev_tail_sets[fs.tail_set];       // the frame's own set: the next frame may have been triangulated already
+    if (ft.timed[fs.tail_set]) {                             // all six events lie before the download this function has waited for
+        const Event* const ev = ft.ev_sets[fs.tail_set];           // the frame's own set: the next frame may have been triangulated already
         for (int k = 0; k < 5; ++k)
             if (hipEventElapsedTime(&out->stage_ms[k], ev[k], ev[k + 1]) != hipSuccess) out->stage_ms[k] = 0.0f;
     }
-    out->n_inliers_out = fs.inl_every > 0 ? ((uint64_t)h.ninl_sel + (uint64_t)fs.inl_every - 1) / (uint64_t)fs.inl_every : 0;
+    out->n_inliers_out = fs.inl_every > 0 ? points_selected(h.ninl_sel, (size_t)fs.inl_every) : 0;
     out->inliers_text_bytes = fs.inl_text ? h.inl_text_bytes : 0;
     out->inliers_text_unsupported = fs.inl_text ? h.inl_text_bad : 0;
     if (fs.sgm_call > 0 && c->nsgm - fs.sgm_call < (unsigned long long)wass_ctx::NSGM_SETS) {
@@ -2140,7 +1979,7 @@ void wass_RT_from_plane(const double plane[4], double R[9], double T[3], double 
 int wass_mesh_encode_xyzc(wass_ctx* c, wass_mesh* m, const double plane[4], void** bytes, size_t* nbytes)
 {
     if (!c || !m || !bytes || !nbytes) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
-    const size_t cap = 148 + m->n() * 6;
+    const size_t cap = xyzc_bytes(m->n());
     void* buf = malloc(cap);
     if (!buf) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
     int rc = wass_mesh_encode_xyzc_to(c, m, plane, buf, cap, nbytes);
@@ -2149,86 +1988,48 @@ int wass_mesh_encode_xyzc(wass_ctx* c, wass_mesh* m, const double plane[4], void
     return WASS_OK;
 }
 
+// save_as_xyz_compressed as a stage-by-stage call: R|T of the given plane (identity without one) go into the current record with
+// the crop switch OFF, whatever an earlier fit left there, and the chain's last step runs on them.  k_frame_rt, which derives R|T
+// from that fit, is not run; `valid` is never written.
 static int encode_xyzc_impl(wass_ctx* c, wass_mesh* m, const double plane[4], void* dst, size_t capacity, size_t* nbytes, bool async)
 {
     if (!c || !m || !dst || !nbytes) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
     WASS_HIP(c, hipSetDevice(c->device));
-    double R[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, T[3] = { 0, 0, 0 }, Rinv[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, Tinv[3] = { 0, 0, 0 };
-    if (plane) wass_RT_from_plane(plane, R, T, Rinv, Tinv);
-    RTDev rt;
-    memcpy(rt.R, R, sizeof R); memcpy(rt.T, T, sizeof T);
+    struct { int refine_ok, pad; double R[9], T[3], Rinv[9], Tinv[3]; } given = { 0, 0, { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, { 0, 0, 0 }, { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, { 0, 0, 0 } };
+    static_assert(offsetof(DevState, rtR) == offsetof(DevState, refine_ok) + 8 && offsetof(DevState, mn) == offsetof(DevState, refine_ok) + sizeof given, "one copy");
+    static_assert(sizeof given <= STAGE_PARAM_BYTES, "the pinned stage's parameter block");
+    if (plane) wass_RT_from_plane(plane, given.R, given.T, given.Rinv, given.Tinv);
+    FrameTail& ft = c->ft;
     const size_t n = m->n();
-    const unsigned nb = nblk(n);
-    int rc = ensure(c, c->scratch, 64 + (size_t)nb * 4 + 16);
-    if (rc) return rc;
-    if ((rc = ensure(c, c->counters, (size_t)NSLOT * 6 * 8))) return rc;
-    // the packed triples get their own buffer: the download may still be in flight (async form) while the next
-    // frame's stages reuse the scratch area
-    if ((rc = ensure(c, c->xyzc, n * 6 + 16))) return rc;
-    unsigned long long* lim = (unsigned long long*)c->counters.p;          // [NSLOT][6] keys
-    unsigned int* total = (unsigned int*)c->scratch.p;
-    unsigned int* bcnt = (unsigned int*)((char*)c->scratch.p + 64);
-    uint16_t* dq = (uint16_t*)c->xyzc.p;
-    unsigned long long init[NSLOT * 6];
-    for (int i = 0; i < NSLOT; ++i) for (int k = 0; k < 6; ++k) init[i * 6 + k] = k < 3 ? ~0ull : 0ull;
-    WASS_HIP(c, hipMemcpyAsync(lim, init, sizeof init, hipMemcpyHostToDevice, c->ts()));
-    hipLaunchKernelGGL(k_xyzc_limits, dim3(1024), dim3(256), 0, c->ts(), m->valid, m->x, m->y, m->z, n, rt, lim);
-    hipLaunchKernelGGL(k_block_counts, dim3(nb), dim3(256), 0, c->ts(), m->valid, n, bcnt);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, c->ts(), bcnt, (int)nb, total);
-    unsigned long long hs[NSLOT * 6], hl[6] = { ~0ull, ~0ull, ~0ull, 0, 0, 0 };
-    unsigned int npts = 0;
-    WASS_HIP(c, hipMemcpyAsync(hs, lim, sizeof hs, hipMemcpyDeviceToHost, c->ts()));
-    WASS_HIP(c, hipMemcpyAsync(&npts, total, 4, hipMemcpyDeviceToHost, c->ts()));
-    WASS_HIP(c, hipStreamSynchronize(c->ts()));
-    for (int i = 0; i < NSLOT; ++i)
-        for (int k = 0; k < 3; ++k) {
-            if (hs[i * 6 + k] < hl[k]) hl[k] = hs[i * 6 + k];
-            if (hs[i * 6 + 3 + k] > hl[3 + k]) hl[3 + k] = hs[i * 6 + 3 + k];
-        }
-    double mn[3], mx[3], sc[3];
-    for (int k = 0; k < 3; ++k) {
-        // no valid point: the reference writes +-DBL_MAX limits; keep that
-        mn[k] = npts ? order_unkey(hl[k]) : 1.7976931348623157e308;
-        mx[k] = npts ? order_unkey(hl[3 + k]) : -1.7976931348623157e308;
-        sc[k] = 65535.0 / (mx[k] - mn[k]);
-    }
-    const size_t total_bytes = 148 + (size_t)npts * 6;
+    DevState *ds = nullptr, h;
+    int rc;
+    // the image has its own buffer: the download may still be in flight (async form) while the next frame's stages reuse the scratch area
+    if ((rc = dstate(c, &ds)) || (rc = scratch_for(c, { lay_bytes<PackLay>(n) })) || (rc = ensure(c, ft.xyzc, xyzc_bytes(n) + 16)) ||
+        (rc = record_put(c, &ds->refine_ok, &given, sizeof given)))
+        return rc;
+    const PackLay pk = scratch_carve<PackLay>(c, n);
+    unsigned char* img = (unsigned char*)ft.xyzc.p;
+    hipStream_t s = c->ts();
+    WASS_HIP(c, hipMemsetAsync(ft.cn.kept, 0, (size_t)2 * NSLOT * 8, s));     // no crop counts here; k_frame_header folds the counters into the record
+    if ((rc = enqueue_limits_header(c, m, ds, 0.0, pk, nullptr, nullptr)) || (rc = record_read(c, ds, &h))) return rc;
+    const size_t total_bytes = xyzc_bytes(h.npts);
     if (total_bytes > capacity)
         return set_err(c, WASS_ERR_INVALID_ARG, "xyzC needs %zu bytes, buffer has %zu", total_bytes, capacity);
-    if (npts) {
-        WASS_HIP(c, hipStreamWaitEvent(c->ts(), c->ev_copy, 0));            // a previous download still reading dq
-        hipLaunchKernelGGL(k_xyzc_pack, dim3(nb), dim3(256), 0, c->ts(), m->valid, m->x, m->y, m->z, n, rt, mn[0], mn[1], mn[2],
-                           sc[0], sc[1], sc[2], (const unsigned int*)bcnt, dq);
-    }
-    unsigned char* buf = (unsigned char*)dst;
-    size_t o = 0;
-    const uint32_t n32 = npts;
-    memcpy(buf + o, &n32, 4); o += 4;
-    memcpy(buf + o, sc, 24); o += 24;
-    memcpy(buf + o, mn, 24); o += 24;
-    memcpy(buf + o, Rinv, 72); o += 72;
-    memcpy(buf + o, Tinv, 24); o += 24;
-    if (npts) {
-        // the download runs on its own stream (a DMA engine), so the next frame's kernels do not wait for PCIe
-        WASS_HIP(c, hipEventRecord(c->ev_pack, c->ts()));
-        WASS_HIP(c, hipStreamWaitEvent(c->copy, c->ev_pack, 0));
-        WASS_HIP(c, hipMemcpyAsync(buf + o, dq, (size_t)npts * 6, hipMemcpyDeviceToHost, c->copy));
-        WASS_HIP(c, hipEventRecord(c->ev_copy, c->copy));
-        if (!async) WASS_HIP(c, hipStreamSynchronize(c->copy));
-    }
+    if (h.npts)
+        hipLaunchKernelGGL(k_xyzc_pack_dev, dim3(nblk(n)), dim3(256), 0, s, m->valid, m->x, m->y, m->z, n, (const DevState*)ds,
+                           (const unsigned int*)pk.bcnt, (uint16_t*)(img + XYZC_HEADER));
+    // the download runs on its own stream (a DMA engine), so the next frame's kernels do not wait for PCIe
+    WASS_HIP(c, hipEventRecord(ft.ev_pack, s));
+    WASS_HIP(c, hipStreamWaitEvent(c->copy, ft.ev_pack, 0));
+    WASS_HIP(c, hipMemcpyAsync(dst, img, total_bytes, hipMemcpyDeviceToHost, c->copy));
+    WASS_HIP(c, hipEventRecord(ft.ev_copy, c->copy));
+    if (!async) WASS_HIP(c, hipStreamSynchronize(c->copy));
     *nbytes = total_bytes;
     return WASS_OK;
 }
 
-int wass_mesh_encode_xyzc_to(wass_ctx* c, wass_mesh* m, const double plane[4], void* dst, size_t capacity, size_t* nbytes)
-{
-    return encode_xyzc_impl(c, m, plane, dst, capacity, nbytes, false);
-}
-
-int wass_mesh_encode_xyzc_async(wass_ctx* c, wass_mesh* m, const double plane[4], void* dst, size_t capacity, size_t* nbytes)
-{
-    return encode_xyzc_impl(c, m, plane, dst, capacity, nbytes, true);
-}
+int wass_mesh_encode_xyzc_to(wass_ctx* c, wass_mesh* m, const double plane[4], void* dst, size_t capacity, size_t* nbytes) { return encode_xyzc_impl(c, m, plane, dst, capacity, nbytes, false); }
+int wass_mesh_encode_xyzc_async(wass_ctx* c, wass_mesh* m, const double plane[4], void* dst, size_t capacity, size_t* nbytes) { return encode_xyzc_impl(c, m, plane, dst, capacity, nbytes, true); }
 
 // np.nanmean over planes.txt rows (wassgridsurface.py:672-678): a row counts if none of its entries is NaN
 // ("nan nan nan nan" is the only way wass_stereo writes NaN, wass_stereo.cpp:2104-2106)

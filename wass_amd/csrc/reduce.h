@@ -14,7 +14,7 @@
 //   - loops of these very shapes that keep their own text because the kernel compiled to other instructions when it called this
 //     header (other registers and schedule, the same values), and the kernels of the frame tail are held to the instruction:
 //     in mesh.hip k_ransac_score (a butterfly over six values), k_ransac_pick, block_sum_store's wave sums (k_refine_cov_dev),
-//     k_inl_text_format's scan, xyzc_limits_body, k_scan_blocks, the key folds of k_crop_limits_counts_dev and k_frame_header;
+//     k_inl_text_format's scan, k_scan_blocks, the key folds of k_crop_limits_counts_dev and k_frame_header;
 //     epipolar.hip's k_epi_best (block_tree cost it a register and six instructions); match.hip's arg-max butterfly in
 //     k_match_iidyn (two (value, index) pairs folded at once: no operation on one value); and the carry of jpeg.hip's
 //     block_excl_scan, which takes prefix and total in one pass over the waves (block_scan cost its kernels thirty instructions).
