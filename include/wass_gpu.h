@@ -607,6 +607,54 @@ int wass_grid_seq_finish(wass_grid_seq* seq, int force_zero_mean, wass_grid_seq_
 int wass_grid_seq_zero_mean_dev(wass_grid_seq* seq, float* d_z_mm, int n_frames);
 void wass_grid_seq_destroy(wass_grid_seq* seq);
 
+/* ---- row f3, --ia LinearND (wassgridsurface.py:437-482): Delaunay linear interpolation of the cloud (grid_linear.hip) --------
+ * The cloud (x_i, y_i, z_i), fp64, at the nodes of XX, YY = meshgrid(linspace(xmin, xmax, width), linspace(ymin, ymax, height)),
+ * the nodes computed as numpy computes linspace.  Points taken: xmin <= x <= xmax and ymin <= y <= ymax, closed (the reference's
+ * area_mask); a NaN or infinite coordinate drops the point; of several points with exactly the same (x, y) the lowest index
+ * stands.  out: height x width fp64; flags: height x width bytes:
+ *   0  the node lies in a triangle of three cloud points whose circumcircle holds no other point, both decided by fp64 orient and
+ *      incircle determinants beyond their rounding bounds (DESIGN.md "LinearND"); with the vertices by index i < j < k the value is
+ *      ((o_i z_i + o_j z_j) + o_k z_k) / ((o_i + o_j) + o_k), o_i = orient(P_j, P_k, q), o_j and o_k cyclically
+ *   1  the node is beyond an edge of the cloud's convex hull by more than the bound: NaN, scipy's fill_value
+ *   2  a triangle or a hull decision was found but not certified (cocircular points, collinear hull points, a node on a hull edge
+ *      within the bound): the value of the triangle found, or NaN
+ *   3  the walk reached its step cap (256): NaN
+ * counts[4] (may be NULL): nodes per flag.  Fewer than three points taken, or all of them collinear: every value NaN, every
+ * flag 1, WASS_ERR_TOO_FEW_POINTS.  WASS_ERR_INVALID_ARG: width or height < 1, xmax <= xmin with width > 1 (ymax, height likewise),
+ * null pointers.  Only xmin .. height of gs are read by the array entries; the mesh entry aligns the resident mesh first, as
+ * wass_mesh_grid_idw does (R, T, z negated, times the baseline).  Every entry runs on the context's stream, takes its scratch
+ * from the context (wass_grid_linear_scratch_bytes says how much for n points, without a GPU) and returns after the stream has
+ * run; the same input gives the same bits, in any order of the points once the indices are mapped. */
+typedef struct {
+    int max_walk_steps;             /* 0: 256                                                       */
+    int accel_w, accel_h;           /* cells of the acceleration grid, 0: about sqrt(n / 2) a side  */
+    int timing;                     /* != 0: fill ms_* of the info (three more events)              */
+} wass_linear_opts;
+typedef struct {
+    uint64_t counts[4];             /* nodes per flag                                               */
+    uint64_t n_taken;               /* points in the area, duplicates counted once                  */
+    int hull_vertices;              /* of the convex hull handed to the walk                        */
+    int hull_candidates;            /* points the device could not discard as interior              */
+    int accel_w, accel_h;
+    float ms_bucket, ms_hull, ms_walk;
+} wass_linear_info;
+int wass_grid_linear_dev(wass_ctx* ctx, const double* d_x, const double* d_y, const double* d_z, size_t n, const wass_grid_setup* gs,
+                         double* d_out_f64, uint8_t* d_flags, uint64_t* counts);
+int wass_grid_linear(wass_ctx* ctx, const double* x, const double* y, const double* z, size_t n, const wass_grid_setup* gs,
+                     double* out_f64, uint8_t* flags, uint64_t* counts);
+int wass_mesh_grid_linear(wass_ctx* ctx, const wass_mesh* mesh, const wass_grid_setup* gs, double* d_out_f64, uint8_t* d_flags,
+                          uint64_t* counts);
+int wass_grid_linear_scratch_bytes(size_t n, int width, int height, size_t* bytes);
+/* The device entries with the full record (info may be NULL) and options (opts may be NULL).  The record is what
+ * grid_sequence's linear_info needs beyond counts[4] (the points taken); the options are there for the tests (the step cap, the
+ * pitch of the acceleration grid) and for scripts/time_linear_nd.py (timing), and no caller should depend on them: with accel_w or
+ * accel_h set the call takes its scratch for THAT grid (cnt, off, fill: 12 bytes per cell), which
+ * wass_grid_linear_scratch_bytes, stating the default grid, does not count. */
+int wass_grid_linear_dev_ex(wass_ctx* ctx, const double* d_x, const double* d_y, const double* d_z, size_t n, const wass_grid_setup* gs,
+                            const wass_linear_opts* opts, double* d_out_f64, uint8_t* d_flags, wass_linear_info* info);
+int wass_mesh_grid_linear_ex(wass_ctx* ctx, const wass_mesh* mesh, const wass_grid_setup* gs, const wass_linear_opts* opts,
+                             double* d_out_f64, uint8_t* d_flags, wass_linear_info* info);
+
 /* Grid set-up (wassgridsurface.py:57-231, `--action setup`): the one step with real work in it, np.quantile over the heights of
  * the first frame's aligned cloud (:122-123), as exact order statistics on the device (grid_setup.hip).
  * wass_quantiles_f64_dev: out[i] = np.quantile(values, q[i]) (method "linear") over n doubles of device memory, i < nq, 1 <= nq <= 8,

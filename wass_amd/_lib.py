@@ -78,6 +78,17 @@ class GridSeqStats(C.Structure):
     _fields_ = [("zmin", C.c_double), ("zmax", C.c_double), ("zmean", C.c_double), ("n_frames", C.c_int)]
 
 
+class LinearOpts(C.Structure):
+    """wass_linear_opts"""
+    _fields_ = [("max_walk_steps", C.c_int), ("accel_w", C.c_int), ("accel_h", C.c_int), ("timing", C.c_int)]
+
+
+class LinearInfo(C.Structure):
+    """wass_linear_info"""
+    _fields_ = [("counts", C.c_uint64 * 4), ("n_taken", C.c_uint64), ("hull_vertices", C.c_int), ("hull_candidates", C.c_int),
+                ("accel_w", C.c_int), ("accel_h", C.c_int), ("ms_bucket", C.c_float), ("ms_hull", C.c_float), ("ms_walk", C.c_float)]
+
+
 class Geom(C.Structure):
     """wass_geom"""
     _fields_ = [("K_left", C.c_double * 9), ("K_right", C.c_double * 9), ("R", C.c_double * 9), ("T", C.c_double * 3),
@@ -220,6 +231,13 @@ SYMBOLS = {
     "wass_grid_seq_finish": (_i, [_vp, _i, C.POINTER(GridSeqStats), _vp, _vp, _vp, _vp]),
     "wass_grid_seq_zero_mean_dev": (_i, [_vp, _vp, _i]),
     "wass_grid_seq_destroy": (None, [_vp]),
+    "wass_grid_linear_dev": (_i, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(GridSetup), _vp, _vp, C.POINTER(C.c_uint64)]),
+    "wass_grid_linear": (_i, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(GridSetup), _vp, _vp, C.POINTER(C.c_uint64)]),
+    "wass_mesh_grid_linear": (_i, [_vp, _vp, C.POINTER(GridSetup), _vp, _vp, C.POINTER(C.c_uint64)]),
+    "wass_grid_linear_scratch_bytes": (_i, [C.c_size_t, _i, _i, C.POINTER(C.c_size_t)]),
+    "wass_grid_linear_dev_ex": (_i, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(GridSetup), C.POINTER(LinearOpts), _vp, _vp,
+                                     C.POINTER(LinearInfo)]),
+    "wass_mesh_grid_linear_ex": (_i, [_vp, _vp, C.POINTER(GridSetup), C.POINTER(LinearOpts), _vp, _vp, C.POINTER(LinearInfo)]),
     "wass_quantiles_f64_dev": (_i, [_vp, _vp, _sz, C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "wass_mesh_aligned_z_quantiles": (_i, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double), _i,
                                            C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

@@ -122,6 +122,7 @@ struct wass_ctx {
     wass::Buf rs_r, rs_l;          // DENSE_SCALE != 1: resized SGBM inputs
     wass::Buf raw2;                // speckle filter: median-filtered padded disparity
     wass::Buf grid;                // wass_mesh_grid_idw: accumulators and maps of the surface grid (grid.hip)
+    wass::Buf linear;              // wass_grid_linear*: the bucketed cloud, the hull and the staging of the LinearND interpolator (grid_linear.hip)
     wass::Buf dct, dct_io;         // wass_grid_dct*: bases, state and partial slabs of the solve / host-pointer staging (grid_dct.hip)
     wass::Buf scratch;             // mesh stages: labels / candidates / partial sums / block counts (mesh_layout.h), one phase after the other
     wass::FrameTail ft;            // the frame tail: records, events, pinned blocks and buffers of the chain behind the SGM call (mesh_tail.h)

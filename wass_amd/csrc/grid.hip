@@ -16,13 +16,9 @@
 //           segment; the result does not depend on the point order either.  Everything after that (the 5x5 inverse-
 // distance convolution, the 5x5 morphological closing of the mask) follows IDWInterpolator literally, in fp64.
 #include "common.h"
+#include "grid_align.h"
 
 namespace wass {
-
-struct GridDev {
-    double R[9], T[3], baseline, xmin, ymin, xext, yext, wm1, hm1;      // xext = xmax - xmin, wm1 = W - 1
-    int gw, gh;
-};
 
 constexpr unsigned int GRID_OUTSIDE = 0xFFFFFFFFu;
 
@@ -33,9 +29,8 @@ constexpr unsigned int GRID_OUTSIDE = 0xFFFFFFFFu;
 // the neighbouring cell (tests/test_grid_bin.py counts them).
 __device__ __forceinline__ unsigned int grid_align_bin(const GridDev& g, double x, double y, double z, double& az)
 {
-    const double ax = (g.R[0] * x + g.R[1] * y + g.R[2] * z + g.T[0]) * g.baseline;
-    const double ay = (g.R[3] * x + g.R[4] * y + g.R[5] * z + g.T[1]) * g.baseline;
-    az = -(g.R[6] * x + g.R[7] * y + g.R[8] * z + g.T[2]) * g.baseline;
+    double ax, ay;
+    grid_align(g, x, y, z, ax, ay, az);
     const double fx = floor((ax - g.xmin) / g.xext * g.wm1 + 0.5), fy = floor((ay - g.ymin) / g.yext * g.hm1 + 0.5);
     if (!(fx >= 0 && fx < g.gw && fy >= 0 && fy < g.gh)) return GRID_OUTSIDE;
     return (unsigned int)((size_t)fy * g.gw + (size_t)fx);
@@ -83,6 +78,10 @@ __global__ void __launch_bounds__(1024) k_grid_scan(const unsigned int* __restri
     lds_scan<1024>(part);
     unsigned int run = part[threadIdx.x] - s;                // exclusive prefix of this thread's chunk
     for (size_t i = a; i < b; ++i) { off[i] = run; run += cnt[i]; }
+}
+void grid_scan_enqueue(const unsigned int* cnt, size_t ng, unsigned int* off, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, s, cnt, ng, off);
 }
 // pass 2: every point into its cell's segment (the order inside a segment depends on the atomics; the median does not)
 __global__ void __launch_bounds__(256) k_grid_bucket_fill(const unsigned int* __restrict__ pcell, const double* __restrict__ pz, size_t n,

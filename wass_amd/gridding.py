@@ -14,6 +14,9 @@ With refine=RefineOptions(...) every frame's surface is also refined against its
 reference's grid() has the call commented out: after the filter, before the statistics.
 load_camera_mesh(path) is the reference's mesh_cam.xyzC reader (wass_utils.py:22-35).
 
+linear_nd(points, gridsetup) is `--ia LinearND` (wassgridsurface.py:437-482): the plane through the three cloud points of the
+Delaunay triangle that holds a node, without a triangulation being built; grid_sequence(..., algorithm="LinearND") runs it per frame.
+
 setup_grid(wdir, meanplane, baseline, ...) is the tool's `--action setup` (wassgridsurface.py:57-231): the dict of its config.mat
 from the first frame of a sequence, with the quantiles of the aligned heights taken on the GPU; generate_gridconfig / read_gridconfig
 are `--action generateconfig` and the reader of that file.  `python -m wass_amd.gridding WORKDIR OUTDIR --action ...` runs them
@@ -98,15 +101,136 @@ class GridSequenceResult:
     frame_min: np.ndarray
     frame_max: np.ndarray
     refine_losses: list | None = None   # with refine: per frame the first and the last row [steps, data, smoothness, energy]
+    linear_info: list | None = None     # LinearND: per frame {"counts": nodes per flag 0 .. 3, "n_taken": points taken}; None for DCT
 
 
 def _scalar(v) -> float:
     return float(np.ravel(np.asarray(v))[0])
 
 
+def _grid_setup_of(gridsetup):
+    """(wass_grid_setup, H, W) of a mapping with the reference's config.mat keys or the path of that file"""
+    if isinstance(gridsetup, (str, os.PathLike)):
+        import scipy.io
+        gridsetup = scipy.io.loadmat(os.fspath(gridsetup))
+    if "XX" in gridsetup:
+        H, W = np.asarray(gridsetup["XX"]).shape
+    else:
+        W, H = int(_scalar(gridsetup["Nx"])), int(_scalar(gridsetup["Ny"]))
+    gs = grid_setup(gridsetup["Rpl"], gridsetup["Tpl"], _scalar(gridsetup["CAM_BASELINE"]), _scalar(gridsetup["xmin"]),
+                    _scalar(gridsetup["xmax"]), _scalar(gridsetup["ymin"]), _scalar(gridsetup["ymax"]), W, H)
+    return gs, H, W
+
+
+def linear_nd(points, gridsetup_or_gs, ctx: Context | None = None, return_flags: bool = False, **options):
+    """wassgridsurface --ia LinearND (:437-482): the cloud interpolated linearly over its Delaunay triangulation at the nodes of
+    XX, YY = meshgrid(linspace(xmin, xmax, W), linspace(ymin, ymax, H)), what scipy.interpolate.LinearNDInterpolator(points[:2].T,
+    points[2])(XX, YY) returns, without a triangulation being built (grid_linear.hip, DESIGN.md "LinearND").
+    points: a 3 x N array (x, y, z rows, already aligned on the sea plane and in metres, as the reference's mesh_aligned) or a
+    tuple of three float64 device tensors; gridsetup_or_gs: a wass_grid_setup (stereo.grid_setup; only the extent and the size are
+    read), a mapping with the reference's config.mat keys, or the path of that file.  Points outside the closed extent, with a NaN
+    or infinite coordinate, and all but the lowest index of equal (x, y) are not taken.
+    Returns the float64 H x W surface; with return_flags also the uint8 H x W flags and the info dict of Context.grid_linear_dev:
+      0  the node lies in a triangle whose circumcircle holds no other point, certified by fp64 determinants beyond their rounding
+         bounds: the value is the plane through its three points
+      1  certainly outside the convex hull: NaN (scipy's fill_value); also everywhere when fewer than three points are taken or
+         all are collinear (info["status"] == -6)
+      2  a triangle or a hull decision was found but not certified (cocircular points, a node on a hull edge within the
+         bound): the value of the triangle found, or NaN.  grid_sequence keeps these values in the cube
+      3  the walk reached its step cap: NaN, in the cube too."""
+    import torch
+    from . import _lib
+    gs = gridsetup_or_gs if isinstance(gridsetup_or_gs, _lib.GridSetup) else _grid_setup_of(gridsetup_or_gs)[0]
+    if ctx is None:
+        ctx = Context(0)
+    dev = torch.device("cuda", ctx.device_id)
+    if isinstance(points, (tuple, list)) and len(points) == 3 and all(isinstance(t, torch.Tensor) for t in points):
+        d_x, d_y, d_z = points
+    else:
+        pts = np.asarray(points, np.float64)
+        if pts.ndim != 2 or pts.shape[0] != 3:
+            raise ValueError("points: a 3 x N array expected")
+        d_x, d_y, d_z = (torch.from_numpy(np.ascontiguousarray(pts[k])).to(dev) for k in range(3))
+    d_out = torch.empty((gs.height, gs.width), dtype=torch.float64, device=dev)
+    d_flags = torch.empty((gs.height, gs.width), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)                                  # the tensors are used on the context's stream from here on
+    info = ctx.grid_linear_dev(d_x, d_y, d_z, gs, d_out, d_flags, **options)
+    out = d_out.cpu().numpy()
+    return (out, d_flags.cpu().numpy(), info) if return_flags else out
+
+
+def _zero_mean_pass(ctx, seq, out, nb_max):
+    """--force-zero-mean after seq.finish: the cube goes through seq.zero_mean_dev in slices of nb_max frames"""
+    import torch
+    count, H, W = out.shape
+    dev = torch.device("cuda", ctx.device_id)
+    d_mm = torch.empty((nb_max, H, W), dtype=torch.float32, device=dev)
+    for i0 in range(0, count, nb_max):
+        nb = min(nb_max, count - i0)
+        d_mm[:nb].copy_(torch.from_numpy(np.ascontiguousarray(out[i0:i0 + nb])))
+        torch.cuda.synchronize(dev)
+        seq.zero_mean_dev(d_mm[:nb])
+        ctx.synchronize()
+        out[i0:i0 + nb] = d_mm[:nb].cpu().numpy()
+
+
+def _sequence_result(frames, fps, out, st, **more) -> GridSequenceResult:
+    count = len(frames)
+    idx = np.arange(count, dtype=np.float64)
+    workdir = np.array([int(os.path.basename(os.path.normpath(f))[:-3]) for f in frames], np.int64)
+    return GridSequenceResult(Z=out, time=idx / fps if fps > 0 else np.zeros(count), workdir=workdir, zmin=st["zmin"], zmax=st["zmax"],
+                              zmean=st["zmean"], mean_perpoint_mm=st["mean_perpoint_mm"], frame_mean=st["frame_mean"],
+                              frame_min=st["frame_min"], frame_max=st["frame_max"], **more)
+
+
+def _grid_sequence_linear(frames, gs, H, W, fps, user_mask, force_zero_mean, ctx, out) -> GridSequenceResult:
+    """The LinearND branch of grid_sequence: per frame load, upload, Mesh.grid_linear_dev, one rounding to float32, push; it shares
+    with the DCT branch the sequence handle's statistics, the zero-mean pass and the result."""
+    import torch
+    dev = torch.device("cuda", ctx.device_id)
+    d_out = torch.empty((H, W), dtype=torch.float64, device=dev)
+    d_flags = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    d_zi, d_mm = torch.empty((1, H, W), dtype=torch.float32, device=dev), torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    d_off = None
+    if user_mask is not None:
+        d_off = torch.from_numpy(~(np.asarray(user_mask).reshape(H, W) > 0)).to(dev)
+    torch.cuda.synchronize(dev)                                  # from here on the buffers are used on the context's stream
+    infos, empty = [], []
+    seq = GridSequence(ctx, W, H)
+    try:
+        for i, d in enumerate(frames):
+            mesh = upload_camera_mesh(ctx, load_camera_mesh(os.path.join(d, "mesh_cam.xyzC")))
+            try:
+                info = mesh.grid_linear_dev(gs, d_out, d_flags)  # returns after the stream has run
+            finally:
+                mesh.close()
+            d_zi[0] = d_out.to(torch.float32)                    # the one rounding fp64 -> float32; flag-3 cells are NaN already
+            if d_off is not None:
+                d_zi[0][d_off] = float("nan")
+            torch.cuda.synchronize(dev)
+            seq.push_dev(d_zi, d_mm)
+            out[i] = d_mm[0].cpu().numpy()
+            infos.append({"counts": info["counts"], "n_taken": info["n_taken"]})
+            if info["status"] != 0:
+                empty.append(i)
+        st = seq.finish(force_zero_mean)
+        if force_zero_mean:
+            _zero_mean_pass(ctx, seq, out, 1)
+    finally:
+        seq.close()
+    return _sequence_result(frames, fps, out, st, dct_info=[], empty_frames=empty, linear_info=infos)
+
+
 def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_options=None, force_zero_mean: bool = False,
-                  batch: int = 8, cell: str = "median", ctx: Context | None = None, out=None, refine=None) -> GridSequenceResult:
-    """wassgridsurface --action grid with --ia DCT on the GPU.  wass_frames: the NNNNNN_wd directories in sequence order (each
+                  batch: int = 8, cell: str = "median", ctx: Context | None = None, out=None, refine=None,
+                  algorithm: str = "DCT") -> GridSequenceResult:
+    """wassgridsurface --action grid with --ia DCT (the default) or --ia LinearND on the GPU.  algorithm="LinearND": every frame
+    goes through load, upload and Mesh.grid_linear_dev (linear_nd has the definition and the flags), is rounded once from fp64 to
+    float32 and pushed like a DCT frame; the cube keeps the values of flag-2 cells and holds NaN at flag-1 and flag-3 cells.
+    linear_info has per frame the nodes per flag and the points taken, dct_info is empty, empty_frames lists the frames with fewer
+    than three points (or all collinear).  The reference applies neither the user mask nor --mf in this branch: here user_mask is
+    applied (cells to NaN), and mf != 0 or refine raise ValueError.  alg_options, batch and cell are not used.
+    What follows describes algorithm="DCT".  wass_frames: the NNNNNN_wd directories in sequence order (each
     holds mesh_cam.xyzC); gridsetup: a mapping with the reference's config.mat keys (Rpl, Tpl, CAM_BASELINE, xmin, xmax, ymin,
     ymax, XX or Nx and Ny, fps) or the path of that file; mf: 0, 3 or 5 (--mf); user_mask: height x width, cells where it is 0
     become NaN; alg_options: the DCT options by the reference's names; batch: frames per DCT solve -- 8 by default: in the
@@ -121,19 +245,20 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
     if isinstance(gridsetup, (str, os.PathLike)):
         import scipy.io
         gridsetup = scipy.io.loadmat(os.fspath(gridsetup))
-    if "XX" in gridsetup:
-        H, W = np.asarray(gridsetup["XX"]).shape
-    else:
-        W, H = int(_scalar(gridsetup["Nx"])), int(_scalar(gridsetup["Ny"]))
+    gs, H, W = _grid_setup_of(gridsetup)
     fps = _scalar(gridsetup["fps"]) if "fps" in gridsetup else 0.0
-    gs = grid_setup(gridsetup["Rpl"], gridsetup["Tpl"], _scalar(gridsetup["CAM_BASELINE"]), _scalar(gridsetup["xmin"]),
-                    _scalar(gridsetup["xmax"]), _scalar(gridsetup["ymin"]), _scalar(gridsetup["ymax"]), W, H)
     frames = [os.fspath(f) for f in wass_frames]
     count, batch = len(frames), max(1, int(batch))
     if count == 0:
         raise ValueError("no frames")
     if mf not in (0, 3, 5):
         raise ValueError(f"mf = {mf}: 0, 3 or 5 (cv.medianBlur, which the reference calls, takes no other size for float32)")
+    if algorithm not in ("DCT", "LinearND"):
+        raise ValueError(f"algorithm = {algorithm!r}: DCT or LinearND")
+    linear = algorithm == "LinearND"
+    if linear and (mf != 0 or refine is not None):
+        raise ValueError("algorithm LinearND takes neither mf nor refine: the reference's LinearND branch applies no median filter "
+                         "and no refinement")
     if out is None:
         out = np.empty((count, H, W), np.float32)
     elif out.shape != (count, H, W) or out.dtype != np.float32:
@@ -143,6 +268,8 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
         pictures = _refine_inputs(frames, gridsetup, H, W)       # raises before anything touches the device
     if ctx is None:
         ctx = Context(0)
+    if linear:
+        return _grid_sequence_linear(frames, gs, H, W, fps, user_mask, force_zero_mean, ctx, out)
     dev = torch.device("cuda", ctx.device_id)
     nb_max = min(batch, count)
     d_cells = torch.empty((nb_max, H, W), dtype=torch.float32, device=dev)
@@ -191,22 +318,12 @@ def grid_sequence(wass_frames, gridsetup, mf: int = 0, user_mask=None, alg_optio
                 empty += [i0 + k for k in range(nb) if status[k] != 0]
         st = seq.finish(force_zero_mean)
         if force_zero_mean:
-            for i0 in range(0, count, batch):
-                nb = min(batch, count - i0)
-                d_mm[:nb].copy_(torch.from_numpy(np.ascontiguousarray(out[i0:i0 + nb])))
-                torch.cuda.synchronize(dev)
-                seq.zero_mean_dev(d_mm[:nb])
-                ctx.synchronize()
-                out[i0:i0 + nb] = d_mm[:nb].cpu().numpy()
+            _zero_mean_pass(ctx, seq, out, nb_max)
     finally:
         seq.close()
         if refiner is not None:
             refiner.close()
-    idx = np.arange(count, dtype=np.float64)
-    workdir = np.array([int(os.path.basename(os.path.normpath(f))[:-3]) for f in frames], np.int64)
-    return GridSequenceResult(Z=out, time=idx / fps if fps > 0 else np.zeros(count), workdir=workdir, zmin=st["zmin"], zmax=st["zmax"],
-                              zmean=st["zmean"], mean_perpoint_mm=st["mean_perpoint_mm"], dct_info=infos, empty_frames=empty,
-                              frame_mean=st["frame_mean"], frame_min=st["frame_min"], frame_max=st["frame_max"], refine_losses=traces)
+    return _sequence_result(frames, fps, out, st, dct_info=infos, empty_frames=empty, refine_losses=traces)
 
 
 REFINE_KEYS = ("Rpl", "Tpl", "CAM_BASELINE", "P0cam", "P1cam", "XX", "YY")

@@ -482,6 +482,26 @@ class Context(_Handle):
                                                      qa.ctypes.data_as(dp), qa.size, out.ctypes.data_as(dp)))
         return out
 
+    def grid_linear_dev(self, d_x, d_y, d_z, gs: "_lib.GridSetup", d_out, d_flags, max_walk_steps: int = 0, accel=None, timing: bool = False):
+        """The LinearND interpolator on device tensors (wass_grid_linear_dev_ex): the cloud d_x, d_y, d_z (float64, n each) at the
+        nodes of gs into d_out (float64 height x width) and d_flags (uint8 height x width); see linear_nd for the flags.  Only
+        xmin .. height of gs are read.  max_walk_steps (0: 256) and accel (None or (cells along x, cells along y) of the
+        acceleration grid) are there for tests and measurements; the result does not depend on accel.  Returns after the stream
+        has run, with a dict: counts (nodes per flag), n_taken, status (0, or -6: fewer than three points or all collinear, the
+        surface is NaN), hull_vertices, hull_candidates, accel, and with timing the milliseconds of bucket, hull and walk."""
+        n = int(d_x.numel())
+        for t in (d_x, d_y, d_z):
+            if t.dtype != d_out.dtype or not t.is_contiguous() or t.numel() != n:
+                raise ValueError("d_x, d_y, d_z: contiguous float64 tensors of one length expected")
+        if tuple(d_out.shape) != (gs.height, gs.width) or tuple(d_flags.shape) != (gs.height, gs.width) or not d_out.is_contiguous() \
+                or not d_flags.is_contiguous() or d_out.element_size() != 8 or d_flags.element_size() != 1:
+            raise ValueError("d_out: contiguous float64 height x width, d_flags: contiguous uint8 height x width expected")
+        opts, info = _linear_opts(max_walk_steps, accel, timing), _lib.LinearInfo()
+        rc = self._check(self._lib.wass_grid_linear_dev_ex(self._h, d_x.data_ptr() if n else None, d_y.data_ptr() if n else None,
+                                                           d_z.data_ptr() if n else None, n, C.byref(gs), C.byref(opts), d_out.data_ptr(),
+                                                           d_flags.data_ptr(), C.byref(info)), allow=(-6,))
+        return _linear_info(info, rc, timing)
+
     def mesh_upload(self, valid, p3d, gray=None):
         valid = np.ascontiguousarray(valid, np.uint8)
         p3d = np.ascontiguousarray(p3d, np.float64)
@@ -592,6 +612,29 @@ def grid_setup(R, T, baseline: float, xmin: float, xmax: float, ymin: float, yma
     return gs
 
 
+def _linear_opts(max_walk_steps, accel, timing):
+    o = _lib.LinearOpts()
+    o.max_walk_steps, o.timing = int(max_walk_steps), int(bool(timing))
+    o.accel_w, o.accel_h = (0, 0) if accel is None else (int(accel[0]), int(accel[1]))
+    return o
+
+
+def _linear_info(info, rc, timing):
+    d = {"counts": [int(v) for v in info.counts], "n_taken": int(info.n_taken), "status": int(rc), "hull_vertices": info.hull_vertices,
+         "hull_candidates": info.hull_candidates, "accel": (info.accel_w, info.accel_h)}
+    if timing:
+        d.update(ms_bucket=info.ms_bucket, ms_hull=info.ms_hull, ms_walk=info.ms_walk)
+    return d
+
+
+def linear_scratch_bytes(n: int, width: int, height: int) -> int:
+    """wass_grid_linear_scratch_bytes: the context's device memory for a LinearND call on n points; no GPU needed."""
+    b = C.c_size_t()
+    if _lib.load().wass_grid_linear_scratch_bytes(int(n), int(width), int(height), C.byref(b)) != 0:
+        raise ValueError("linear_scratch_bytes: bad sizes")
+    return int(b.value)
+
+
 def quantiles_launch_shape():
     """(elements one workgroup takes per sweep, elements one launch takes per sweep) of the quantile selection (grid_setup.hip)."""
     a, b = C.c_int(), C.c_int()
@@ -700,6 +743,17 @@ class Mesh(_Handle):
             raise ValueError("d_cells: a contiguous float32 height x width tensor expected")
         self.ctx._check(self.ctx._lib.wass_mesh_grid_cells_dev(self.ctx._h, self._h, C.byref(gs), {"mean": 0, "median": 1}[cell],
                                                                d_cells.data_ptr()))
+
+    def grid_linear_dev(self, gs: "_lib.GridSetup", d_out, d_flags, max_walk_steps: int = 0, accel=None, timing: bool = False):
+        """The LinearND interpolator from the resident mesh (wass_mesh_grid_linear_ex): the valid points aligned like grid_cells_dev
+        aligns them (gs.R, gs.T, z negated, times the baseline), then Context.grid_linear_dev; the same dict comes back."""
+        if tuple(d_out.shape) != (gs.height, gs.width) or tuple(d_flags.shape) != (gs.height, gs.width) or not d_out.is_contiguous() \
+                or not d_flags.is_contiguous() or d_out.element_size() != 8 or d_flags.element_size() != 1:
+            raise ValueError("d_out: contiguous float64 height x width, d_flags: contiguous uint8 height x width expected")
+        opts, info = _linear_opts(max_walk_steps, accel, timing), _lib.LinearInfo()
+        rc = self.ctx._check(self.ctx._lib.wass_mesh_grid_linear_ex(self.ctx._h, self._h, C.byref(gs), C.byref(opts), d_out.data_ptr(),
+                                                                    d_flags.data_ptr(), C.byref(info)), allow=(-6,))
+        return _linear_info(info, rc, timing)
 
     def aligned_z_quantiles(self, R, T, baseline: float, q):
         """np.quantile of the heights of the valid points after the alignment on the sea plane, z = -(R[2] . p + T[2]) * baseline
