@@ -150,11 +150,12 @@ def disparity_postprocess(d16, mindisp, num_disp, disp_offset=0, dilate_steps=1,
     return out
 
 
-def clahe(img, clip_limit, tiles):
+def clahe(img, clip_limit, tiles, tiles_y=None):
+    """tiles columns by tiles_y rows of tiles (square when tiles_y is None)"""
     img = np.ascontiguousarray(img, np.uint8)
     out = np.empty_like(img)
-    rc = lib().orc_clahe(_p(img, C.c_uint8), img.shape[1], img.shape[0], C.c_size_t(img.shape[1]), C.c_double(clip_limit), tiles, tiles,
-                         _p(out, C.c_uint8))
+    rc = lib().orc_clahe(_p(img, C.c_uint8), img.shape[1], img.shape[0], C.c_size_t(img.shape[1]), C.c_double(clip_limit), int(tiles),
+                         int(tiles if tiles_y is None else tiles_y), _p(out, C.c_uint8))
     assert rc == 0
     return out
 

@@ -105,6 +105,18 @@ def other_cases():
                           ("shift", 200, 120, np.array([[1, 0, 7.0], [0, 1, -3.0], [0, 0, 1.0]])),
                           ("zoom", 260, 180, np.array([[1.3, 0.0, -30.0], [0.0, 1.3, -20.0], [0, 0, 1.0]]))):
         out.append(dict(name=f"warp_{name}", kind="warp", H=Hm, src=_texture(w, h, 21)))
+    # the horizons of tests/prepare_probes.py: the denominator reaches 0 exactly, comes within 2^-30 of it, and does so in a 300 x 5
+    # destination, whose blocks are 204 columns wide; H = inv(M), M given from the destination to the source
+    for name, M, dsize in (("horizon_zero", [[.5, 0, 0], [0, 1, 0], [-1 / 128, 0, 1]], (160, 40)),
+                           ("horizon_tiny", [[.5, 0, 0], [0, 1, 0], [-1 / 128, 0, 1 + 2.0 ** -30]], (160, 40)),
+                           ("horizon_204", [[.5, 0, 3], [0, .75, 2], [-1 / 128, 0, 1]], (300, 5))):
+        out.append(dict(name=f"warp_{name}", kind="warp", H=np.linalg.inv(np.array(M)), dsize=dsize, src=np.maximum(_texture(97, 61, 22), 1)))
+    # calibrated camera matrices: (fx fy) * (1 / (fx fy)) != 1 in fp64, so the normalised coordinates are divided by a _w that is not 1
+    for name, fx, fy, cx, cy, w, h in (("diag1234", 1234.5, 1234.5, 44.7, 35.2, 90, 70), ("f3366", 3366.3, 1714.0, 2499.7, 2.3, 5000, 5),
+                                       ("f3783", 3783.4, 1290.5, 128.6, 16.2, 258, 33), ("f1107", 1107.9, 3746.7, 33.1, 20.6, 64, 48),
+                                       ("short", 77.7, 80.3, 44.7, 35.2, 90, 70)):
+        K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
+        out.append(dict(name=f"undistort_K_{name}", kind="undistort", K=K, dist=np.array([-0.25, 0.08, 0.002, -0.001, 0.01]), src=_texture(w, h, 32)))
     for name, w, h, dist in (("k1k2", 320, 240, [-0.21, 0.09, 0.0, 0.0]), ("5coef", 400, 300, [-0.28, 0.11, 1e-3, -7e-4, -0.02]),
                              ("8coef", 300, 220, [0.1, -0.05, 5e-4, 2e-4, 0.01, 0.02, -0.01, 0.003]), ("tall", 5000 // 32, 300, [-0.1, 0.02, 0, 0])):
         K = np.array([[0.9 * w, 0, w / 2 + 3.0], [0, 0.92 * w, h / 2 - 2.0], [0, 0, 1.0]])
@@ -146,7 +158,7 @@ def run_other(cv2, c):
                     left_rect=cv2.remap(c["left"], mx1, my1, cv2.INTER_CUBIC), right_rect=cv2.remap(c["right"], mx2, my2, cv2.INTER_CUBIC))   # :603-604
     if k == "warp":
         h, w = c["src"].shape
-        return dict(dst=cv2.warpPerspective(c["src"], c["H"], (w, h)))                                       # :515-516
+        return dict(dst=cv2.warpPerspective(c["src"], c["H"], c.get("dsize", (w, h))))                       # :515-516
     if k == "undistort":
         return dict(dst=cv2.undistort(c["src"], c["K"], c["dist"]))                                          # wass_prepare.cpp:268
     if k == "clahe":

@@ -66,7 +66,8 @@ def _inv3(m):
 
 def undistort_map(w, h, K, dist):
     """(iu, iv) int64 [h, w]: where cv::undistort reads, in 1/32 pixel.  Stripes of max(1, 4096 / w) rows, the principal point shifted
-    by the stripe's origin, the column value an accumulated sum, the polynomial in fp64, round to nearest even."""
+    by the stripe's origin, the column value an accumulated sum, both divided by _w = ir[8] (which need not be 1 for a calibrated K), the
+    polynomial in fp64, round to nearest even."""
     K = np.asarray(K, np.float64).reshape(3, 3)
     k = np.zeros(12)
     k[:len(np.ravel(dist))] = np.ravel(dist)
@@ -76,13 +77,13 @@ def undistort_map(w, h, K, dist):
         Ar = K.copy()
         Ar[1, 2] = K[1, 2] - y0
         ir = _inv3(Ar)
-        if y0 == 0:
-            _x = ir[2]
+        if y0 == 0:                                     # ir[0], ir[2], ir[8] are the same in every stripe
+            _x, ww = ir[2], 1.0 / ir[8]
             for j in range(w):
-                xs[j] = _x
+                xs[j] = _x * ww
                 _x += ir[0]
         for i in range(min(stripe0, h - y0)):
-            ys[y0 + i] = i * ir[4] + ir[5]
+            ys[y0 + i] = (i * ir[4] + ir[5]) * (1.0 / (i * ir[7] + ir[8]))
     x, y = np.meshgrid(xs, ys)
     x2, y2 = x * x, y * y
     r2, _2xy = x2 + y2, 2 * x * y

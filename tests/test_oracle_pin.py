@@ -74,7 +74,7 @@ def oracle_other(O, c):
                     mx2=mx2, my2=my2, left_rect=O.remap_cubic(c["left"], mx1, my1), right_rect=O.remap_cubic(c["right"], mx2, my2))
     if k == "warp":
         h, w = c["src"].shape
-        return dict(dst=O.warp_perspective(c["src"], c["H"], w, h))
+        return dict(dst=O.warp_perspective(c["src"], c["H"], *c.get("dsize", (w, h))))
     if k == "undistort":
         return dict(dst=O.undistort(c["src"], c["K"], list(c["dist"])))
     if k == "clahe":

@@ -392,13 +392,20 @@ int undistort_tables(wass_ctx* c, const double* K, int w, int h, const double** 
             memcpy(Ar, K, sizeof Ar);
             Ar[5] = K[5] - y0;
             if (!inv33(Ar, ir)) return set_err(c, WASS_ERR_INVALID_ARG, "singular camera matrix");
-            if (ir[1] != 0 || ir[3] != 0 || ir[6] != 0 || ir[7] != 0 || ir[8] != 1)
+            // ir[8] = (fx fy) * (1 / (fx fy)) need not be 1 in fp64: it is divided out below, as cv::undistort divides by _w
+            if (ir[1] != 0 || ir[3] != 0 || ir[6] != 0 || ir[7] != 0)
                 return set_err(c, WASS_ERR_UNSUPPORTED, "camera matrix with skew is not supported");
             if (y0 == 0) {
+                // ir[0], ir[2] and ir[8] do not depend on the stripe: Ar[5] enters them only through products with exact zeros,
+                // so the column table of stripe 0 is every stripe's
+                const double ww = 1. / ir[8];
                 double _x = ir[2];
-                for (int j = 0; j < w; ++j, _x += ir[0]) xy[j] = _x * (1. / 1.);
+                for (int j = 0; j < w; ++j, _x += ir[0]) xy[j] = _x * ww;
             }
-            for (int i = 0; i < stripe; ++i) xy[(size_t)w + y0 + i] = (i * ir[4] + ir[5]) * (1. / 1.);
+            for (int i = 0; i < stripe; ++i) {
+                const double ww = 1. / (i * ir[7] + ir[8]);
+                xy[(size_t)w + y0 + i] = (i * ir[4] + ir[5]) * ww;
+            }
         }
         wass_ctx::UndCache& e = c->und_cache[c->und_next];
         c->und_next ^= 1;
