@@ -747,6 +747,55 @@ int wass_spatial_filter_apply_dev(wass_spatial_filter* h, const float* d_frames,
                                   float* d_out, size_t out_stride_t, size_t out_stride_y);
 void wass_spatial_filter_destroy(wass_spatial_filter* h);
 
+/* ---- Wavenumber-frequency filter of the gridded cube (beyond the reference; DESIGN.md, "Dispersion filter"):
+ * out = real(ifftn(fftn(p) * H)) over the whole nt x ny x nx float32 cube, cell (t, y, x) at cube[t * stride_t + y * stride_y + x]
+ * (strides in elements), with the DFT stages of the spectrum on the f32 MFMA and a closing stage that makes the real part only.
+ *   prepare  m_c = the fp64 sum of the cell's samples that are not NaN, in frame order, divided by their count (0 for a cell that
+ *            is NaN throughout, and for every cell with WASS_KFILTER_NO_CENTRE); p = (float)((double)v - m_c), 0 for a NaN sample
+ *   H        real float32 in the un-shifted half layout of np.fft.rfftn, [nt][ny][nx / 2 + 1].  PRECONDITION: H is even,
+ *            H[f][ky][kx] == H[-f][-ky][kx] on the columns kx = 0 and, nx even, nx / 2; the other columns stand for their mirror
+ *            image as well.  The product is conj(X) * H * w / (nt ny nx) in fp64 with one rounding, w = 2 off those columns.
+ *   undo     out = (float)((double)y + m_c) with WASS_KFILTER_RESTORE_MEAN, else y; with WASS_KFILTER_KEEP_NAN a sample that was NaN
+ *            is NaN, without it it holds the filtered value; a cell that was NaN throughout is NaN either way
+ * An infinite sample is WASS_ERR_INVALID_ARG.  The same input gives the same bits on every run, for host and device memory.
+ * create: the handle owns about 3.6 f32 copies of the cube (wass_kfilter_scratch_bytes says how much, without a GPU);
+ * WASS_ERR_NO_MEMORY when that is more than 16 GiB or the allocation fails, WASS_ERR_INVALID_ARG for an axis outside 1 .. 8192.
+ * set_mask: H from the host.  set_shell: H made on the device from host maps given on the np.fft.fftshift-ed axes: omega[nt],
+ * kappa_x[nx], kappa_y[ny], sigma0[ny][nx] doubles and used[ny][nx] bytes.  H = 0 at frequency 0 and at the Nyquist index of every
+ * even axis.  A bin of positive frequency (un-shifted 1 <= f <= (nt - 1) / 2) at the shifted indices (p, i, j) is 1 if
+ * used[i][j] and f_lo <= omega[p] <= f_hi and |r| <= G, r = (omega[p] - sigma0[i][j]) - (kappa_x[j] * U + kappa_y[i] * V) in that
+ * order of operations, else 0; a bin of negative frequency takes the value of its mirror image (-f, -ky, -kx).  complement != 0
+ * exchanges 0 and 1 on the bins so decided.  f_lo and f_hi are compared with omega, in its units.  *n_pass (may be NULL) = the bins
+ * of the full cube with H = 1.  get_mask: H back to the host.
+ * apply: a host cube, returns with out filled; apply_dev: device memory (out may be the cube).  Both wait for the device, since
+ * *stats (may be NULL) comes from it: var_in and var_out are the mean squares of p and of the filtered field y over the samples
+ * that were not NaN (fp64 sums in a fixed order; NaN without such a sample). */
+enum { WASS_KFILTER_RESTORE_MEAN = 1, WASS_KFILTER_KEEP_NAN = 2, WASS_KFILTER_NO_CENTRE = 4 };
+typedef struct wass_kfilter_stats {
+    double var_in, var_out;
+    uint64_t n_nan;             /* NaN samples of the input */
+    uint64_t n_empty_cells;     /* cells that are NaN in every frame */
+} wass_kfilter_stats;
+typedef struct wass_kfilter wass_kfilter;
+int wass_kfilter_scratch_bytes(int nt, int ny, int nx, size_t* bytes);
+int wass_kfilter_create(wass_ctx* ctx, int nt, int ny, int nx, wass_kfilter** out);
+int wass_kfilter_set_mask(wass_kfilter* h, const float* H);
+int wass_kfilter_set_shell(wass_kfilter* h, const double* omega, const double* kappa_x, const double* kappa_y, const double* sigma0,
+                           const unsigned char* used, double U, double V, double G, double f_lo, double f_hi, int complement,
+                           uint64_t* n_pass);
+int wass_kfilter_get_mask(wass_kfilter* h, float* H);
+int wass_kfilter_apply(wass_kfilter* h, const float* cube, size_t stride_t, size_t stride_y, float* out, size_t out_stride_t,
+                       size_t out_stride_y, int flags, wass_kfilter_stats* stats);
+int wass_kfilter_apply_dev(wass_kfilter* h, const float* d_cube, size_t stride_t, size_t stride_y, float* d_out, size_t out_stride_t,
+                           size_t out_stride_y, int flags, wass_kfilter_stats* stats);
+/* Measuring: with set_timing(on != 0) every apply brackets its stages with events, also runs the full closing stage
+ * (k_dft_stage<true, true>, the spatial filter's last launch) on the same half spectrum just before k_dft_close, and waits for the
+ * device; the result is unchanged.  last_timings: ten floats, milliseconds of the last timed apply: upload + prepare, x, y, t, the
+ * product, t, y, the full closing stage, k_dft_close (+ the fold of its sums), the copy to out. */
+int wass_kfilter_set_timing(wass_kfilter* h, int on);
+int wass_kfilter_last_timings(wass_kfilter* h, float* stage_ms);
+void wass_kfilter_destroy(wass_kfilter* h);
+
 /* ---- Visibility map of the gridded cube: wasspost visibilitymap (wasspost.py:495-621, geometry.py:5-100) as an array function.
  * For every frame of a count x H x W float32 cube (cell (t, y, x) at in[t * stride_t + y * stride_y + x], strides in elements) and
  * every cell: zf = in * (float)datascale is the height in metres; the unit ray d from (XX, YY, zf) to the camera `origin` (grid

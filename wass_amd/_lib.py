@@ -15,6 +15,7 @@ SO_PATH = os.environ.get("WASS_GPU_LIB") or os.path.join(_HERE, "libwassgpu.so")
 
 WASS_OK = 0
 WASS_ERR_INVALID_ARG = -1
+WASS_ERR_NO_MEMORY = -3
 WASS_ERR_COST_OVERFLOW = -5
 
 
@@ -134,6 +135,11 @@ class PolPrepParams(C.Structure):
 class PolPrepOut(C.Structure):
     """wass_pol_prep_out"""
     _fields_ = [(n, C.c_void_p) for n in ("S", "image", "dolp", "aolp", "channels", "image_f32", "aolp_f32")] + [("ranges", C.c_float * 8)]
+
+
+class KFilterStatsC(C.Structure):
+    """wass_kfilter_stats"""
+    _fields_ = [("var_in", C.c_double), ("var_out", C.c_double), ("n_nan", C.c_uint64), ("n_empty_cells", C.c_uint64)]
 
 
 def default_sgm_params(num_disp: int, ndirs: int = 5, min_disp: int = 1, win: int = 13, p1_mult: int = 2,
@@ -258,6 +264,17 @@ SYMBOLS = {
     "wass_spatial_filter_apply": (_i, [_vp, _vp, _sz, _sz, _i, _vp, _sz, _sz]),
     "wass_spatial_filter_apply_dev": (_i, [_vp, _vp, _sz, _sz, _i, _vp, _sz, _sz]),
     "wass_spatial_filter_destroy": (None, [_vp]),
+    "wass_kfilter_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "wass_kfilter_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "wass_kfilter_set_mask": (_i, [_vp, _vp]),
+    "wass_kfilter_set_shell": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
+                                    C.POINTER(C.c_uint64)]),
+    "wass_kfilter_get_mask": (_i, [_vp, _vp]),
+    "wass_kfilter_apply": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, C.POINTER(KFilterStatsC)]),
+    "wass_kfilter_apply_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, C.POINTER(KFilterStatsC)]),
+    "wass_kfilter_set_timing": (_i, [_vp, _i]),
+    "wass_kfilter_last_timings": (_i, [_vp, C.POINTER(C.c_float * 10)]),
+    "wass_kfilter_destroy": (None, [_vp]),
     "wass_visibility_scratch_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i)]),
     "wass_visibility": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "wass_visibility_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),

@@ -771,3 +771,553 @@ extern "C" int wass_spatial_filter_apply_dev(wass_spatial_filter* h, const float
 {
     return spat_apply(h, false, d_frames, stride_t, stride_y, n_frames, d_out, out_stride_t, out_stride_y);
 }
+
+// ---- the wavenumber-frequency filter of the whole cube (beyond the reference; DESIGN.md, "Dispersion filter") -------------------
+// y = real(ifftn(fftn(p) * H)) over nt x ny x nx, p the cube minus every cell's time mean with its NaN samples at 0, H real and even,
+// f32, in the un-shifted half layout [nt][ny][ch] of np.fft.rfftn.  The stages above do the work:
+//   k_kf_prepare   cell mean (fp64, frame order), p, one bit per NaN sample, the counts and sum p^2
+//   x, y, t        k_dft_stage, as spec3d_run
+//   k_kf_mul       X -> conj(X) * H * w / (nt ny nx), the rule of k_spat_mul with the weight made on the fly from the f32 mask
+//   t, y           k_dft_stage again: H is even, so the inverse is the conjugate of the forward transform of the conjugate
+//   k_dft_close    x: complex half spectrum [row][kx] -> real [row][x].  Only the real accumulators of k_dft_stage<true, true>, in its k
+//                  order (the same bits), no imaginary plane stored anywhere; the tile goes through LDS so that a wave stores whole
+//                  256-byte pieces of rows; the epilogue adds the cell mean, puts the NaN samples back and sums y^2
+// k_kf_shell makes the dispersion-shell mask on the device from host maps: comparisons, one subtraction and two products, nothing else.
+// No atomic on a floating-point number anywhere: the same input gives the same bits.
+namespace wass {
+
+constexpr int KF_RESTORE_MEAN = 1, KF_KEEP_NAN = 2, KF_NO_CENTRE = 4;
+constexpr int KF_STAGES = 10;                           // upload + prepare, x, y, t, mul, t, y, (k_dft_stage<true, true>,) close, download
+constexpr int KF_CL_LD = 68;                            // LDS row pitch of k_dft_close's output tile: 16-byte aligned rows
+
+// One thread per cell, the frames in order, twice: the fp64 sum and count of the samples that are not NaN, then p and the bitmap.
+// bits[t * wpf + (cell >> 6)] bit (cell & 63) = sample (t, cell) is NaN: one wave's ballot is one word.  means[cell] = m_c, NaN for a
+// cell that is NaN throughout (it enters as zeros; k_dft_close reads the NaN as "empty").  part[block * 4 ..] = the block's sum of
+// p^2 over its samples that are not NaN, its NaN samples, its empty cells and its infinite samples, fp64 (exact for the counts).
+// src and out may be the same dense cube: a thread writes no element another thread reads.
+__global__ void __launch_bounds__(256) k_kf_prepare(const float* src, long long st, long long sy, int nt, int ny, int nx, int centre, float* out,
+                                                    double* __restrict__ means, unsigned long long* __restrict__ bits, int wpf,
+                                                    double* __restrict__ part)
+{
+    __shared__ double sh[256];
+    const int cells = ny * nx, i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < cells;
+    const float* p = src + (live ? (long long)(i / nx) * sy + (i % nx) : 0);
+    double sd = 0.0, ninf = 0.0;
+    int cnt = 0;
+    if (live)
+        for (int t = 0; t < nt; ++t) {
+            const float v = p[(long long)t * st];
+            if (!isnan(v)) { sd += (double)v; ++cnt; }
+            if (isinf(v)) ninf += 1.0;
+        }
+    const double m = cnt && centre ? sd / (double)cnt : 0.0;
+    if (live) means[i] = cnt ? m : (double)__builtin_nanf("");
+    double s2 = 0.0;
+    for (int t = 0; t < nt; ++t) {                       // every lane of the wave stays in the loop: the ballot needs them all
+        float r = 0.f;
+        bool nan = false;
+        if (live) {
+            const float v = p[(long long)t * st];
+            nan = isnan(v);
+            if (!nan) {
+                r = (float)((double)v - m);
+                s2 += (double)r * (double)r;
+            }
+            out[(size_t)t * cells + i] = r;
+        }
+        const unsigned long long b = __ballot(nan);
+        if ((threadIdx.x & 63) == 0 && i < cells) bits[(size_t)t * wpf + (i >> 6)] = b;
+    }
+    const double a0 = block_sum<256>(s2, sh), a1 = block_sum<256>(live ? (double)(nt - cnt) : 0.0, sh),
+                 a2 = block_sum<256>(live && !cnt ? 1.0 : 0.0, sh), a3 = block_sum<256>(ninf, sh);
+    if (threadIdx.x == 0) {
+        part[(size_t)blockIdx.x * 4 + 0] = a0;
+        part[(size_t)blockIdx.x * 4 + 1] = a1;
+        part[(size_t)blockIdx.x * 4 + 2] = a2;
+        part[(size_t)blockIdx.x * 4 + 3] = a3;
+    }
+}
+
+// dst[j] = the sum of part[i * nv + j] over i < npart, thread-strided then a tree; one block per j
+__global__ void __launch_bounds__(256) k_kf_fold(const double* __restrict__ part, size_t npart, int nv, double* __restrict__ dst)
+{
+    __shared__ double sh[256];
+    const int j = blockIdx.x;
+    double s = 0.0;
+    for (size_t i = threadIdx.x; i < npart; i += 256) s += part[i * nv + j];
+    s = block_sum<256>(s, sh);
+    if (threadIdx.x == 0) dst[j] = s;
+}
+
+struct ShellArgs {
+    const double* omega; const double* kap_x; const double* kap_y; const double* sigma0; const unsigned char* used;   // fftshifted axes
+    double U, V, G, lo, hi;
+    int nt, ny, nx, ch, complement;
+};
+
+// H[f][ky][kx] of the un-shifted half layout.  0 on the zero-frequency plane and on the Nyquist index of every even axis; a bin of
+// positive frequency (1 <= f <= (nt - 1) / 2) is decided at its own fftshifted indices (p, i, j) = (f + nt / 2, ..) mod n, one of negative
+// frequency at those of its mirror image (-f, -ky, -kx):  used[i][j] and lo <= omega[p] <= hi and |r| <= G,
+// r = (omega[p] - sigma0[i][j]) - (kap_x[j] U + kap_y[i] V), not contracted (the library is built with -ffp-contract=off).
+// count[0] += the bins of the FULL cube that pass (a column that stands for its mirror image counts twice): an integer atomic.
+__global__ void __launch_bounds__(256) k_kf_shell(const ShellArgs a, float* __restrict__ H, unsigned long long* __restrict__ count)
+{
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x, plane = (size_t)a.ny * a.ch;
+    unsigned n = 0;
+    if (q < (size_t)a.nt * plane) {
+        int f = (int)(q / plane), ky = (int)(q % plane) / a.ch, kx = (int)(q % plane) % a.ch;
+        const bool alone = kx == 0 || (a.nx % 2 == 0 && kx == a.nx / 2);
+        const bool nyq = (a.nt % 2 == 0 && f == a.nt / 2) || (a.ny % 2 == 0 && ky == a.ny / 2) || (a.nx % 2 == 0 && kx == a.nx / 2);
+        bool pass = false;
+        if (f != 0 && !nyq) {
+            if (f > a.nt / 2) {
+                f = a.nt - f;
+                ky = (a.ny - ky) % a.ny;
+                kx = (a.nx - kx) % a.nx;
+            }
+            const int p = (f + a.nt / 2) % a.nt, i = (ky + a.ny / 2) % a.ny, j = (kx + a.nx / 2) % a.nx;
+            const double w = a.omega[p], d = w - a.sigma0[(size_t)i * a.nx + j];
+            const double r = d - (a.kap_x[j] * a.U + a.kap_y[i] * a.V);
+            pass = a.used[(size_t)i * a.nx + j] && w >= a.lo && w <= a.hi && fabs(r) <= a.G;
+            if (a.complement) pass = !pass;
+        }
+        H[q] = pass ? 1.f : 0.f;
+        n = pass ? (alone ? 1u : 2u) : 0u;
+    }
+    n = wave_fold(n, [](unsigned x, unsigned y) { return x + y; });
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(count, (unsigned long long)n);
+}
+
+// X -> conj(X) * (H * w * inv) over [nt][ny][ch]: the products in fp64, one rounding; w = 2 for the columns that stand for their mirror
+// image too, inv = 1 / (nt ny nx)
+__global__ void __launch_bounds__(256) k_kf_mul(float* __restrict__ re, float* __restrict__ im, const float* __restrict__ H, int ch, int nx, double inv,
+                                                size_t total)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int kx = (int)(i % ch);
+    const bool alone = kx == 0 || (nx % 2 == 0 && kx == nx / 2);
+    const double h = (double)H[i] * (alone ? 1.0 : 2.0) * inv;
+    re[i] = (float)((double)re[i] * h);
+    im[i] = (float)(-((double)im[i] * h));
+}
+
+struct CloseArgs {
+    const float* Tc; const float* Ts; int Mp;       // twiddle pair of the x axis, [Kp][Mp]
+    const float* Bre; const float* Bim;             // the half spectrum, [N][K]
+    float* out;                                     // [N][M], dense
+    const double* means;                            // [ny * M]
+    const unsigned long long* bits; int wpf;        // the NaN bitmap of k_kf_prepare
+    double* part;                                   // [blocks]: the block's sum of y^2 over the samples that were not NaN
+    int M, N, K, ny, flags;                         // x, rows = nt * ny, kx <= nx / 2
+};
+
+// The closing x stage: Out[m][n] = Re sum_k (cos - i sin)(2 pi m k / nx) In[n][k] = sum_k (c br + s bi), the acc_re chain of
+// k_dft_stage<true, true> MFMA for MFMA (c br, then s bi, per k step), so the bits are that stage's real part; acc_im is never made.
+// Loads outside K x N read as 0, stores outside M x N are dropped, the twiddle's padding is 0, as there.
+__global__ void __launch_bounds__(256) k_dft_close(const CloseArgs a)
+{
+    // the four operand tiles of k_dft_stage, then (after the last MFMA) the 64 x 64 output tile [n][m]
+    __shared__ __attribute__((aligned(16))) float lds[4 * SP_TK * SP_LD];
+    __shared__ double sh[256];
+    static_assert(4 * SP_TK * SP_LD >= SP_TN * KF_CL_LD, "the output tile fits the operand tiles");
+    float (*As_c)[SP_LD] = (float (*)[SP_LD])lds;
+    float (*As_s)[SP_LD] = (float (*)[SP_LD])(lds + SP_TK * SP_LD);
+    float (*Bs_r)[SP_LD] = (float (*)[SP_LD])(lds + 2 * SP_TK * SP_LD);
+    float (*Bs_i)[SP_LD] = (float (*)[SP_LD])(lds + 3 * SP_TK * SP_LD);
+
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, lo = l & 15, hi = l >> 4;
+    const int m0 = blockIdx.y * SP_TM, n0 = blockIdx.x * SP_TN;
+    const int ak = tid >> 4, am = (tid & 15) * 4;
+    const int bk = tid & 15, bn = tid >> 4;             // k is the input's contiguous axis
+    sp_f32x4 pc, ps;
+    float pr[4], pi[4];
+    auto fetch = [&](int k0) {
+        pc = *(const sp_f32x4*)&a.Tc[(size_t)(k0 + ak) * a.Mp + m0 + am];
+        ps = *(const sp_f32x4*)&a.Ts[(size_t)(k0 + ak) * a.Mp + m0 + am];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = k0 + bk, n = n0 + bn + i * 16;
+            const bool in = k < a.K && n < a.N;
+            const long long q = (long long)n * a.K + k;
+            pr[i] = in ? a.Bre[q] : 0.f;
+            pi[i] = in ? a.Bim[q] : 0.f;
+        }
+    };
+
+    sp_f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = sp_f32x4{0.f, 0.f, 0.f, 0.f};
+    const int wm = (w & 1) * 32, wn = (w >> 1) * 32;
+    const int nk = (a.K + SP_TK - 1) / SP_TK;
+    fetch(0);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();
+        *(sp_f32x4*)&As_c[ak][am] = pc;
+        *(sp_f32x4*)&As_s[ak][am] = ps;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            Bs_r[bk][bn + i * 16] = pr[i];
+            Bs_i[bk][bn + i * 16] = pi[i];
+        }
+        __syncthreads();
+        if (kt + 1 < nk) fetch((kt + 1) * SP_TK);
+#pragma unroll
+        for (int s = 0; s < SP_TK / 4; ++s) {
+            const int kk = 4 * s + hi;
+            float ac[2], as[2], br[2], bi[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                ac[i] = As_c[kk][wm + 16 * i + lo];
+                as[i] = As_s[kk][wm + 16 * i + lo];
+                br[i] = Bs_r[kk][wn + 16 * i + lo];
+                bi[i] = Bs_i[kk][wn + 16 * i + lo];
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[i], br[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(as[i], bi[j], acc[i][j], 0, 0, 0);
+                }
+        }
+    }
+    // acc[i][j][r] = Out[m0 + wm + 16 i + 4 hi + r][n0 + wn + 16 j + lo]  ->  tile[n][m]: four consecutive m are one 16-byte write
+    __syncthreads();                                   // every wave has read the last operand tiles
+    float* tile = lds;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) *(sp_f32x4*)&tile[(wn + 16 * j + lo) * KF_CL_LD + wm + 16 * i + 4 * hi] = acc[i][j];
+    __syncthreads();
+    // a thread takes four consecutive x of one row, sixteen threads a row's 256 bytes, four rows per wave and pass
+    const bool restore = a.flags & KF_RESTORE_MEAN, keep = a.flags & KF_KEEP_NAN;
+    const bool wide = a.M % 4 == 0;                     // every row of out starts 16-byte aligned
+    double s2 = 0.0;
+#pragma unroll
+    for (int ps4 = 0; ps4 < 4; ++ps4) {
+        const int nl = ps4 * 16 + (tid >> 4), ml = (tid & 15) * 4;
+        const int n = n0 + nl, m = m0 + ml;
+        if (n >= a.N || m >= a.M) continue;
+        const sp_f32x4 y = *(const sp_f32x4*)&tile[nl * KF_CL_LD + ml];
+        const int t = n / a.ny, cell0 = (n % a.ny) * a.M + m;
+        sp_f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float v = __builtin_nanf("");
+            if (m + r < a.M) {
+                const int cell = cell0 + r;
+                const double mc = a.means[cell];
+                const bool nan = (a.bits[(size_t)t * a.wpf + (cell >> 6)] >> (cell & 63)) & 1ull;
+                if (!nan) s2 += (double)y[r] * (double)y[r];
+                if (mc == mc && !(nan && keep)) v = restore ? (float)((double)y[r] + mc) : y[r];
+            }
+            o[r] = v;
+        }
+        float* dst = a.out + (long long)n * a.M + m;
+        if (wide) *(sp_f32x4*)dst = o;                  // m + 3 < M: M and m are multiples of 4
+        else
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (m + r < a.M) dst[r] = o[r];
+    }
+    s2 = block_sum<256>(s2, sh);
+    if (tid == 0) a.part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s2;
+}
+
+}  // namespace wass
+
+struct wass_kfilter {
+    wass_kfilter(wass_ctx* c_, int nt_, int ny_, int nx_) : c(c_), nt(nt_), ny(ny_), nx(nx_), ch(nx_ / 2 + 1) {}
+    wass_ctx* c;
+    int nt, ny, nx, ch;
+    Arena arena;
+    float* cube = nullptr;          // [nt][ny][nx]: staging of a host cube, the prepared cube, then the result
+    float* a_re = nullptr; float* a_im = nullptr;   // [nt][ny][ch]
+    float* b_re = nullptr; float* b_im = nullptr;
+    float* H = nullptr;             // [nt][ny][ch]
+    unsigned long long* bits = nullptr;   // [nt][wpf]
+    double* means = nullptr;        // [ny][nx]
+    double* part = nullptr;         // the partial sums of k_kf_prepare (4 per block) or k_dft_close (1 per block)
+    double* sums = nullptr;         // [8]: s2_in, n_nan, n_empty, n_inf, s2_out
+    unsigned long long* count = nullptr;
+    int wpf = 0, nprep = 0;
+    size_t nclose = 0;
+    bool has_mask = false;
+    Twiddle tx, ty, tt;
+    // stage timing (wass_kfilter_set_timing): events around every stage of an apply, made on first use
+    bool timing = false;
+    hipEvent_t ev[KF_STAGES + 1] = {};
+    float stage_ms[KF_STAGES] = {};
+    ~wass_kfilter()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+void carve(wass_kfilter& h, Arena& a)
+{
+    const size_t cells = (size_t)h.ny * h.nx, win = (size_t)h.nt * cells, half = (size_t)h.nt * h.ny * h.ch;
+    h.wpf = (int)((cells + 63) / 64);
+    h.nprep = (int)((cells + 255) / 256);
+    h.nclose = (((size_t)h.nt * h.ny + SP_TN - 1) / SP_TN) * (size_t)((h.nx + SP_TM - 1) / SP_TM);
+    const size_t npart = (size_t)h.nprep * 4 > h.nclose ? (size_t)h.nprep * 4 : h.nclose;
+    h.cube = a.take<float>(win * 4);
+    h.a_re = a.take<float>(2 * half * 4); h.a_im = piece_at(h.a_re, half);
+    h.b_re = a.take<float>(2 * half * 4); h.b_im = piece_at(h.b_re, half);
+    h.H = a.take<float>(half * 4);
+    h.bits = a.take<unsigned long long>((size_t)h.nt * h.wpf * 8);
+    h.means = a.take<double>(cells * 8);
+    h.part = a.take<double>(npart * 8);
+    h.sums = a.take<double>(8 * 8);
+    h.count = a.take<unsigned long long>(256);
+    h.tx = make_twiddle(a, h.nx, h.nx);
+    h.ty = make_twiddle(a, h.ny, h.ny);
+    h.tt = make_twiddle(a, h.nt, h.nt);
+}
+
+size_t kfilter_bytes(int nt, int ny, int nx)
+{
+    wass_kfilter h(nullptr, nt, ny, nx);
+    carve(h, h.arena);
+    return h.arena.used;
+}
+
+int kfilter_apply(wass_kfilter* h, bool host, const float* in, size_t st, size_t sy, float* out, size_t ost, size_t osy, int flags,
+                  wass_kfilter_stats* stats)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    const int nt = h->nt, ny = h->ny, nx = h->nx, ch = h->ch;
+    if (!in || !out || sy < (size_t)nx || osy < (size_t)nx || (nt > 1 && (st < (size_t)nx || ost < (size_t)nx)) || (flags & ~7))
+        return set_err(c, WASS_ERR_INVALID_ARG, "bad cube pointer, strides or flags");
+    if (!h->has_mask) return set_err(c, WASS_ERR_INVALID_ARG, "no mask was set");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    const size_t cells = (size_t)ny * nx, half = (size_t)nt * ny * ch;
+    int nmark = 0;
+    auto mark = [&]() {                                   // the end of a stage (and the start of the next one)
+        if (h->timing && nmark <= KF_STAGES) (void)hipEventRecord(h->ev[nmark++], s);
+    };
+    if (h->timing)
+        for (hipEvent_t& e : h->ev)
+            if (!e) WASS_HIP(c, hipEventCreate(&e));
+    mark();
+    const float* src = in;
+    long long sst = (long long)st, ssy = (long long)sy;
+    if (host) {
+        WASS_HIP(c, upload_rows(h->cube, in, 4, nt, 0, ny, nx, st, sy, s));
+        src = h->cube;
+        sst = (long long)cells;
+        ssy = nx;
+    }
+    hipLaunchKernelGGL(k_kf_prepare, dim3(h->nprep), dim3(256), 0, s, src, sst, ssy, nt, ny, nx, (flags & KF_NO_CENTRE) ? 0 : 1, h->cube, h->means,
+                       h->bits, h->wpf, h->part);
+    hipLaunchKernelGGL(k_kf_fold, dim3(4), dim3(256), 0, s, (const double*)h->part, (size_t)h->nprep, 4, h->sums);
+    WASS_HIP(c, hipGetLastError());
+    mark();
+    int rc;
+    const long long plane = (long long)ny * ch;
+    DftArgs x = {h->tx.c, h->tx.s, h->tx.Mp, h->cube, nullptr, h->a_re, h->a_im, ch, nt * ny, nx, 1, nx, 0, 1, ch, 0};
+    if ((rc = launch_dft(c, s, x, false, true, 1))) return rc;
+    mark();
+    DftArgs y = {h->ty.c, h->ty.s, h->ty.Mp, h->a_re, h->a_im, h->b_re, h->b_im, ny, ch, ny, ch, 1, plane, ch, 1, plane};
+    if ((rc = launch_dft(c, s, y, true, false, nt))) return rc;
+    mark();
+    DftArgs t = {h->tt.c, h->tt.s, h->tt.Mp, h->b_re, h->b_im, h->a_re, h->a_im, nt, (int)plane, nt, plane, 1, 0, plane, 1, 0};
+    if ((rc = launch_dft(c, s, t, true, false, 1))) return rc;
+    mark();
+    hipLaunchKernelGGL(k_kf_mul, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, s, h->a_re, h->a_im, (const float*)h->H, ch, nx,
+                       1.0 / ((double)nt * (double)ny * (double)nx), half);
+    WASS_HIP(c, hipGetLastError());
+    mark();
+    DftArgs ti = {h->tt.c, h->tt.s, h->tt.Mp, h->a_re, h->a_im, h->b_re, h->b_im, nt, (int)plane, nt, plane, 1, 0, plane, 1, 0};
+    if ((rc = launch_dft(c, s, ti, true, false, 1))) return rc;
+    mark();
+    DftArgs yi = {h->ty.c, h->ty.s, h->ty.Mp, h->b_re, h->b_im, h->a_re, h->a_im, ny, ch, ny, ch, 1, plane, ch, 1, plane};
+    if ((rc = launch_dft(c, s, yi, true, false, nt))) return rc;
+    mark();
+    if (h->timing) {
+        // the yardstick of k_dft_close: the full stage on the same operands, its real part to the cube (k_dft_close writes it again)
+        // and its imaginary part to the b planes, which are free by now and hold 2 nt ny ch >= nt ny nx floats
+        DftArgs xi = {h->tx.c, h->tx.s, h->tx.Mp, h->a_re, h->a_im, h->cube, h->b_re, nx, nt * ny, ch, 1, ch, 0, 1, nx, 0};
+        if ((rc = launch_dft(c, s, xi, true, true, 1))) return rc;
+    }
+    mark();
+    CloseArgs cl = {h->tx.c, h->tx.s, h->tx.Mp, h->a_re, h->a_im, h->cube, h->means, h->bits, h->wpf, h->part, nx, nt * ny, ch, ny, flags};
+    const dim3 grid((nt * ny + SP_TN - 1) / SP_TN, (nx + SP_TM - 1) / SP_TM);
+    hipLaunchKernelGGL(k_dft_close, grid, dim3(256), 0, s, cl);
+    hipLaunchKernelGGL(k_kf_fold, dim3(1), dim3(256), 0, s, (const double*)h->part, h->nclose, 1, h->sums + 4);
+    WASS_HIP(c, hipGetLastError());
+    mark();
+    double sums[5];
+    WASS_HIP(c, hipMemcpyAsync(sums, h->sums, sizeof sums, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipStreamSynchronize(s));
+    if (sums[3] != 0.0) return set_err(c, WASS_ERR_INVALID_ARG, "the cube holds %.0f infinite samples", sums[3]);
+    if (stats) {
+        const double n = (double)nt * (double)cells - sums[1];
+        stats->var_in = n > 0 ? sums[0] / n : (double)NAN;
+        stats->var_out = n > 0 ? sums[4] / n : (double)NAN;
+        stats->n_nan = (unsigned long long)sums[1];
+        stats->n_empty_cells = (unsigned long long)sums[2];
+    }
+    WASS_HIP(c, download_rows(out, h->cube, 4, nt, 0, ny, nx, ost, osy, s, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    mark();
+    if (host || h->timing) WASS_HIP(c, hipStreamSynchronize(s));
+    if (h->timing)
+        for (int i = 0; i < KF_STAGES; ++i) WASS_HIP(c, hipEventElapsedTime(&h->stage_ms[i], h->ev[i], h->ev[i + 1]));
+    return WASS_OK;
+}
+
+}  // namespace
+
+extern "C" int wass_kfilter_set_timing(wass_kfilter* h, int on)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    h->timing = on != 0;
+    return WASS_OK;
+}
+
+extern "C" int wass_kfilter_last_timings(wass_kfilter* h, float* stage_ms)
+{
+    if (!h || !stage_ms) return WASS_ERR_INVALID_ARG;
+    memcpy(stage_ms, h->stage_ms, sizeof h->stage_ms);
+    return WASS_OK;
+}
+
+extern "C" int wass_kfilter_scratch_bytes(int nt, int ny, int nx, size_t* bytes)
+{
+    if (!bytes || !spec3d_dims_ok(nt, ny, nx)) return WASS_ERR_INVALID_ARG;
+    *bytes = kfilter_bytes(nt, ny, nx);
+    return WASS_OK;
+}
+
+extern "C" void wass_kfilter_destroy(wass_kfilter* h)
+{
+    if (!h) return;
+    if (h->c) (void)hipSetDevice(h->c->device);
+    if (h->arena.mem) (void)hipDeviceSynchronize();     // the device form of apply returns with its copy in flight
+    delete h;
+}
+
+extern "C" int wass_kfilter_create(wass_ctx* c, int nt, int ny, int nx, wass_kfilter** out)
+{
+    if (!c || !out) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!spec3d_dims_ok(nt, ny, nx)) return set_err(c, WASS_ERR_INVALID_ARG, "bad cube size %d x %d x %d (each axis 1 .. %d)", nt, ny, nx, SPEC_MAX_AXIS);
+    // rows, cells and the columns of the t stage are indexed with 32 bits
+    if ((size_t)ny * (nx / 2 + 1) > 0x7fffffffu || (size_t)nt * ny > 0x7fffff00u || (size_t)ny * nx > 0x7fffff00u)
+        return set_err(c, WASS_ERR_UNSUPPORTED, "cube too large");
+    const size_t total = kfilter_bytes(nt, ny, nx);
+    if (total > SPEC_SCRATCH_CAP)
+        return set_err(c, WASS_ERR_NO_MEMORY, "a %d x %d x %d cube needs %zu bytes of scratch, the cap is %zu", nt, ny, nx, total, SPEC_SCRATCH_CAP);
+    WASS_HIP(c, hipSetDevice(c->device));
+    wass_kfilter* h = new (std::nothrow) wass_kfilter(c, nt, ny, nx);
+    if (!h) return set_err(c, WASS_ERR_NO_MEMORY, "out of host memory");
+    int rc = h->arena.reserve(c, total, "the filter's scratch");
+    if (rc) {
+        wass_kfilter_destroy(h);
+        return rc;
+    }
+    carve(*h, h->arena);
+    hipStream_t s = c->ts();
+    rc = fill_twiddle(c, s, h->tx);
+    if (!rc) rc = fill_twiddle(c, s, h->ty);
+    if (!rc) rc = fill_twiddle(c, s, h->tt);
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(c, WASS_ERR_DEVICE, "filter set-up failed");
+    if (rc) {
+        wass_kfilter_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return WASS_OK;
+}
+
+extern "C" int wass_kfilter_set_mask(wass_kfilter* h, const float* H)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    if (!H) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    WASS_HIP(c, hipMemcpyAsync(h->H, H, (size_t)h->nt * h->ny * h->ch * 4, hipMemcpyHostToDevice, s));
+    WASS_HIP(c, hipStreamSynchronize(s));
+    h->has_mask = true;
+    return WASS_OK;
+}
+
+extern "C" int wass_kfilter_set_shell(wass_kfilter* h, const double* omega, const double* kappa_x, const double* kappa_y, const double* sigma0,
+                                      const unsigned char* used, double U, double V, double G, double f_lo, double f_hi, int complement,
+                                      uint64_t* n_pass)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    if (!omega || !kappa_x || !kappa_y || !sigma0 || !used) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (!(U == U && V == V && G >= 0)) return set_err(c, WASS_ERR_INVALID_ARG, "U, V must be numbers and G >= 0");
+    const int nt = h->nt, ny = h->ny, nx = h->nx;
+    const size_t cells = (size_t)ny * nx, half = (size_t)nt * ny * h->ch;
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    // the maps are the call's own scratch (9 bytes per cell), freed when it returns
+    double *d_om, *d_kx, *d_ky, *d_s0;
+    unsigned char* d_used;
+    auto lay = [&](Carve& a) {
+        d_om = a.take<double>((size_t)nt * 8);
+        d_kx = a.take<double>((size_t)nx * 8);
+        d_ky = a.take<double>((size_t)ny * 8);
+        d_s0 = a.take<double>(cells * 8);
+        d_used = a.take<unsigned char>(cells);
+    };
+    Arena maps;
+    if (int rc = maps.reserve(c, measure(lay), "the shell maps")) return rc;
+    lay(maps);
+    hipError_t e = hipMemcpyAsync(d_om, omega, (size_t)nt * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_kx, kappa_x, (size_t)nx * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_ky, kappa_y, (size_t)ny * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_s0, sigma0, cells * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_used, used, cells, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(h->count, 0, 8, s);
+    unsigned long long n = 0;
+    if (e == hipSuccess) {
+        ShellArgs a = {d_om, d_kx, d_ky, d_s0, d_used, U, V, G, f_lo, f_hi, nt, ny, nx, h->ch, complement ? 1 : 0};
+        hipLaunchKernelGGL(k_kf_shell, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, s, a, h->H, h->count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&n, h->count, 8, hipMemcpyDeviceToHost, s);
+    const int rc = finish(c, 0, e, s, "shell mask");      // synchronises: the maps are freed after this
+    if (rc) return rc;
+    if (n_pass) *n_pass = n;
+    h->has_mask = true;
+    return WASS_OK;
+}
+
+extern "C" int wass_kfilter_get_mask(wass_kfilter* h, float* H)
+{
+    if (!h) return WASS_ERR_INVALID_ARG;
+    wass_ctx* c = h->c;
+    if (!H) return set_err(c, WASS_ERR_INVALID_ARG, "null argument");
+    if (!h->has_mask) return set_err(c, WASS_ERR_INVALID_ARG, "no mask was set");
+    WASS_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->ts();
+    WASS_HIP(c, hipMemcpyAsync(H, h->H, (size_t)h->nt * h->ny * h->ch * 4, hipMemcpyDeviceToHost, s));
+    WASS_HIP(c, hipStreamSynchronize(s));
+    return WASS_OK;
+}
+
+extern "C" int wass_kfilter_apply(wass_kfilter* h, const float* cube, size_t stride_t, size_t stride_y, float* out, size_t out_stride_t,
+                                  size_t out_stride_y, int flags, wass_kfilter_stats* stats)
+{
+    return kfilter_apply(h, true, cube, stride_t, stride_y, out, out_stride_t, out_stride_y, flags, stats);
+}
+
+extern "C" int wass_kfilter_apply_dev(wass_kfilter* h, const float* d_cube, size_t stride_t, size_t stride_y, float* d_out, size_t out_stride_t,
+                                      size_t out_stride_y, int flags, wass_kfilter_stats* stats)
+{
+    return kfilter_apply(h, false, d_cube, stride_t, stride_y, d_out, out_stride_t, out_stride_y, flags, stats);
+}

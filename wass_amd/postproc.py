@@ -1781,3 +1781,197 @@ def dispersion_current(S, kx, ky, f, depth: float = np.inf, g: float = 9.81, thr
         rms = float(np.sqrt(np.float64(sums["sr2"]) / np.float64(sums["sw"])))
     return CurrentFit(U=U, V=V, speed=float(np.hypot(U, V)), direction=float(np.mod(np.arctan2(V, U), _TWO_PI)), n_bins=n, rms=rms,
                       singular=bool(singular), trace=trace)
+
+
+# ---- the wavenumber-frequency filter of the cube: a 3-D Fourier mask and its inverse (beyond the reference; DESIGN.md, "Dispersion
+# filter", is the specification).  As above, sqrt, tanh and atan2 are evaluated here; the device gets maps and compares.
+KFILTER_SCRATCH_CAP = 16 << 30
+_KF_RESTORE_MEAN, _KF_KEEP_NAN, _KF_NO_CENTRE = 1, 2, 4
+
+
+def fourier_filter_scratch_bytes(nt: int, ny: int, nx: int) -> int:
+    """Bytes of device scratch a Fourier3DFilter of nt x ny x nx holds, for host and device input alike; no GPU needed.  Above
+    KFILTER_SCRATCH_CAP the filter cannot be made (MemoryError)."""
+    from . import _lib
+    return _lib.scratch_bytes("kfilter", (int(nt), int(ny), int(nx)), f"a cube of {nt} x {ny} x {nx}: every axis must be 1 .. 8192")
+
+
+@dataclass
+class KFilterStats:
+    """What a filter run measured.  var_in and var_out are the mean squares of the prepared (centred, NaN at 0) cube and of the
+    filtered field before the mean is put back, over the samples that were not NaN; kept = var_out / var_in."""
+    var_in: float
+    var_out: float
+    kept: float
+    n_pass: int | None          # bins of the full cube with H = 1 (set_shell), None for an explicit mask
+    n_nan: int
+    n_empty_cells: int
+
+
+def check_even_mask(H, nx: int):
+    """ValueError unless H [nt][ny][nx // 2 + 1] is finite and even on the columns that stand alone: H[f, ky, kx] == H[-f, -ky, kx]
+    for kx = 0 and, nx even, kx = nx // 2."""
+    if not np.isfinite(H).all():
+        raise ValueError("the mask must be finite")
+    for kx in {0, nx // 2} if nx % 2 == 0 else {0}:
+        col = H[:, :, kx]
+        mirror = np.roll(col[::-1, ::-1], (1, 1), (0, 1))             # [f][ky] -> [-f][-ky]
+        if not np.array_equal(col, mirror):
+            raise ValueError(f"the mask is not even: H[f, ky, {kx}] != H[-f, -ky, {kx}] somewhere")
+
+
+class Fourier3DFilter(_Handle):
+    """wass_kfilter: out = real(ifftn(fftn(p) * H)) over nt x ny x nx cubes, p the cube minus every cell's time mean with NaN at 0.
+    Set H with set_mask or set_shell, then apply as often as needed; .stats holds the KFilterStats of the last apply."""
+
+    def __init__(self, nt: int, ny: int, nx: int, ctx: Context | None = None):
+        from . import _lib
+        self.nt, self.ny, self.nx = int(nt), int(ny), int(nx)
+        self.ch = self.nx // 2 + 1
+        if fourier_filter_scratch_bytes(self.nt, self.ny, self.nx) > KFILTER_SCRATCH_CAP:
+            raise MemoryError(f"a {self.nt} x {self.ny} x {self.nx} cube needs more than {KFILTER_SCRATCH_CAP} bytes of scratch")
+        self.ctx = Context(0) if ctx is None else ctx
+        h = C.c_void_p()
+        rc = self.ctx._lib.wass_kfilter_create(self.ctx._h, self.nt, self.ny, self.nx, C.byref(h))
+        if rc == _lib.WASS_ERR_NO_MEMORY:
+            raise MemoryError(self.ctx._lib.wass_last_error(self.ctx._h).decode())
+        self.ctx._check(rc)
+        self._h = h
+        self.stats, self.n_pass = None, None
+
+    def _destroy(self, h):
+        self.ctx._lib.wass_kfilter_destroy(h)
+
+    def set_mask(self, H):
+        """H: real, [nt][ny][nx // 2 + 1] in the un-shifted order of np.fft.rfftn, taken as float32; it must be even (check_even_mask)."""
+        H = np.ascontiguousarray(H, np.float32)
+        if H.shape != (self.nt, self.ny, self.ch):
+            raise ValueError(f"a mask of shape {H.shape}, expected {(self.nt, self.ny, self.ch)}")
+        check_even_mask(H, self.nx)
+        self.ctx._check(self.ctx._lib.wass_kfilter_set_mask(self._h, H.ctypes.data))
+        self.n_pass = None
+
+    def set_shell(self, omega, kappa_x, kappa_y, sigma0, used, U: float = 0.0, V: float = 0.0, G: float = 0.0, f_lo: float = -np.inf,
+                  f_hi: float = np.inf, complement: bool = False) -> int:
+        """The shell mask from maps on the fftshifted axes, all taken as given (a probe can use numbers that are exact in binary):
+        omega[nt], kappa_x[nx], kappa_y[ny], sigma0[ny][nx] float64, used[ny][nx] uint8.  f_lo and f_hi bound omega, in its units.
+        Returns the number of bins of the full cube that pass."""
+        omega, kappa_x, kappa_y, sigma0 = (np.ascontiguousarray(a, np.float64) for a in (omega, kappa_x, kappa_y, sigma0))
+        used = np.ascontiguousarray(used, np.uint8)
+        if omega.shape != (self.nt,) or kappa_x.shape != (self.nx,) or kappa_y.shape != (self.ny,) or sigma0.shape != (self.ny, self.nx) \
+                or used.shape != (self.ny, self.nx):
+            raise ValueError("omega[nt], kappa_x[nx], kappa_y[ny], sigma0[ny][nx] and used[ny][nx] are needed")
+        if not (np.isfinite(U) and np.isfinite(V) and G >= 0):
+            raise ValueError("U and V must be finite and G >= 0")
+        n = C.c_uint64()
+        _check_spec(self.ctx, self.ctx._lib.wass_kfilter_set_shell(self._h, omega.ctypes.data, kappa_x.ctypes.data, kappa_y.ctypes.data,
+                                                                   sigma0.ctypes.data, used.ctypes.data, float(U), float(V), float(G), float(f_lo),
+                                                                   float(f_hi), int(bool(complement)), C.byref(n)))
+        self.n_pass = int(n.value)
+        return self.n_pass
+
+    def mask(self) -> np.ndarray:
+        """The mask in use, float32 [nt][ny][nx // 2 + 1]."""
+        H = np.empty((self.nt, self.ny, self.ch), np.float32)
+        _check_spec(self.ctx, self.ctx._lib.wass_kfilter_get_mask(self._h, H.ctypes.data))
+        return H
+
+    STAGES = ("prepare", "x", "y", "t", "mul", "t_inv", "y_inv", "full_close_stage", "close", "copy_out")
+
+    def set_timing(self, on: bool = True):
+        """Bracket the stages of every apply with events (and run the full closing stage beside k_dft_close, as a yardstick)."""
+        self.ctx._check(self.ctx._lib.wass_kfilter_set_timing(self._h, int(bool(on))))
+
+    def last_timings(self) -> dict:
+        """{stage: milliseconds} of the last apply made with set_timing on."""
+        ms = (C.c_float * 10)()
+        self.ctx._check(self.ctx._lib.wass_kfilter_last_timings(self._h, C.byref(ms)))
+        return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+    def apply(self, data, out=None, restore_mean: bool = True, keep_nan: bool = True, centre: bool = True):
+        """The filtered cube: a host array or memmap gives a host array, a device tensor a device tensor; strided views pass as they
+        are and `out` may be `data`.  An infinite sample is a ValueError.  centre=False takes every cell's mean as 0."""
+        if tuple(int(v) for v in data.shape) != (self.nt, self.ny, self.nx):
+            raise ValueError(f"a cube of shape {tuple(data.shape)}, expected {(self.nt, self.ny, self.nx)}")
+        from . import _lib
+        data, (out,), suffix, a = _cube_io(data, (out,), "Fourier3DFilter.apply")
+        flags = (_KF_RESTORE_MEAN if restore_mean else 0) | (_KF_KEEP_NAN if keep_nan else 0) | (0 if centre else _KF_NO_CENTRE)
+        st = _lib.KFilterStatsC()
+        _check_spec(self.ctx, getattr(self.ctx._lib, "wass_kfilter_apply" + suffix)(self._h, *a[:3], *_ptr_strides(out), flags, C.byref(st)))
+        if suffix:
+            self.ctx.synchronize()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            kept = float(np.float64(st.var_out) / np.float64(st.var_in))
+        self.stats = KFilterStats(float(st.var_in), float(st.var_out), kept, self.n_pass, int(st.n_nan), int(st.n_empty_cells))
+        return out
+
+
+def dispersion_mask_maps(nt: int, ny: int, nx: int, du: float, dt: float, depth: float = np.inf, g: float = 9.81, k_min: float = 0.0,
+                         k_max: float = np.inf, sector=None) -> dict:
+    """The host maps of the shell mask on the fftshifted axes of dft_axes(nt, ny, nx, du, dt), with dispersion_current's quantities:
+    f, omega = 2 pi f, domega = 2 pi df, kappa_x = -kx, kappa_y = -ky, kmod, theta (spectral_label_maps'), sigma0 = sqrt(g kmod
+    tanh(kmod depth)) or sqrt(g kmod), and used (uint8 ny x nx): kmod != 0, k_min <= kmod <= k_max and, with sector = (direction,
+    half_width) in radians, the direction of travel theta within half_width of direction (the difference folded into [-pi, pi])."""
+    if not (du > 0 and dt > 0 and g > 0 and depth > 0):
+        raise ValueError("du, dt, g and depth must be positive")
+    kx, ky, f = dft_axes(nt, ny, nx, du, dt)
+    labels, _, _, kmod = spectral_label_maps(kx, ky, 1, 1.0, k_min, k_max)
+    KX, KY = np.meshgrid(-kx, -ky)
+    theta = np.mod(np.arctan2(KY, KX), _TWO_PI)
+    used = labels >= 0
+    if sector is not None:
+        direction, half_width = (float(v) for v in sector)
+        if not (np.isfinite(direction) and half_width >= 0):
+            raise ValueError("sector = (direction, half_width >= 0) in radians")
+        used &= np.abs(np.mod(theta - direction + np.pi, _TWO_PI) - np.pi) <= half_width
+    sigma0 = np.sqrt(g * kmod) if np.isinf(depth) else np.sqrt(g * kmod * np.tanh(kmod * depth))
+    df = 1.0 / (int(nt) * dt)
+    return {"f": f, "df": df, "omega": _TWO_PI * f, "domega": _TWO_PI * df, "kappa_x": -kx, "kappa_y": -ky, "kmod": kmod, "theta": theta,
+            "sigma0": sigma0, "used": used.astype(np.uint8)}
+
+
+def shell_band(maps: dict, f_min: float = 0.0, f_max: float = np.inf):
+    """(f_lo, f_hi) for set_shell: the omega of the first and last frequency above half a bin with f_min <= f <= f_max, so that the
+    device's comparison of omega decides exactly what a comparison of f decides; (inf, -inf) for a band without a bin."""
+    f = maps["f"]
+    P = np.flatnonzero((f > 0.5 * maps["df"]) & (f >= f_min) & (f <= f_max))
+    return (float(maps["omega"][P[0]]), float(maps["omega"][P[-1]])) if len(P) else (np.inf, -np.inf)
+
+
+def fourier_filter_3d(data, H, restore_mean: bool = True, keep_nan: bool = True, ctx: Context | None = None, out=None):
+    """real(ifftn(fftn(p) * H)) of a count x H x W float32 cube for an explicit real, even mask H [count][H][W // 2 + 1] in
+    np.fft.rfftn's order; p, the undoing, inputs and outputs as Fourier3DFilter.apply has them."""
+    if len(data.shape) != 3 or min(data.shape) < 1:
+        raise ValueError("data must be a count x H x W cube")
+    with Fourier3DFilter(*data.shape, ctx=ctx) as filt:
+        filt.set_mask(H)
+        return filt.apply(data, out=out, restore_mean=restore_mean, keep_nan=keep_nan)
+
+
+def dispersion_filter(data, du: float, dt: float, depth: float = np.inf, current=(0.0, 0.0), width: float = 2.0, f_min: float = 0.0,
+                      f_max: float = np.inf, k_min: float = 0.0, k_max: float = np.inf, sector=None, complement: bool = False, g: float = 9.81,
+                      restore_mean: bool = True, keep_nan: bool = True, ctx: Context | None = None, out=None):
+    """(cube, KFilterStats): the cube with everything removed that lies more than `width` frequency bins off the dispersion shell
+    omega = sigma0(k) + kappa . (U, V), or outside the band f_min .. f_max, k_min .. k_max and the sector (direction, half_width) of
+    directions of travel (radians, counter-clockwise from +x).  current is (U, V) or the CurrentFit of dispersion_current; a singular
+    fit is a ValueError.  complement=True returns what the filter removes instead.  keep_nan=False fills the NaN samples with the
+    filtered field (all-NaN cells stay NaN).  Inputs and outputs as Fourier3DFilter.apply has them."""
+    if len(data.shape) != 3 or min(data.shape) < 1:
+        raise ValueError("data must be a count x H x W cube")
+    if isinstance(current, CurrentFit):
+        if current.singular or not (np.isfinite(current.U) and np.isfinite(current.V)):
+            raise ValueError("the current fit is singular")
+        U, V = current.U, current.V
+    else:
+        U, V = (float(v) for v in current)
+        if not (np.isfinite(U) and np.isfinite(V)):
+            raise ValueError("the current must be finite")
+    if not width >= 0:
+        raise ValueError("width must be >= 0")
+    nt, ny, nx = (int(v) for v in data.shape)
+    maps = dispersion_mask_maps(nt, ny, nx, du, dt, depth, g, k_min, k_max, sector)
+    with Fourier3DFilter(nt, ny, nx, ctx=ctx) as filt:
+        filt.set_shell(maps["omega"], maps["kappa_x"], maps["kappa_y"], maps["sigma0"], maps["used"], U, V, width * maps["domega"],
+                       *shell_band(maps, f_min, f_max), complement)
+        res = filt.apply(data, out=out, restore_mean=restore_mean, keep_nan=keep_nan)
+        return res, filt.stats
